@@ -23,7 +23,12 @@ single-GPU packets, every rank the same mix); the partial films are summed to ra
 pixel bands.  `--scaling weak` gives every rank its own film of the same size (N independent renders).
 `--emulate-shard R/N` runs rank R's share of an N-GPU strong-scaling run alone on one GPU.
 
-Also reported (rank 0, N = 1):
+A plain run sets up, warms up, times the steps, writes the film with `--dump-outputs DIR` (DIR/film.npy:
+the film the last timed step completed, float32) and prints the result line.  Everything else runs after
+the timed steps only with `--full`: the film digest, the counters / phase-timing pass (`--no-diag` skips
+it), the C3 / C4 / C5 legs (`--no-legs`), and on rank 0 at N = 1 the two blocks below.
+
+Reported with `--full` (rank 0, N = 1):
 * `roofline` — the tile kernel's VALU issue roofline (`bound` "valu_issue"): wave64 VALU
   instructions per second of the iteration-0 launch against 256 CU x 4 SIMD / 2 clocks, from this
   run's own rocprofv3 PMC passes (`issue`: SQ counters, LDS busy, waits, and the vector-memory
@@ -142,6 +147,13 @@ def parse(argv=None):
     ap.add_argument("--c5-leg", choices=["auto", "on", "off"], default="auto",
                     help="c2: the C5 last-pass (iteration 9) gather leg (auto: with strong scaling, at every N)")
     ap.add_argument("--json-out", default=None)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything beside the headline figure: the film digest, "
+                         "the counters / phase-timing pass, the CPU baseline, the rocprofv3 roofline passes and "
+                         "the C3 / C4 / C5 legs (each still switched off by its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed steps computed (the film the last timed step completed, on the "
+                         "root) to DIR/film.npy, float32")
     ap.add_argument("--progress", action="store_true",
                     help="print a line per timed step to stderr (synchronises each step; long C4/C5 runs)")
     a = ap.parse_args(argv)
@@ -279,8 +291,11 @@ def main():
         dist.barrier()
     t1 = time.perf_counter()
     elapsed = t1 - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, frame)
     # the rendered film's bits (root): with packet-class films the same for every N dividing 8
-    digest = film_digest(frame) if (rank == 0 and args.workload != "synthetic" and not args.emulate_shard) else None
+    digest = (film_digest(frame)
+              if (args.full and rank == 0 and args.workload != "synthetic" and not args.emulate_shard) else None)
     gather_per_step = [a.elapsed_time(b) for a, b in events]
     gather_ms = float(np.mean(gather_per_step))
     if world > 1:
@@ -299,7 +314,7 @@ def main():
     # (the largest radius: the roofline's launch) and at the smallest-radius iteration the line times
     # (the scan-bound end of the render: C2 iteration 15 whenever --steps >= 16)
     diag, st, st_last = {}, None, None
-    if not args.no_diag:
+    if args.full and not args.no_diag:
         g.set_option(bre.OPT_COUNTERS, 1)
         g.set_option(bre.OPT_TIMING, 1)
         diag = wl.diagnostics(0)
@@ -344,7 +359,7 @@ def main():
         result["counters_last_iteration"] = last
     result.update(diag)
 
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         cpu = cpu_baseline(wl, args, gather_per_step)
         result["cpu_baseline"] = cpu["report"]
         result["speedup_vs_cpu"] = value / cpu["report"]["value"]
@@ -360,7 +375,7 @@ def main():
     # the other BASELINE configurations, outside the headline's timed region: C3's
     # iteration 0 on rank 0 at N = 1, and C4's iteration-0 gather on every rank (max over ranks), so an
     # N-GPU run also measures the north star's scaling configuration
-    if args.workload == "c2" and not args.no_legs and not args.emulate_shard:
+    if args.full and args.workload == "c2" and not args.no_legs and not args.emulate_shard:
         legs = {}
         if world == 1 and rank == 0:
             legs["c3"] = config_leg(args, bre, dmod, dev, "c3", 1, 0)
@@ -395,6 +410,25 @@ def film_digest(frame):
     img = frame.resolve().detach().to("cpu").contiguous().numpy()
     return {"sha256": hashlib.sha256(img.tobytes()).hexdigest()[:32], "sum": float(img.astype(np.float64).sum()),
             "classes": frame.classes, "pixels": int(img.shape[0])}
+
+
+DUMP_MAX_BYTES = 60_000_000  # 64 MB less room for the .npy headers
+
+
+def dump_outputs(path, frame):
+    """--dump-outputs: the film a caller of the timed path holds after the last timed step (the
+    root's resolved film, [pixels, 3] float32) as DIR/film.npy.  The scene, the photon and camera
+    sequences and the accumulation order are fixed by the arguments, so two builds run with the same
+    arguments are compared pixel for pixel.  A film above 64 MB is stored as a fixed, seeded sample
+    of its pixels (film.npy) with their indices (film_pixels.npy)."""
+    os.makedirs(path, exist_ok=True)
+    img = np.ascontiguousarray(frame.resolve().detach().to("cpu").numpy(), dtype=np.float32)
+    if img.nbytes > DUMP_MAX_BYTES:
+        row = img[0].nbytes + 8  # a pixel and its float64 index
+        idx = np.sort(np.random.default_rng(20240601).choice(img.shape[0], DUMP_MAX_BYTES // row, replace=False))
+        np.save(os.path.join(path, "film_pixels.npy"), idx.astype(np.float64))
+        img = np.ascontiguousarray(img[idx])
+    np.save(os.path.join(path, "film.npy"), img)
 
 
 def late_step(wl, steps):

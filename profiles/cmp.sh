@@ -8,6 +8,6 @@ tail -n 1 "$OUT/pytest_gpu.log"
 i=0
 for a in "$@"; do
   i=$((i+1))
-  timeout -k 10 300 python -u bench.py --steps 3 --warmup 1 --no-cpu $a > "$OUT/bench$i.log" 2>&1 || { tail -n 20 "$OUT/bench$i.log"; exit 1; }
+  timeout -k 10 300 python -u bench.py --full --steps 3 --warmup 1 --no-cpu $a > "$OUT/bench$i.log" 2>&1 || { tail -n 20 "$OUT/bench$i.log"; exit 1; }
   echo "[$a] $(grep '^{' "$OUT/bench$i.log" | python3 -c 'import json,sys; d=json.loads(sys.stdin.read()); print({k: d.get(k) for k in ("value","ms_per_step","gather_kernel_ms","candidates_per_estimate","contributions_per_estimate")})')"
 done

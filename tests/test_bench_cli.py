@@ -25,6 +25,40 @@ def test_defaults_are_the_c2_contract(bench):
     assert (c5.steps, c5.photons, c5.width) == (10, 50_000_000, 1024)
 
 
+def test_plain_run_is_lean_and_full_is_opt_in(bench):
+    a = bench.parse([])
+    assert a.full is False and a.dump_outputs is None
+    f = bench.parse(["--full", "--no-cpu", "--dump-outputs", "d"])
+    assert f.full is True and f.no_cpu is True and f.dump_outputs == "d"
+
+
+def test_dump_outputs_writes_the_film_as_float32(bench, tmp_path, monkeypatch):
+    import numpy as np
+    import torch
+
+    class Frame:
+        def __init__(self, n):
+            self.img = torch.arange(n * 3, dtype=torch.float32).reshape(n, 3)
+
+        def resolve(self):
+            return self.img
+
+    fr = Frame(100)
+    bench.dump_outputs(str(tmp_path / "a"), fr)
+    got = np.load(tmp_path / "a" / "film.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, fr.img.numpy())
+    assert not (tmp_path / "a" / "film_pixels.npy").exists()
+    # above the size limit: the same seeded pixel sample on every run, with its indices
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 400)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), fr)
+    film, pix = np.load(tmp_path / "b" / "film.npy"), np.load(tmp_path / "b" / "film_pixels.npy")
+    assert film.dtype == np.float32 and pix.dtype == np.float64
+    assert film.nbytes + pix.nbytes <= 400 and len(pix) == len(film) == 20 and len(set(pix)) == 20
+    assert np.array_equal(film, fr.img.numpy()[pix.astype(np.int64)])
+    assert np.array_equal(pix, np.load(tmp_path / "c" / "film_pixels.npy"))
+
+
 def test_roofline_fraction_is_achieved_over_peak(bench):
     class WL:
         def segments_per_gather(self):
