@@ -29,6 +29,10 @@ OPT_SHARD_RANK, OPT_SHARD_COUNT, OPT_TILE_LEAF = 8, 9, 10
 OPT_CHUNK_LEN, OPT_CHUNK_LEAF, OPT_SORT_SEGMENTS, OPT_SHARD_BLOCK, OPT_SHARD_MODE = 11, 12, 13, 14, 15
 OPT_FILM_CLASSES, FILM_CLASSES = 16, 8
 EMPTY_CHILD = -(2 ** 31)  # kEmptyChild (bre_device.h): no child
+# Node / Node4 (bre_device.h) as bre_device_check kinds 10 and 11 return them
+NODE_DTYPE = np.dtype([("lo", "<f4", (2, 3)), ("hi", "<f4", (2, 3)), ("child", "<i4", (2,)), ("parent", "<i4"),
+                       ("nleaf", "<i4")])
+NODE4_DTYPE = np.dtype([("lo", "<f4", (3, 4)), ("hi", "<f4", (3, 4)), ("child", "<i4", (4,)), ("pad", "<i4", (4,))])
 
 # Every entry point include/bre.h declares (checked by tests/test_abi.py).
 EXPORTS = [
@@ -459,6 +463,51 @@ class BeamGather:
         a = np.array([S], np.float32)
         self._check(self.lib.bre_device_check(self.h, 5, x.shape[0], _ptr(x), 1, _ptr(a), _ptr(y)))
         return [int(v) for v in y[:int(y[S])]]
+
+    def hierarchy_check(self, keys, boxes, leaf_size: int = 1, key_lo: int = 0):
+        """bre_device_check kind 10: the hierarchy kernels (k_karras, k_refit / k_single, k_collapse4) on
+        sorted uint64 keys [m] and member boxes [m, 6] (lo xyz, hi xyz).  Returns a dict: nodes (NODE_DTYPE
+        [nnodes]), leaf_parent (int32 [nleaf]), nodes4 (NODE4_DTYPE [nnodes]).  Keys whose `>> key_lo` is
+        not non-decreasing are refused by the library (BRE_ERR_INVALID_ARG) before any launch."""
+        k = np.ascontiguousarray(keys, dtype=np.uint64)
+        b = np.ascontiguousarray(boxes, dtype=np.float32).reshape(-1, 6)
+        m = k.shape[0]
+        if b.shape[0] != m or m < 1:
+            raise ValueError(f"hierarchy_check: {m} keys, {b.shape[0]} boxes")
+        nleaf = (m + leaf_size - 1) // leaf_size
+        nn = max(nleaf - 1, 1)
+        x = np.concatenate([k.view(np.uint32), b.view(np.uint32).ravel()])
+        y = np.zeros(16 * nn + nleaf + 32 * nn, np.uint32)
+        a = np.array([key_lo, leaf_size], np.float32)
+        self._check(self.lib.bre_device_check(self.h, 10, x.shape[0], _ptr(x), 2, _ptr(a), _ptr(y)))
+        return {"nodes": y[: 16 * nn].view(NODE_DTYPE).copy(),
+                "leaf_parent": y[16 * nn: 16 * nn + nleaf].view(np.int32).copy(),
+                "nodes4": y[16 * nn + nleaf:].view(NODE4_DTYPE).copy()}
+
+    def read_tree(self):
+        """bre_device_check kind 11: the current build, after set_beams / set_beams_device and before a
+        gather.  Returns a dict: nvalid, leaf_size, key_lo, nleaf (ints), keys (uint64 [nvalid], sorted as
+        the hierarchy read them), index (int32 [nvalid], sorted position -> input beam), boxes (float32
+        [nvalid, 6], each record's test box), nodes (NODE_DTYPE), leaf_parent (int32 [nleaf]) and nodes4
+        (NODE4_DTYPE, or None where the build made none)."""
+        s = self.stats()
+        nv, nn = int(s["n_beams_valid"]), int(s["n_nodes"])
+        y = np.zeros(8 + 9 * nv + 49 * nn + 1, np.uint32)
+        self._check(self.lib.bre_device_check(self.h, 11, y.shape[0], None, 0, None, _ptr(y)))
+        head = y[:8].view(np.int32)
+        nv2, ls, key_lo, nn2, has4, nleaf = int(y[:2].view(np.int64)[0]), *(int(v) for v in head[2:7])
+        if nv2 != nv or (nv and nn2 != nn):
+            raise RuntimeError(f"read_tree: the header ({nv2} valid, {nn2} nodes) disagrees with stats() ({nv}, {nn})")
+        o = 8
+        out = {"nvalid": nv, "leaf_size": ls, "key_lo": key_lo, "nleaf": nleaf}
+        out["keys"] = y[o: o + 2 * nv].view(np.uint64).copy(); o += 2 * nv
+        out["index"] = y[o: o + nv].view(np.int32).copy(); o += nv
+        out["boxes"] = y[o: o + 6 * nv].view(np.float32).reshape(nv, 6).copy(); o += 6 * nv
+        nn = nn2
+        out["nodes"] = y[o: o + 16 * nn].view(NODE_DTYPE).copy(); o += 16 * nn
+        out["leaf_parent"] = y[o: o + nleaf].view(np.int32).copy(); o += nleaf
+        out["nodes4"] = y[o: o + 32 * nn].view(NODE4_DTYPE).copy() if has4 else None
+        return out
 
     def close(self):
         if getattr(self, "h", None):

@@ -109,6 +109,8 @@ struct bre_ctx {
     int64_t nbeams = 0, nvalid = 0, nnodes = 0;
     BeamSet bset;  // the built set's radius layout (BeamRec)
     int built_leaf_size = 1;
+    int built_key_lo = 0;        // BuildBuffers::key_lo of the current build (bre_device_check kind 11)
+    bool build_scratch_ok = false;  // keys_alt / vals_alt / leaf_parent still hold the current build's (kind 11)
     DevMem in_start, in_end, in_radius, in_power;  // staging for host-pointer uploads
     DevMem box, cent, cbounds, nvalid_buf, keys, keys_alt, vals, vals_alt, sort_tmp, leaf_parent, visit, gbox;
     DevMem recs, pow, nodes;
@@ -285,6 +287,8 @@ bre_status build(bre_ctx *c, int64_t n, const float *start, const float *end, co
     c->nnodes = 0;
     c->roots_split = -1;
     c->nodes4_ok = false;
+    c->build_scratch_ok = false;
+    c->built_key_lo = 0;
     c->stats = bre_stats{};
     c->stats.n_beams = n;
     if (n == 0) return BRE_OK;
@@ -388,6 +392,8 @@ bre_status build(bre_ctx *c, int64_t n, const float *start, const float *end, co
     }
     c->nnodes = nnodes;
     c->built_leaf_size = K;
+    c->built_key_lo = b.key_lo;
+    c->build_scratch_ok = true;
     c->stats.n_nodes = nnodes;
     if (c->kernel == 0 || c->kernel == 4) {
         // the tile kernel's work roots and 4-wide view, here on the build's stream: with two contexts
@@ -411,6 +417,7 @@ bre_status check_flags(bre_ctx *c);
 // scratch (keys / vals / sort_tmp / leaf_parent / visit) is reused, it is dead after the build.
 bre_status gather_chunk(bre_ctx *c, const GatherArgs &a) {
     const int64_t np = c->nvalid;
+    c->build_scratch_ok = false;  // the chunk index reuses the beam build's keys / vals / leaf_parent
     if (c->timing) HIPCHK(c, hipEventRecord(c->ev[2], c->stream));
     ChunkBuild cb;
     HIPCHK(c, c->ch_bounds.ensure(12 * sizeof(unsigned int)));
@@ -1934,10 +1941,117 @@ int64_t bre_shard_segments(int64_t n_segments, int32_t rank, int32_t count, int3
     return packets * 64 - (last ? npk * 64 - n_segments : 0);
 }
 
+// bre_device_check kind 10: the hierarchy kernels (k_karras and k_refit, or k_single; then k_collapse4) on
+// the caller's sorted keys and member boxes, through the production launchers and their capacity checks,
+// in the check's own buffers (the context's current build is not touched).  x: m keys (2 words each), then
+// m boxes (lo xyz, hi xyz); y: the Node records, the leaf_parent words, the Node4 records.
+static bre_status check_hierarchy(bre_ctx *c, int64_t n, const float *x, int32_t n_aux, const float *aux, float *y) {
+    if (n_aux < 2 || !aux) return fail(c, BRE_ERR_INVALID_ARG, "bre_device_check: kind 10 needs aux = (key_lo, leaf_size)");
+    const int key_lo = (int)aux[0], K = (int)aux[1];
+    if (n < 8 || n % 8 || !x || !y || key_lo < 0 || key_lo > 63 || K < 1 || K > 64 || n / 8 > ((int64_t)1 << 24))
+        return fail(c, BRE_ERR_INVALID_ARG, "bre_device_check: kind 10 needs m <= 2^24 keys and boxes (8 words each), "
+                    "key_lo in 0..63 and leaf_size in 1..64");
+    const int64_t m = n / 8;
+    std::vector<unsigned long long> keys((size_t)m);
+    std::memcpy(keys.data(), x, (size_t)m * 8);
+    // the hierarchy is only ever launched on the order its sort left: a non-monotone sequence is refused here
+    for (int64_t i = 1; i < m; ++i)
+        if ((keys[(size_t)i] >> key_lo) < (keys[(size_t)i - 1] >> key_lo))
+            return fail(c, BRE_ERR_INVALID_ARG, "bre_device_check: kind 10 keys >> %d decrease at %lld: the hierarchy "
+                        "kernels need a non-decreasing sequence", key_lo, (long long)i);
+    std::vector<BeamRec> recs((size_t)m);  // zeroed; only lo / hi are read
+    const float *bx = x + 2 * m;
+    for (int64_t i = 0; i < m; ++i)
+        for (int k = 0; k < 3; ++k) {
+            recs[(size_t)i].lo[k] = bx[6 * i + k];
+            recs[(size_t)i].hi[k] = bx[6 * i + 3 + k];
+        }
+    const int64_t nleaf = (m + K - 1) / K;
+    const int64_t nnodes = nleaf > 1 ? nleaf - 1 : 1;
+    bre_status st = set_device(c);
+    if (st != BRE_OK) return st;
+    const size_t recs_off = ((size_t)m * 8 + 63) / 64 * 64;
+    const size_t n4_off = (size_t)nnodes * sizeof(Node), lp_off = n4_off + (size_t)nnodes * sizeof(Node4);
+    HIPCHK(c, c->chk_x.ensure(recs_off + (size_t)m * sizeof(BeamRec)));
+    HIPCHK(c, c->chk_y.ensure(lp_off + (size_t)nleaf * sizeof(int32_t)));
+    HIPCHK(c, c->chk_aux.ensure((size_t)nnodes * sizeof(unsigned int)));
+    char *dx = static_cast<char *>(c->chk_x.ptr), *dy = static_cast<char *>(c->chk_y.ptr);
+    BuildBuffers b{};
+    b.n = m;
+    b.leaf_size = K;
+    b.key_lo = key_lo;
+    b.slot = c->slot_passes;
+    b.keys_alt = reinterpret_cast<unsigned long long *>(dx);
+    b.recs = reinterpret_cast<BeamRec *>(dx + recs_off);
+    b.nodes = reinterpret_cast<Node *>(dy);
+    b.leaf_parent = reinterpret_cast<int32_t *>(dy + lp_off);
+    b.visit = c->chk_aux.as<unsigned int>();
+    b.nodes_cap = (uint64_t)nnodes;  // exactly what is read back below
+    b.leaf_parent_cap = (uint64_t)nleaf;
+    b.visit_cap = (uint64_t)nnodes;
+    Node4 *d4 = reinterpret_cast<Node4 *>(dy + n4_off);
+    HIPCHK(c, hipMemcpyAsync(b.keys_alt, keys.data(), (size_t)m * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(b.recs, recs.data(), (size_t)m * sizeof(BeamRec), hipMemcpyHostToDevice, c->stream));
+    // a single leaf has no leaf_parent word (k_single writes none): 0, the root
+    HIPCHK(c, hipMemsetAsync(b.leaf_parent, 0, (size_t)nleaf * sizeof(int32_t), c->stream));
+    HIPCHK(c, launch_hierarchy(b, m, c->stream));
+    HIPCHK(c, launch_collapse4(b.nodes, nnodes, d4, c->stream));
+    char *hy = reinterpret_cast<char *>(y);
+    HIPCHK(c, hipMemcpyAsync(hy, b.nodes, (size_t)nnodes * sizeof(Node), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(hy + n4_off, b.leaf_parent, (size_t)nleaf * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(hy + n4_off + (size_t)nleaf * 4, d4, (size_t)nnodes * sizeof(Node4), hipMemcpyDeviceToHost,
+                             c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return BRE_OK;
+}
+
+// bre_device_check kind 11: the context's current build read back (layout: include/bre.h); n = the words y holds
+static bre_status check_read_tree(bre_ctx *c, int64_t n, float *y) {
+    if (!y || n < 8) return fail(c, BRE_ERR_INVALID_ARG, "bre_device_check: kind 11 needs y of at least 8 words");
+    if (c->nvalid > 0 && !c->build_scratch_ok)
+        return fail(c, BRE_ERR_STATE, "bre_device_check: kind 11 reads a build after bre_set_beams* and before a "
+                    "kernel-5 gather has reused its sort buffers");
+    const int64_t nv = c->nvalid, nn = nv > 0 ? c->nnodes : 0;
+    const int K = c->built_leaf_size;
+    const int64_t nleaf = nv > 0 ? (nv + K - 1) / K : 0;
+    const bool has4 = nv > 0 && c->nodes4_ok;
+    const int64_t need = 8 + 9 * nv + 16 * nn + nleaf + (has4 ? 32 * nn : 0);
+    if (n < need)
+        return fail(c, BRE_ERR_INVALID_ARG, "bre_device_check: kind 11: y holds %lld words, the build needs %lld",
+                    (long long)n, (long long)need);
+    int32_t head[8] = {0, 0, K, c->built_key_lo, (int32_t)nn, has4 ? 1 : 0, (int32_t)nleaf, 0};
+    std::memcpy(head, &nv, sizeof(int64_t));
+    std::memcpy(y, head, sizeof(head));
+    if (nv == 0) return BRE_OK;
+    bre_status st = set_device(c);
+    if (st != BRE_OK) return st;
+    float *keys = y + 8, *idx = keys + 2 * nv, *box = idx + nv, *nodes = box + 6 * nv, *lp = nodes + 16 * nn,
+          *nodes4 = lp + nleaf;
+    std::vector<BeamRec> recs((size_t)nv);
+    HIPCHK(c, hipMemcpyAsync(keys, c->keys_alt.ptr, (size_t)nv * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(idx, c->vals_alt.ptr, (size_t)nv * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(recs.data(), c->recs.ptr, (size_t)nv * sizeof(BeamRec), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(nodes, c->nodes.ptr, (size_t)nn * sizeof(Node), hipMemcpyDeviceToHost, c->stream));
+    if (nleaf > 1)
+        HIPCHK(c, hipMemcpyAsync(lp, c->leaf_parent.ptr, (size_t)nleaf * 4, hipMemcpyDeviceToHost, c->stream));
+    if (has4)
+        HIPCHK(c, hipMemcpyAsync(nodes4, c->nodes4.ptr, (size_t)nn * sizeof(Node4), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (nleaf == 1) std::memset(lp, 0, 4);  // k_single writes no leaf_parent word: 0, the root
+    for (int64_t i = 0; i < nv; ++i)
+        for (int k = 0; k < 3; ++k) {
+            box[6 * i + k] = recs[(size_t)i].lo[k];
+            box[6 * i + 3 + k] = recs[(size_t)i].hi[k];
+        }
+    return BRE_OK;
+}
+
 bre_status bre_device_check(bre_ctx *c, int32_t kind, int64_t n, const float *x, int32_t n_aux, const float *aux,
                             float *y) {
     if (!c) return BRE_ERR_INVALID_ARG;
-    if (kind < 0 || kind > 9) return fail(c, BRE_ERR_INVALID_ARG, "bre_device_check: kind %d not in [0, 9]", kind);
+    if (kind < 0 || kind > 11) return fail(c, BRE_ERR_INVALID_ARG, "bre_device_check: kind %d not in [0, 11]", kind);
+    if (kind == 10) return check_hierarchy(c, n, x, n_aux, aux, y);
+    if (kind == 11) return check_read_tree(c, n, y);
     if (n < 0 || (n > 0 && (!x || !y))) return fail(c, BRE_ERR_INVALID_ARG, "bre_device_check: bad arrays");
     if (kind >= 6 && kind <= 8) {
         // the pass chain's one-wave primitives (bre_slot.hip) on caller data

@@ -351,8 +351,30 @@ bre_status bre_resolve_image(int64_t npix, const float *ld_rgb, int iteration, f
      kind 7: its exclusive scan of the n int32 words of x; y receives n + 1 int64 (the total last)
      kind 9: y[4i .. 4i + 3] = expf, logf, sinf, cosf of x[i] as the photon and camera passes compute
              them (include/bre_fmath.h: the x86-64 glibc libm's results bit for bit)
+     kind 10: the beam BVH's hierarchy kernels (k_karras and k_refit, or k_single for one leaf, then
+             k_collapse4) on caller data, through the build's own launchers and their capacity checks, in
+             buffers of the check's own (the context's current build is untouched).  x holds m 64-bit
+             keys (2 words each), then m member boxes of 6 floats (lo xyz, hi xyz): n = 8 m words.
+             aux = (key_lo, leaf_size): leaf l is the members [l * leaf_size, (l + 1) * leaf_size), its
+             key is keys[l * leaf_size], compared from bit key_lo up.  `keys >> key_lo` must be
+             non-decreasing, as behind the build's sort: any other sequence is refused on the host with
+             BRE_ERR_INVALID_ARG before any launch.  With nleaf = ceil(m / leaf_size) and nnodes =
+             max(nleaf - 1, 1), y receives nnodes Node records (16 words: lo[2][3], hi[2][3], child[2],
+             parent, nleaf), nleaf leaf_parent words (int32; 0 for a single leaf), then nnodes Node4
+             records (32 words: lo[3][4], hi[3][4], child[4], pad[4]).
+     kind 11: the context's current build read back, after bre_set_beams / bre_set_beams_device and before
+             a gather (a kernel-5 gather reuses the build's sort buffers: BRE_ERR_STATE after one).  x and
+             aux are unused; n is the number of 32-bit words y can hold, and a y too small for the build
+             is refused with BRE_ERR_INVALID_ARG (8 + 9 nvalid + 49 n_nodes + 1 words always suffice,
+             with nvalid and n_nodes from bre_get_stats).  y receives 8 header words { nvalid (int64),
+             built leaf size, key_lo, nnodes, 1 if Node4 records follow, nleaf, 0 } (int32), then the
+             nvalid sorted keys as the hierarchy read them (2 words each), the sorted-to-input beam index
+             (nvalid int32), each sorted record's test box (6 floats: lo xyz, hi xyz), the nnodes Node
+             records, the nleaf leaf_parent words (0 for a single leaf) and, where the build made them
+             (kernels 0 and 4), the nnodes Node4 records.
    so the tests can hold them against the reference's own primitive tests (src/tests/fp_tests.cpp,
-   find_interval.cpp) and against the compiler's correctly rounded sqrt and division. */
+   find_interval.cpp), against the compiler's correctly rounded sqrt and division, and (kinds 10, 11)
+   against a host restatement and validator of the hierarchy (tests/refpy_lbvh.py). */
 bre_status bre_device_check(bre_ctx *ctx, int32_t kind, int64_t n, const float *x, int32_t n_aux, const float *aux,
                             float *y);
 
