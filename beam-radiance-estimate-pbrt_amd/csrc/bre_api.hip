@@ -1784,7 +1784,18 @@ bre_status bre_gather(bre_ctx *c, int64_t nseg, const float *o, const float *p, 
     bre_status st = set_device(c);
     if (st != BRE_OK) return st;
     const size_t S = (size_t)nseg, P = (size_t)npix;
-    if (nseg == 0) return BRE_OK;
+    if (nseg == 0) {
+        // nothing to copy or launch, but the stats describe this gather, not the one before it
+        // (bre_gather_device with no segments reports the same through gather_device)
+        c->stats.n_segments = 0;
+        if (c->counters) {
+            c->stats.candidates = c->stats.contributions = 0;
+            c->stats.node_visits = c->stats.leaf_visits = c->stats.beam_evals = 0;
+            c->stats.ccp_wave_evals = c->stats.prefilter_rejects = c->stats.useful_beam_evals = 0;
+            c->stats.max_stack_depth = c->stats.queued_pairs = 0;
+        }
+        return BRE_OK;
+    }
     HIPCHK(c, c->g_o.ensure(S * 3 * sizeof(float)));
     HIPCHK(c, c->g_p.ensure(S * 3 * sizeof(float)));
     HIPCHK(c, c->g_d.ensure(S * 3 * sizeof(float)));

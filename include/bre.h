@@ -69,7 +69,17 @@ typedef enum bre_option {
                                 4 = the same kernel on a tree of BRE_OPT_LEAF_SIZE-beam leaves,
                                 2 = thread-per-segment traversal (an independent cross-check),
                                 5 = capsule-chunk index.  Values 1, 3 and 6 (round-1 kernels) are
-                                rejected.  Every kernel gives the same pair contributions. */
+                                rejected.  Every kernel gives the same pair contributions.
+                                The option binds twice.  At the next build (bre_set_beams*,
+                                bre_trace_photons) it picks the tree: 0 = the (start, end) order in
+                                BRE_OPT_TILE_LEAF-beam tiles; 2, 4, 5 = the centroid Morton order in
+                                BRE_OPT_LEAF_SIZE-beam leaves.  At each gather it picks the kernel,
+                                which walks whatever tree the last build left (0 and 4 are then the
+                                same kernel; 5 indexes the built beams anew and walks no beam tree).
+                                It may change between a build and a gather: all 16 (build, gather)
+                                pairs give the same candidate and contribution sets, and a gather's
+                                bits depend on the build and the gather kernel only, not on what
+                                ran in between (tests/test_context_reuse_gpu.py, walk C). */
     BRE_OPT_LEAF_SIZE = 4,   /* beams per BVH leaf cluster, 1..64 (default 1); applies at next build */
     BRE_OPT_SQRT_MODE = 5,   /* 0 = libstdc++ reading of WorldBound's sqrt (double), 1 = float */
     BRE_OPT_SPLIT = 6,       /* kernels 0/4: BVH subtrees per segment packet, power of two 1..1024 (default 256) */

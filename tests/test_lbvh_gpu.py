@@ -114,25 +114,29 @@ BEAM_SETS = ["fog-1", "fog-2", "fog-64", "fog-65", "fog-5000", "copies-4097", "l
 _CACHE = {}
 
 
+def case_of(oracle, b):
+    """A beam set with its valid input indices and every beam's equal-centroid group box."""
+    with np.errstate(invalid="ignore"):
+        box = oracle.beam_bounds(b["start"], b["end"], b["radius"])
+        cent = np.float32(0.5) * box[:, :3] + np.float32(0.5) * box[:, 3:]
+    valid = np.isfinite(box).all(axis=1) & np.isfinite(cent).all(axis=1)
+    gbox = box.copy()
+    vi = np.nonzero(valid)[0]
+    _, inv = np.unique(cent[vi] + np.float32(0), axis=0, return_inverse=True)  # -0 == +0
+    inv = inv.ravel()
+    glo = np.full((inv.max() + 1, 3), np.inf, np.float32)
+    ghi = np.full((inv.max() + 1, 3), -np.inf, np.float32)
+    np.minimum.at(glo, inv, box[vi, :3])
+    np.maximum.at(ghi, inv, box[vi, 3:])
+    gbox[vi, :3], gbox[vi, 3:] = glo[inv], ghi[inv]
+    grown = bool((gbox[vi] != box[vi]).any())  # some group's box is larger than a member's own
+    return (b, vi, gbox, int(inv.max() + 1), grown)
+
+
 def beam_case(synth, oracle, name):
-    """The beams, the valid input indices and every beam's equal-centroid group box, computed once."""
+    """The named set's case_of, computed once."""
     if name not in _CACHE:
-        b = _beam_set(synth, name)
-        with np.errstate(invalid="ignore"):
-            box = oracle.beam_bounds(b["start"], b["end"], b["radius"])
-            cent = np.float32(0.5) * box[:, :3] + np.float32(0.5) * box[:, 3:]
-        valid = np.isfinite(box).all(axis=1) & np.isfinite(cent).all(axis=1)
-        gbox = box.copy()
-        vi = np.nonzero(valid)[0]
-        _, inv = np.unique(cent[vi] + np.float32(0), axis=0, return_inverse=True)  # -0 == +0
-        inv = inv.ravel()
-        glo = np.full((inv.max() + 1, 3), np.inf, np.float32)
-        ghi = np.full((inv.max() + 1, 3), -np.inf, np.float32)
-        np.minimum.at(glo, inv, box[vi, :3])
-        np.maximum.at(ghi, inv, box[vi, 3:])
-        gbox[vi, :3], gbox[vi, 3:] = glo[inv], ghi[inv]
-        grown = bool((gbox[vi] != box[vi]).any())  # some group's box is larger than a member's own
-        _CACHE[name] = (b, vi, gbox, int(inv.max() + 1), grown)
+        _CACHE[name] = case_of(oracle, _beam_set(synth, name))
     return _CACHE[name]
 
 
@@ -154,8 +158,14 @@ def _configure(bre, g, cfg):
 
 
 def check_build(g, case, leaf_size, key_lo, has4):
-    b, vi, gbox = case[:3]
+    b = case[0]
     g.set_beams(b["start"], b["end"], b["radius"], b["power"])
+    return check_tree(g, case, leaf_size, key_lo, has4)
+
+
+def check_tree(g, case, leaf_size, key_lo, has4):
+    """The context's current build (of case's beams, however they were set) against the restatement."""
+    b, vi, gbox = case[:3]
     t = g.read_tree()
     st = g.stats()
     nv = vi.shape[0]
