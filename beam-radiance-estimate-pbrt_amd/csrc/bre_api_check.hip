@@ -1,0 +1,207 @@
+// bre_api_check.hip — bre_device_check, the test hooks of the C ABI: device functions, the pass
+// chain's one-wave primitives and the hierarchy kernels on caller data, and the read-back of the
+// context's current build.
+#include <cstring>
+#include <vector>
+
+#include "bre_ctx.h"
+
+using namespace bre;
+
+namespace {
+
+// bre_device_check kind 10: the hierarchy kernels (k_karras and k_refit, or k_single; then k_collapse4) on
+// the caller's sorted keys and member boxes, through the production launchers and their capacity checks,
+// in the check's own buffers (the context's current build is not touched).  x: m keys (2 words each), then
+// m boxes (lo xyz, hi xyz); y: the Node records, the leaf_parent words, the Node4 records.
+bre_status check_hierarchy(bre_ctx *c, int64_t n, const float *x, int32_t n_aux, const float *aux, float *y) {
+    if (n_aux < 2 || !aux) return fail(c, BRE_ERR_INVALID_ARG, "bre_device_check: kind 10 needs aux = (key_lo, leaf_size)");
+    const int key_lo = (int)aux[0], K = (int)aux[1];
+    if (n < 8 || n % 8 || !x || !y || key_lo < 0 || key_lo > 63 || K < 1 || K > 64 || n / 8 > ((int64_t)1 << 24))
+        return fail(c, BRE_ERR_INVALID_ARG, "bre_device_check: kind 10 needs m <= 2^24 keys and boxes (8 words each), "
+                    "key_lo in 0..63 and leaf_size in 1..64");
+    const int64_t m = n / 8;
+    std::vector<unsigned long long> keys((size_t)m);
+    std::memcpy(keys.data(), x, (size_t)m * 8);
+    // the hierarchy is only ever launched on the order its sort left: a non-monotone sequence is refused here
+    for (int64_t i = 1; i < m; ++i)
+        if ((keys[(size_t)i] >> key_lo) < (keys[(size_t)i - 1] >> key_lo))
+            return fail(c, BRE_ERR_INVALID_ARG, "bre_device_check: kind 10 keys >> %d decrease at %lld: the hierarchy "
+                        "kernels need a non-decreasing sequence", key_lo, (long long)i);
+    std::vector<BeamRec> recs((size_t)m);  // zeroed; only lo / hi are read
+    const float *bx = x + 2 * m;
+    for (int64_t i = 0; i < m; ++i)
+        for (int k = 0; k < 3; ++k) {
+            recs[(size_t)i].lo[k] = bx[6 * i + k];
+            recs[(size_t)i].hi[k] = bx[6 * i + 3 + k];
+        }
+    const int64_t nleaf = (m + K - 1) / K;
+    const int64_t nnodes = nleaf > 1 ? nleaf - 1 : 1;
+    BRE_TRY(set_device(c));
+    const size_t recs_off = ((size_t)m * 8 + 63) / 64 * 64;
+    const size_t n4_off = (size_t)nnodes * sizeof(Node), lp_off = n4_off + (size_t)nnodes * sizeof(Node4);
+    HIPCHK(c, c->chk_x.ensure(recs_off + (size_t)m * sizeof(BeamRec)));
+    HIPCHK(c, c->chk_y.ensure(lp_off + (size_t)nleaf * sizeof(int32_t)));
+    HIPCHK(c, c->chk_aux.ensure((size_t)nnodes * sizeof(unsigned int)));
+    char *dx = static_cast<char *>(c->chk_x.ptr), *dy = static_cast<char *>(c->chk_y.ptr);
+    BuildBuffers b{};
+    b.n = m;
+    b.leaf_size = K;
+    b.key_lo = key_lo;
+    b.slot = c->slot_passes;
+    b.keys_alt = reinterpret_cast<unsigned long long *>(dx);
+    b.recs = reinterpret_cast<BeamRec *>(dx + recs_off);
+    b.nodes = reinterpret_cast<Node *>(dy);
+    b.leaf_parent = reinterpret_cast<int32_t *>(dy + lp_off);
+    b.visit = c->chk_aux.as<unsigned int>();
+    b.nodes_cap = (uint64_t)nnodes;  // exactly what is read back below
+    b.leaf_parent_cap = (uint64_t)nleaf;
+    b.visit_cap = (uint64_t)nnodes;
+    Node4 *d4 = reinterpret_cast<Node4 *>(dy + n4_off);
+    HIPCHK(c, hipMemcpyAsync(b.keys_alt, keys.data(), (size_t)m * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(b.recs, recs.data(), (size_t)m * sizeof(BeamRec), hipMemcpyHostToDevice, c->stream));
+    // a single leaf has no leaf_parent word (k_single writes none): 0, the root
+    HIPCHK(c, hipMemsetAsync(b.leaf_parent, 0, (size_t)nleaf * sizeof(int32_t), c->stream));
+    HIPCHK(c, launch_hierarchy(b, m, c->stream));
+    HIPCHK(c, launch_collapse4(b.nodes, nnodes, d4, c->stream));
+    char *hy = reinterpret_cast<char *>(y);
+    HIPCHK(c, hipMemcpyAsync(hy, b.nodes, (size_t)nnodes * sizeof(Node), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(hy + n4_off, b.leaf_parent, (size_t)nleaf * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(hy + n4_off + (size_t)nleaf * 4, d4, (size_t)nnodes * sizeof(Node4), hipMemcpyDeviceToHost,
+                             c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return BRE_OK;
+}
+
+// bre_device_check kind 11: the context's current build read back (layout: include/bre.h); n = the words y holds
+bre_status check_read_tree(bre_ctx *c, int64_t n, float *y) {
+    if (!y || n < 8) return fail(c, BRE_ERR_INVALID_ARG, "bre_device_check: kind 11 needs y of at least 8 words");
+    if (c->nvalid > 0 && !c->build_scratch_ok)
+        return fail(c, BRE_ERR_STATE, "bre_device_check: kind 11 reads a build after bre_set_beams* and before a "
+                    "kernel-5 gather has reused its sort buffers");
+    const int64_t nv = c->nvalid, nn = nv > 0 ? c->nnodes : 0;
+    const int K = c->built_leaf_size;
+    const int64_t nleaf = nv > 0 ? (nv + K - 1) / K : 0;
+    const bool has4 = nv > 0 && c->nodes4_ok;
+    const int64_t need = 8 + 9 * nv + 16 * nn + nleaf + (has4 ? 32 * nn : 0);
+    if (n < need)
+        return fail(c, BRE_ERR_INVALID_ARG, "bre_device_check: kind 11: y holds %lld words, the build needs %lld",
+                    (long long)n, (long long)need);
+    int32_t head[8] = {0, 0, K, c->built_key_lo, (int32_t)nn, has4 ? 1 : 0, (int32_t)nleaf, 0};
+    std::memcpy(head, &nv, sizeof(int64_t));
+    std::memcpy(y, head, sizeof(head));
+    if (nv == 0) return BRE_OK;
+    BRE_TRY(set_device(c));
+    float *keys = y + 8, *idx = keys + 2 * nv, *box = idx + nv, *nodes = box + 6 * nv, *lp = nodes + 16 * nn,
+          *nodes4 = lp + nleaf;
+    std::vector<BeamRec> recs((size_t)nv);
+    HIPCHK(c, hipMemcpyAsync(keys, c->keys_alt.ptr, (size_t)nv * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(idx, c->vals_alt.ptr, (size_t)nv * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(recs.data(), c->recs.ptr, (size_t)nv * sizeof(BeamRec), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(nodes, c->nodes.ptr, (size_t)nn * sizeof(Node), hipMemcpyDeviceToHost, c->stream));
+    if (nleaf > 1)
+        HIPCHK(c, hipMemcpyAsync(lp, c->leaf_parent.ptr, (size_t)nleaf * 4, hipMemcpyDeviceToHost, c->stream));
+    if (has4)
+        HIPCHK(c, hipMemcpyAsync(nodes4, c->nodes4.ptr, (size_t)nn * sizeof(Node4), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (nleaf == 1) std::memset(lp, 0, 4);  // k_single writes no leaf_parent word: 0, the root
+    for (int64_t i = 0; i < nv; ++i)
+        for (int k = 0; k < 3; ++k) {
+            box[6 * i + k] = recs[(size_t)i].lo[k];
+            box[6 * i + 3 + k] = recs[(size_t)i].hi[k];
+        }
+    return BRE_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+bre_status bre_device_check(bre_ctx *c, int32_t kind, int64_t n, const float *x, int32_t n_aux, const float *aux,
+                            float *y) {
+    if (!c) return BRE_ERR_INVALID_ARG;
+    if (kind < 0 || kind > 11) return fail(c, BRE_ERR_INVALID_ARG, "bre_device_check: kind %d not in [0, 11]", kind);
+    if (kind == 10) return check_hierarchy(c, n, x, n_aux, aux, y);
+    if (kind == 11) return check_read_tree(c, n, y);
+    if (n < 0 || (n > 0 && (!x || !y))) return fail(c, BRE_ERR_INVALID_ARG, "bre_device_check: bad arrays");
+    if (kind >= 6 && kind <= 8) {
+        // the pass chain's one-wave primitives (bre_slot.hip) on caller data
+        BRE_TRY(set_device(c));
+        if (n == 0) return BRE_OK;
+        if (kind == 7) {  // exclusive scan of n int32 words; y: n + 1 int64 (the total last)
+            int32_t *dx = nullptr;
+            int64_t *dy = nullptr;
+            HIPCHK(c, c->chk_x.get((size_t)n, &dx));
+            HIPCHK(c, c->chk_y.get((size_t)(n + 1), &dy));
+            HIPCHK(c, c->chk_aux.ensure(slot_scan_temp_bytes(n)));
+            HIPCHK(c, hipMemcpyAsync(dx, x, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, slot_exclusive_scan(dx, dy, n, dy + n, c->chk_aux.ptr, c->stream));
+            HIPCHK(c, hipMemcpyAsync(y, dy, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            return BRE_OK;
+        }
+        // kind 6 / 8: stable sort of m = n / 2 64-bit (n 32-bit) keys by bits [aux[0], aux[1]), values = the
+        // input positions; y: the sorted keys, then the values
+        if (n_aux < 2 || !aux) return fail(c, BRE_ERR_INVALID_ARG, "bre_device_check: kinds 6 / 8 need aux[0..1] bits");
+        const int kb = kind == 6 ? 8 : 4;
+        if ((n * 4) % kb) return fail(c, BRE_ERR_INVALID_ARG, "bre_device_check: kind 6 needs an even word count");
+        const int64_t m = n * 4 / kb;
+        const size_t tb = slot_sort_temp_bytes(m, kb);
+        HIPCHK(c, c->chk_x.ensure((size_t)m * (kb + 4) * 2 + tb + 512));
+        char *base = static_cast<char *>(c->chk_x.ptr);
+        char *k0 = base, *k1 = k0 + (size_t)m * kb, *v0 = k1 + (size_t)m * kb, *v1 = v0 + (size_t)m * 4;
+        void *tmp = v1 + ((size_t)m * 4 + 256) / 256 * 256;
+        std::vector<int32_t> idx((size_t)m);
+        for (int64_t i = 0; i < m; ++i) idx[(size_t)i] = (int32_t)i;
+        HIPCHK(c, hipMemcpyAsync(k0, x, (size_t)m * kb, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(v0, idx.data(), (size_t)m * 4, hipMemcpyHostToDevice, c->stream));
+        const int b0 = (int)aux[0], b1 = (int)aux[1];
+        if (kb == 8)
+            HIPCHK(c, slot_sort_pairs(tmp, reinterpret_cast<unsigned long long *>(k0), reinterpret_cast<unsigned long long *>(k1),
+                                      reinterpret_cast<int32_t *>(v0), reinterpret_cast<int32_t *>(v1), m, b0, b1, c->stream));
+        else
+            HIPCHK(c, slot_sort_pairs(tmp, reinterpret_cast<unsigned int *>(k0), reinterpret_cast<unsigned int *>(k1),
+                                      reinterpret_cast<int32_t *>(v0), reinterpret_cast<int32_t *>(v1), m, b0, b1, c->stream));
+        HIPCHK(c, hipMemcpyAsync(y, k1, (size_t)m * kb, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(reinterpret_cast<char *>(y) + (size_t)m * kb, v1, (size_t)m * 4, hipMemcpyDeviceToHost,
+                                 c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return BRE_OK;
+    }
+    if (kind == 5) {
+        // the tile kernel's work roots (k_roots) of a caller tree: x = n / 16 Node records as words
+        if (n_aux < 1 || !aux) return fail(c, BRE_ERR_INVALID_ARG, "bre_device_check: kind 5 needs aux[0] = S");
+        const int S = (int)aux[0];
+        if (n < 16 || n % 16 || S < 1 || S > kMaxSplit || (S & (S - 1)))
+            return fail(c, BRE_ERR_INVALID_ARG, "bre_device_check: kind 5 needs whole Node records and S a power of two <= %d",
+                        kMaxSplit);
+        BRE_TRY(set_device(c));
+        Node *dx = nullptr;
+        int32_t *dy = nullptr;
+        HIPCHK(c, c->chk_x.get((size_t)n / 16, &dx));
+        HIPCHK(c, c->chk_y.get((size_t)(S + 1), &dy));
+        HIPCHK(c, hipMemcpyAsync(dx, x, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, c->roots_tmp.ensure(roots_scratch_bytes()));
+        HIPCHK(c, launch_roots(dx, S, dy, c->roots_tmp.ptr, c->stream));
+        HIPCHK(c, hipMemcpyAsync(y, dy, (size_t)(S + 1) * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return BRE_OK;
+    }
+    const bool need_aux = kind == 3 || kind == 4;
+    if (need_aux && (n_aux < 1 || !aux)) return fail(c, BRE_ERR_INVALID_ARG, "bre_device_check: kind %d needs aux", kind);
+    if (n == 0) return BRE_OK;
+    BRE_TRY(set_device(c));
+    const int64_t outs = kind == 9 ? 4 * n : (kind == 2 || kind == 4) ? 2 * n : n;
+    float *dx = nullptr, *dy = nullptr, *daux = nullptr;
+    HIPCHK(c, c->chk_x.get((size_t)n, &dx));
+    HIPCHK(c, c->chk_y.get((size_t)outs, &dy));
+    HIPCHK(c, c->chk_aux.get(need_aux ? (size_t)n_aux : 1, &daux));
+    HIPCHK(c, hipMemcpyAsync(dx, x, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    if (need_aux) HIPCHK(c, hipMemcpyAsync(daux, aux, (size_t)n_aux * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, launch_device_check(kind, n, dx, need_aux ? n_aux : 0, daux, dy, c->stream));
+    HIPCHK(c, hipMemcpyAsync(y, dy, (size_t)outs * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return BRE_OK;
+}
+
+}  // extern "C"

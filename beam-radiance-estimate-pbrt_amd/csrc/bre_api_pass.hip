@@ -1,0 +1,386 @@
+// bre_api_pass.hip — the photon and camera passes behind the C ABI: scene and medium checks, the
+// scene upload with its geometry cache, bre_trace_photons, bre_camera_pass, bre_get_segments and the
+// bre_render* loops over them.
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+#include "bre_ctx.h"
+
+using namespace bre;
+
+namespace {
+
+// Medium parameters: GridDensityMedium needs a density grid with a positive maximum (the ctor's
+// invMaxDensity = 1/maxDensity, grid.h:73-76); a non-uniform sigma_t is accepted as pbrt does
+// (its Error() only reports it, grid.h:66-70) and channel 0 is used.
+bre_status check_medium(bre_ctx *c, const bre_scene *scene, const char *fn) {
+    if (!scene) return fail(c, BRE_ERR_INVALID_ARG, "%s: null scene", fn);
+    if (scene->has_medium < BRE_MEDIUM_NONE || scene->has_medium > BRE_MEDIUM_GRID)
+        return fail(c, BRE_ERR_INVALID_ARG, "%s: unknown medium type %d", fn, scene->has_medium);
+    if (scene->has_medium != BRE_MEDIUM_GRID) return BRE_OK;
+    const int64_t nx = scene->grid_n[0], ny = scene->grid_n[1], nz = scene->grid_n[2];
+    if (nx < 1 || ny < 1 || nz < 1 || nx * ny * nz > BRE_MAX_GRID_CELLS)
+        return fail(c, BRE_ERR_INVALID_ARG, "%s: grid dimensions must be >= 1 with at most %d cells", fn,
+                    BRE_MAX_GRID_CELLS);
+    if (!scene->grid_density) return fail(c, BRE_ERR_INVALID_ARG, "%s: null grid_density", fn);
+    if (!(grid_max_density(scene) > 0))
+        return fail(c, BRE_ERR_INVALID_ARG, "%s: grid density maximum must be > 0", fn);
+    return BRE_OK;
+}
+
+// Triangle count in range and at least one area light (the passes need scene.lights non-empty)
+bre_status check_scene(bre_ctx *c, const bre_scene *scene, const char *fn) {
+    if (!scene) return fail(c, BRE_ERR_INVALID_ARG, "%s: null scene", fn);
+    const int cap = scene->triangles_ext ? BRE_MAX_SCENE_TRIANGLES : BRE_MAX_TRIANGLES;
+    if (scene->n_triangles < 1 || scene->n_triangles > cap)
+        return fail(c, BRE_ERR_INVALID_ARG, "%s: triangle count must be in 1..%d (%s)", fn, cap,
+                    scene->triangles_ext ? "triangles_ext" : "inline triangles; use triangles_ext for more");
+    const bre_triangle *tri = scene_triangles(scene);
+    int64_t lights = 0;
+    for (int i = 0; i < scene->n_triangles; ++i) lights += tri[i].emit != 0;
+    if (lights == 0) return fail(c, BRE_ERR_INVALID_ARG, "%s: the scene has no area light", fn);
+    return BRE_OK;
+}
+
+// 64-bit hash of the scene's triangles (the geometry cache key of upload_scene)
+uint64_t hash_triangles(const bre_scene *s) {
+    const bre_triangle *tri = scene_triangles(s);
+    const size_t bytes = (size_t)s->n_triangles * sizeof(bre_triangle);
+    const unsigned char *p = reinterpret_cast<const unsigned char *>(tri);
+    uint64_t h = 0x9e3779b97f4a7c15ull ^ (uint64_t)s->n_triangles;
+    size_t i = 0;
+    for (; i + 8 <= bytes; i += 8) {
+        uint64_t w;
+        memcpy(&w, p + i, 8);
+        h = (h ^ w) * 0x100000001b3ull;
+        h ^= h >> 29;
+    }
+    for (; i < bytes; ++i) h = (h ^ p[i]) * 0x100000001b3ull;
+    return h | 1ull;  // never 0 (= no scene)
+}
+
+// DevScene (+ the density grid of a GridDensityMedium) into ph_scene on the context's stream.  The
+// geometry (triangles, BVHAccel, lights) is rebuilt and uploaded only when the triangles change.
+bre_status upload_scene(bre_ctx *c, const bre_scene *scene) {
+    float *dd = nullptr;
+    if (scene->has_medium == BRE_MEDIUM_GRID) {
+        const size_t n = (size_t)scene->grid_n[0] * scene->grid_n[1] * scene->grid_n[2];
+        // uploaded only when the density values change (every pass of a render shares one grid)
+        const unsigned char *src = reinterpret_cast<const unsigned char *>(scene->grid_density);
+        const bool same = c->grid_dens.ptr && c->grid_bytes.size() == n * sizeof(float) &&
+                          memcmp(c->grid_bytes.data(), src, n * sizeof(float)) == 0;
+        if (!same) {
+            HIPCHK(c, c->grid_dens.get(n, &dd));
+            HIPCHK(c, hipMemcpyAsync(dd, scene->grid_density, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            c->grid_bytes.assign(src, src + n * sizeof(float));
+        }
+        dd = c->grid_dens.as<float>();
+    }
+    const uint64_t h = hash_triangles(scene);
+    // the geometry is reused only when the hash AND the bytes match (a hash collision between two
+    // scenes must not trace against the stale BVH and lights)
+    const size_t tri_bytes = (size_t)scene->n_triangles * sizeof(bre_triangle);
+    const bool same = h == c->sc_hash && c->sc_bytes.size() == tri_bytes &&
+                      (tri_bytes == 0 || memcmp(c->sc_bytes.data(), scene_triangles(scene), tri_bytes) == 0);
+    if (!same) {
+        HostScene hs;
+        prepare_geometry(scene, &hs);
+        if (hs.depth > kSceneStack)
+            return fail(c, BRE_ERR_INVALID_ARG, "scene BVH depth %d exceeds the %d-entry traversal stack (as in "
+                        "BVHAccel::Intersect)", hs.depth, kSceneStack);
+        const auto up = [&](DevMem &m, const void *src, size_t bytes) -> hipError_t {
+            hipError_t e = m.ensure(bytes > 0 ? bytes : 4);
+            if (e != hipSuccess || bytes == 0) return e;
+            return hipMemcpyAsync(m.ptr, src, bytes, hipMemcpyHostToDevice, c->stream);
+        };
+        HIPCHK(c, up(c->sc_tris, hs.tris.data(), hs.tris.size() * sizeof(PTri)));
+        HIPCHK(c, up(c->sc_nodes, hs.nodes.data(), hs.nodes.size() * sizeof(SceneNode)));
+        HIPCHK(c, up(c->sc_prims, hs.prims.data(), hs.prims.size() * sizeof(int32_t)));
+        HIPCHK(c, up(c->sc_light_tri, hs.light_tri.data(), hs.light_tri.size() * sizeof(int32_t)));
+        HIPCHK(c, up(c->sc_light_func, hs.light_func.data(), hs.light_func.size() * sizeof(float)));
+        HIPCHK(c, up(c->sc_light_cdf, hs.light_cdf.data(), hs.light_cdf.size() * sizeof(float)));
+        HIPCHK(c, hipStreamSynchronize(c->stream));  // the host vectors go out of scope
+        c->sc_head = hs.head;
+        c->sc_head.t = c->sc_tris.as<PTri>();
+        c->sc_head.nodes = c->sc_nodes.as<SceneNode>();
+        c->sc_head.prims = c->sc_prims.as<int32_t>();
+        c->sc_head.light_tri = c->sc_light_tri.as<int32_t>();
+        c->sc_head.light_func = c->sc_light_func.as<float>();
+        c->sc_head.light_cdf = c->sc_light_cdf.as<float>();
+        c->sc_hash = h;
+        const unsigned char *tb = reinterpret_cast<const unsigned char *>(scene_triangles(scene));
+        c->sc_bytes.assign(tb, tb + tri_bytes);
+    }
+    DevScene ds;
+    memcpy(&ds, &c->sc_head, sizeof(DevScene));  // padding bytes included: the record compares bytewise
+    prepare_medium(scene, &ds, dd);
+    // the scene record is copied only when it changes: in a render every pass uploads the same record,
+    // and a copy queued behind another context's gather waits for that gather's blocks (round 5 trace:
+    // a 1.6 KB upload took 110 ms in the two-context pipeline)
+    if (!c->ph_scene.ptr || memcmp(&ds, &c->ph_scene_host, sizeof(DevScene)) != 0) {
+        HIPCHK(c, c->ph_scene.ensure(sizeof(DevScene)));
+        HIPCHK(c, hipMemcpyAsync(c->ph_scene.ptr, &ds, sizeof(DevScene), hipMemcpyHostToDevice, c->stream));
+        // the host copies are read by the DMA before the call returns
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        memcpy(&c->ph_scene_host, &ds, sizeof(DevScene));
+    }
+    return BRE_OK;
+}
+
+bre_status check_params(bre_ctx *c, const bre_render_params *rp) {
+    if (!rp) return fail(c, BRE_ERR_INVALID_ARG, "bre_render: null params");
+    if (rp->width < 1 || rp->height < 1 || rp->start_iteration < 0 ||
+        rp->end_iteration < rp->start_iteration || rp->max_depth < 1 || rp->max_depth > BRE_MAX_DEPTH)
+        return fail(c, BRE_ERR_INVALID_ARG, "bre_render: bad parameters");
+    return BRE_OK;
+}
+
+struct FinalImage {
+    float *dst;
+    size_t n;
+};
+int keep_final_image(int32_t, const float *img, void *user) {
+    FinalImage *f = static_cast<FinalImage *>(user);
+    memcpy(f->dst, img, f->n * sizeof(float));
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+bre_status bre_trace_photons(bre_ctx *c, const bre_scene *scene, int64_t n_photons, int32_t iteration,
+                             int32_t max_depth, float beam_radius, int64_t *n_beams) {
+    if (!c) return BRE_ERR_INVALID_ARG;
+    if (n_beams) *n_beams = 0;
+    if (!scene) return fail(c, BRE_ERR_INVALID_ARG, "bre_trace_photons: null scene");
+    if (n_photons < 0 || iteration < 0) return fail(c, BRE_ERR_INVALID_ARG, "bre_trace_photons: negative count");
+    if (max_depth < 1 || max_depth > BRE_MAX_DEPTH)
+        return fail(c, BRE_ERR_INVALID_ARG, "bre_trace_photons: max_depth must be in [1, %d]", BRE_MAX_DEPTH);
+    BRE_TRY(check_scene(c, scene, "bre_trace_photons"));
+    BRE_TRY(check_medium(c, scene, "bre_trace_photons"));
+    BRE_TRY(set_device(c));
+    PassStream pass(c);
+    // an earlier asynchronous gather's device errors are reported before this call changes anything
+    BRE_TRY(check_flags(c));
+    BRE_TRY(upload_scene(c, scene));
+    const size_t N = (size_t)n_photons;
+    int32_t *counts = nullptr;
+    int64_t *offsets = nullptr;
+    HIPCHK(c, c->ph_counts.get(N + 1, &counts));
+    HIPCHK(c, c->ph_offsets.get(N + 1, &offsets));
+    HIPCHK(c, c->ph_tmp.ensure(count_scan_temp_bytes(n_photons) + 16));
+    const uint64_t seq0 = (uint64_t)iteration * (uint64_t)n_photons + 1;
+    const DevScene *ds = c->ph_scene.as<DevScene>();
+    if (c->timing) HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
+    const int sdepth = c->sc_head.stack_depth;
+    // single-trace form (bre_photon.hip): `cap` beam slots per photon, scratch at most 2.5 GB (62 slots at
+    // 1M photons: the re-trace of the photons with more beams than slots is the form's tail, 1.65 ms
+    // with 16 slots vs 1.41 with 64 at C2, profiles/r4/run36); below 4 slots, or with option 116 = 0,
+    // the two-trace form
+    int cap = c->photon_single ? (int)std::min<int64_t>(64, ((int64_t)5 << 29) / (40 * std::max<int64_t>(n_photons, 1))) : 0;
+    if (cap < 4) cap = 0;
+    if (c->photon_single >= 2) cap = c->photon_single;  // tests: a forced slot count (overflow paths)
+    BeamArrays &slots = c->ph_s, &in = c->in;
+    if (cap > 0) {
+        HIPCHK(c, slots.ensure(N * (size_t)cap));
+        HIPCHK(c, launch_photons(ds, sdepth, n_photons, seq0, max_depth, beam_radius, counts, nullptr, slots.start,
+                                 slots.end, slots.radius, slots.power, 2, cap, c->stream));
+    } else {
+        HIPCHK(c, launch_photons(ds, sdepth, n_photons, seq0, max_depth, beam_radius, counts, nullptr, nullptr, nullptr,
+                                 nullptr, nullptr, 0, 0, c->stream));
+    }
+    HIPCHK(c, launch_count_scan(c->ph_tmp.ptr, c->ph_tmp.cap, counts, offsets, n_photons, c->stream,
+                                c->slot_passes != 0));
+    int64_t total = 0;
+    BRE_TRY(read_small(c, {{&total, offsets + n_photons, sizeof(total)}}));
+    if (total > 0) {
+        HIPCHK(c, in.ensure((size_t)total));
+        if (cap > 0)
+            HIPCHK(c, launch_photon_slots(n_photons, cap, counts, offsets, slots.start, slots.end, slots.radius,
+                                          slots.power, in.start, in.end, in.radius, in.power, c->stream));
+        // every photon (two-trace form), or only those with more beams than slots
+        HIPCHK(c, launch_photons(ds, sdepth, n_photons, seq0, max_depth, beam_radius, counts, offsets, in.start, in.end,
+                                 in.radius, in.power, 1, cap, c->stream));
+    }
+    float photon_ms = 0.f;
+    if (c->timing) {
+        HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
+        HIPCHK(c, hipEventSynchronize(c->ev[1]));
+        HIPCHK(c, hipEventElapsedTime(&photon_ms, c->ev[0], c->ev[1]));
+    }
+    c->beams_kept = false;
+    BRE_TRY(build(c, total, in.start, in.end, in.radius, in.power));
+    c->beams_kept = true;
+    c->stats.n_photons = n_photons;
+    c->stats.photon_ms = photon_ms;
+    if (n_beams) *n_beams = total;
+    return check_flags(c);
+}
+
+bre_status bre_camera_pass(bre_ctx *c, const bre_scene *scene, int32_t width, int32_t height, int32_t iteration,
+                           int32_t max_depth, int32_t render_surfaces, int32_t render_media, float *d_surface,
+                           int64_t *n_segments) {
+    if (!c) return BRE_ERR_INVALID_ARG;
+    if (n_segments) *n_segments = 0;
+    BRE_TRY(check_scene(c, scene, "bre_camera_pass"));
+    if (width < 1 || height < 1 || (int64_t)width * height > (int64_t)INT32_MAX / BRE_MAX_DEPTH || iteration < 0)
+        return fail(c, BRE_ERR_INVALID_ARG, "bre_camera_pass: bad film size or iteration");
+    if (max_depth < 1 || max_depth > BRE_MAX_DEPTH)
+        return fail(c, BRE_ERR_INVALID_ARG, "bre_camera_pass: max_depth must be in [1, %d]", BRE_MAX_DEPTH);
+    BRE_TRY(check_medium(c, scene, "bre_camera_pass"));
+    BRE_TRY(set_device(c));
+    PassStream pass(c);
+    BRE_TRY(check_flags(c));  // an earlier gather's device errors, before this pass changes anything
+    // scene + camera/Halton tables (rebuilt when the scene or film changes)
+    BRE_TRY(upload_scene(c, scene));
+    if (c->cam_w != width || c->cam_h != height || memcmp(&c->cam_scene, scene, sizeof(bre_scene)) != 0) {
+        DevCamera cam;
+        std::vector<uint16_t> perms;
+        prepare_camera(scene, width, height, &cam, &perms);
+        HIPCHK(c, c->cam_dev.ensure(sizeof(DevCamera)));
+        HIPCHK(c, c->cam_perms.ensure(perms.size() * sizeof(uint16_t)));
+        HIPCHK(c, hipMemcpyAsync(c->cam_dev.ptr, &cam, sizeof(cam), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->cam_perms.ptr, perms.data(), perms.size() * sizeof(uint16_t),
+                                 hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));  // host vectors go out of scope
+        c->cam_w = width;
+        c->cam_h = height;
+        memcpy(&c->cam_scene, scene, sizeof(bre_scene));
+    }
+    const int64_t nslots = camera_slots(width, height);
+    const size_t S = (size_t)(nslots * max_depth);
+    int32_t *valid = nullptr, *depth = nullptr;
+    int64_t *offs = nullptr;
+    unsigned int *cam_flags = nullptr;
+    HIPCHK(c, c->cs.ensure(S));
+    HIPCHK(c, c->cs_valid.get(S, &valid));
+    HIPCHK(c, c->cam_offs.get(S + 1, &offs));
+    HIPCHK(c, c->cam_tmp.ensure(camera_scan_temp_bytes((int64_t)S) + 16));
+    HIPCHK(c, c->cam_flags.get(1, &cam_flags));
+    HIPCHK(c, fill_words(c, cam_flags, sizeof(unsigned int)));
+    CamSlots cs{c->cs.o, c->cs.p, c->cs.d, c->cs.t, c->cs.pix, valid};
+    if (c->timing) HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
+    HIPCHK(c, launch_camera(c->ph_scene.as<DevScene>(), c->sc_head.stack_depth, c->cam_dev.as<DevCamera>(),
+                            c->cam_perms.as<uint16_t>(),
+                            width, height, iteration, max_depth, render_surfaces, render_media, cs, d_surface,
+                            cam_flags, c->shard_rank, c->shard_count,
+                            c->shard_mode != 0 ? 0 : c->shard_block, c->film_classes, c->stream));
+    // exclusive scan of the slots' valid flags into cam_offs: total = offs[S-1] + valid[S-1]
+    HIPCHK(c, launch_camera_scan(c->cam_tmp.ptr, c->cam_tmp.cap, cs, nslots, max_depth, offs, c->stream,
+                                 c->slot_passes != 0));
+    int64_t last_off = 0;
+    int32_t last_valid = 0;
+    unsigned int flags = 0;
+    BRE_TRY(read_small(c, {{&last_off, offs + (S - 1), sizeof(int64_t)},
+                           {&last_valid, valid + (S - 1), sizeof(int32_t)},
+                           {&flags, cam_flags, sizeof(flags)}}));
+    const int64_t n = last_off + last_valid;
+    const size_t N = (size_t)(n > 0 ? n : 1);
+    HIPCHK(c, c->seg.ensure(N));
+    HIPCHK(c, c->seg_depth.get(N, &depth));
+    HIPCHK(c, launch_camera_compact(cs, nslots, max_depth, offs, c->seg.o, c->seg.p, c->seg.d, c->seg.t, c->seg.pix,
+                                    depth, c->stream));
+    float ms = 0.f;
+    if (c->timing) {
+        HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
+        HIPCHK(c, hipEventSynchronize(c->ev[1]));
+        HIPCHK(c, hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+    }
+    c->cam_nseg = n;
+    c->cam_npix = (int64_t)width * height;
+    c->stats.n_camera_segments = n;
+    c->stats.camera_ms = ms;
+    if (n_segments) *n_segments = n;
+    return check_flags(c);
+}
+
+bre_status bre_get_segments(bre_ctx *c, int64_t capacity, float *o, float *p, float *d, float *tmax, int32_t *pixel,
+                            int32_t *depth, int64_t *n_segments) {
+    if (!c) return BRE_ERR_INVALID_ARG;
+    if (capacity < 0) return fail(c, BRE_ERR_INVALID_ARG, "bre_get_segments: negative capacity");
+    if (n_segments) *n_segments = c->cam_nseg;
+    const int64_t k = capacity < c->cam_nseg ? capacity : c->cam_nseg;
+    if (k <= 0) return BRE_OK;
+    if (!o || !p || !d || !tmax || !pixel || !depth)
+        return fail(c, BRE_ERR_INVALID_ARG, "bre_get_segments: null array");
+    BRE_TRY(set_device(c));
+    const size_t K = (size_t)k;
+    HIPCHK(c, c->seg.download(K, o, p, d, tmax, pixel, c->stream));
+    HIPCHK(c, hipMemcpyAsync(depth, c->seg_depth.ptr, K * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    return check_flags(c);
+}
+
+bre_status bre_render_iteration(bre_ctx *c, const bre_scene *scene, const bre_render_params *rp, int32_t iteration,
+                                float *d_ld) {
+    if (!c) return BRE_ERR_INVALID_ARG;
+    BRE_TRY(check_params(c, rp));
+    if (!d_ld) return fail(c, BRE_ERR_INVALID_ARG, "bre_render_iteration: null Ld buffer");
+    const float R = bre_beam_radius_at(rp->initial_radius, rp->alpha, iteration);
+    // photonsperiteration <= 0 means the film's pixel count (photonbeam.h:37-39, the -1 default)
+    const int64_t photons =
+        rp->photons_per_iteration > 0 ? rp->photons_per_iteration : (int64_t)rp->width * rp->height;
+    BRE_TRY(bre_trace_photons(c, scene, photons, iteration, rp->max_depth, R, nullptr));
+    BRE_TRY(bre_camera_pass(c, scene, rp->width, rp->height, iteration, rp->max_depth, rp->render_surfaces,
+                            rp->render_media, d_ld, nullptr));
+    if (rp->render_media) return bre_gather_camera(c, R, d_ld);
+    return BRE_OK;
+}
+
+bre_status bre_render_progressive(bre_ctx *c, const bre_scene *scene, const bre_render_params *rp,
+                                  int32_t write_frequency, bre_image_fn on_image, void *user) {
+    if (!c) return BRE_ERR_INVALID_ARG;
+    bre_status st = check_params(c, rp);
+    if (st != BRE_OK) return st;
+    if (c->film_classes > 1) return fail(c, BRE_ERR_STATE, "bre_render*: BRE_OPT_FILM_CLASSES is for caller device films");
+    BRE_TRY(set_device(c));
+    const int64_t npix = (int64_t)rp->width * rp->height;
+    float *ld = nullptr;
+    HIPCHK(c, hipMalloc(&ld, (size_t)npix * 3 * sizeof(float)));
+    if (hipMemsetAsync(ld, 0, (size_t)npix * 3 * sizeof(float), c->stream) != hipSuccess)
+        st = fail(c, BRE_ERR_HIP, "bre_render: memset failed");
+    std::vector<float> h, img;
+    for (int it = rp->start_iteration; st == BRE_OK && it < rp->end_iteration; ++it) {
+        st = bre_render_iteration(c, scene, rp, it, ld);
+        if (st != BRE_OK) break;
+        // photonbeam.cpp:564: write at the last iteration and whenever (iter + 1) % writeFrequency == 0,
+        // negative frequencies included (-k fires every k iterations); the reference's default
+        // 1 << 31 wraps to INT32_MIN and never fires, and 0 (a division by zero there) means never
+        const bool periodic = write_frequency != 0 && write_frequency != INT32_MIN &&
+                              (it + 1) % write_frequency == 0;
+        const bool write = (it + 1 == rp->end_iteration) || periodic;
+        if (!write || !on_image) continue;
+        h.resize((size_t)npix * 3);
+        img.resize(h.size());
+        if (hipMemcpyAsync(h.data(), ld, h.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+            hipStreamSynchronize(c->stream) != hipSuccess) {
+            st = fail(c, BRE_ERR_HIP, "bre_render: copy-back failed");
+            break;
+        }
+        st = bre_resolve_image(npix, h.data(), it, img.data());  // L = Ld / (iter + 1), :578
+        if (st == BRE_OK && on_image(it, img.data(), user) != 0)
+            st = fail(c, BRE_ERR_STATE, "bre_render: image callback stopped the render after iteration %d", it);
+    }
+    const bre_status fst = check_flags(c);  // the last iteration's gather
+    if (st == BRE_OK) st = fst;
+    (void)hipFree(ld);
+    return st;
+}
+
+bre_status bre_render(bre_ctx *c, const bre_scene *scene, const bre_render_params *rp, float *image) {
+    if (!c) return BRE_ERR_INVALID_ARG;
+    BRE_TRY(check_params(c, rp));
+    if (c->film_classes > 1) return fail(c, BRE_ERR_STATE, "bre_render: BRE_OPT_FILM_CLASSES is for caller device films");
+    if (!image) return fail(c, BRE_ERR_INVALID_ARG, "bre_render: null image");
+    FinalImage f{image, (size_t)rp->width * rp->height * 3};
+    if (rp->end_iteration == rp->start_iteration) {
+        memset(image, 0, f.n * sizeof(float));
+        return BRE_OK;
+    }
+    // only the last iteration's image is kept (write_frequency 0 = at the end only)
+    return bre_render_progressive(c, scene, rp, 0, keep_final_image, &f);
+}
+
+}  // extern "C"

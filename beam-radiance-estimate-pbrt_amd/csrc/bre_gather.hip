@@ -715,7 +715,7 @@ __device__ __forceinline__ void tile_exact(TileShared &sh, int first, int n, con
     (void)L;
     (void)sr;
     // SegRec plane k of this packet at byte (seg0 / 64) * 4096 + k * 1024 + sl * 16 (packet-plane layout;
-    // one launch's records stay far below 4 GiB: bre_api.hip caps a launch's segments).  The beam
+    // one launch's records stay far below 4 GiB: bre_api_gather.hip caps a launch's segments).  The beam
     // record and power stay 64-bit pointer loads: a beam index may exceed 2^26 (2^28) records of 64
     // (16) bytes, past a 32-bit byte offset.
     const __amdgpu_buffer_rsrc_t srs = buf_rsrc(srec);
@@ -1171,7 +1171,7 @@ __global__ __launch_bounds__(kTileBlock, MINW) void k_gather_tile(
                 }
             }
             if (ovf) {
-                // never silent: the host turns the flag into BRE_ERR_STATE (bre_api.hip)
+                // never silent: the host turns the flag into BRE_ERR_STATE (bre_api.hip: check_flags)
                 if (lane == 0) atomicOr(&ctr->flags, kFlagStack);
                 break;
             }

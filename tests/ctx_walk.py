@@ -97,7 +97,7 @@ def film_base(npix):
 
 
 def compose(film, pixel, seg_rgb):
-    """The documented compose, sequentially in float32 (gather_segments' comment in bre_api.hip, bre_sort.hip
+    """The documented compose, sequentially in float32 (gather_segments' comment in bre_api_gather.hip, bre_sort.hip
     above k_pix_keys): per pixel s = 0, the pixel's seg_rgb rows added in the caller's order, then
     film[p] += s where s is not zero."""
     out = np.array(film, np.float32, copy=True)
