@@ -44,7 +44,10 @@ EXPORTS = [
     "bre_render_iteration", "bre_render",
     "bre_render_progressive", "bre_shard_segments", "bre_set_beams_sharded", "bre_gather_sharded",
     "bre_device_check", "bre_resolve_classes", "bre_film_add", "bre_set_gather_after", "bre_set_gather_events",
+    "bre_render_sharded", "bre_render_progressive_sharded",
 ]
+# bre_image_fn: int on_image(int32 iteration, const float *image_rgb, void *user)
+IMAGE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_int32, ctypes.POINTER(ctypes.c_float), ctypes.c_void_p)
 
 
 class BreError(RuntimeError):
@@ -149,6 +152,11 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.bre_set_beams_sharded.restype = I32
     lib.bre_gather_sharded.argtypes = [P, I32, I64, P, P, P, P, P, F, I64, P, P, P]
     lib.bre_gather_sharded.restype = I32
+    if hasattr(lib, "bre_render_sharded"):  # (absent from earlier libraries loaded for A/B timing)
+        lib.bre_render_sharded.argtypes = [P, I32, P, P, P]
+        lib.bre_render_sharded.restype = I32
+        lib.bre_render_progressive_sharded.argtypes = [P, I32, P, P, I32, IMAGE_FN, P]
+        lib.bre_render_progressive_sharded.restype = I32
     if hasattr(lib, "bre_resolve_classes"):  # (absent from round-4 libraries loaded for A/B timing)
         lib.bre_resolve_classes.argtypes = [P, I64, P, P]
         lib.bre_resolve_classes.restype = I32
@@ -563,6 +571,39 @@ def gather_sharded(ctxs, o, p, d, tmax, pixel=None, R=0.01, npix=0, accum=None, 
     if cnt is not None:
         res["counts"] = cnt
     return res
+
+
+def render_sharded(ctxs, scene, params):
+    """bre_render_sharded over BeamGather contexts (one per GPU): the whole render split over them;
+    returns the (H, W, 3) float32 image Ld / end_iteration, as BeamGather.render."""
+    img = np.zeros((params.height, params.width, 3), np.float32)
+    _check_group(ctxs, ctxs[0].lib.bre_render_sharded(_ctx_array(ctxs), len(ctxs), ctypes.addressof(scene),
+                                                      ctypes.addressof(params), _ptr(img)))
+    return img
+
+
+def render_progressive_sharded(ctxs, scene, params, write_frequency: int = 0, on_image=None):
+    """bre_render_progressive_sharded: on_image(iteration, image) is called on this thread with the
+    (H, W, 3) float32 image L = Ld / (iteration + 1) (a copy) at every write of the schedule; a true
+    return value stops the render (BreError, BRE_ERR_STATE).  An exception raised by on_image stops the
+    render too and is raised again here."""
+    raised = []
+
+    def call(it, image, _user):
+        try:
+            n = params.height * params.width * 3
+            img = np.ctypeslib.as_array(image, shape=(n,)).reshape(params.height, params.width, 3).copy()
+            return 1 if on_image(int(it), img) else 0
+        except BaseException as e:  # nothing may unwind through the C frames
+            raised.append(e)
+            return 1
+
+    fn = IMAGE_FN(call) if on_image is not None else ctypes.cast(None, IMAGE_FN)
+    st = ctxs[0].lib.bre_render_progressive_sharded(_ctx_array(ctxs), len(ctxs), ctypes.addressof(scene),
+                                                    ctypes.addressof(params), int(write_frequency), fn, None)
+    if raised:
+        raise raised[0]
+    _check_group(ctxs, st)
 
 
 def shard_segments(n_segments: int, rank: int, count: int, chunk: int = 1) -> int:

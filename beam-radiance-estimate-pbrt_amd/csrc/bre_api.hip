@@ -191,6 +191,10 @@ const IntOption kIntOptions[] = {
     // passes each instead of 8; round 6, profiles/r6/e13) / all bits (0, default).  Off: its first form hung the
     // full C5 render (the hierarchy saw unsorted low bits) and the fixed form is not yet measured on the GPU.
     {121, &bre_ctx::coarse_keys, 0, 1, "coarse keys mode must be 0 or 1"},
+    // internal: the film collective of the sharded calls, read from context 0: 0 (default) reads a source on context
+    // 0's device in place and stages only the other devices' through hipMemcpyPeerAsync / 1 stages every non-root
+    // source (tests: the cross-device path on one GPU)
+    {122, &bre_ctx::stage_all, 0, 1, "collective staging must be 0 or 1"},
 };
 }  // namespace
 

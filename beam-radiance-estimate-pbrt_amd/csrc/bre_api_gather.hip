@@ -415,6 +415,65 @@ bre_status gather_camera(bre_ctx *c, float R, float *d_accum, float *d_seg_rgb, 
 
 }  // namespace
 
+namespace bre {
+
+bre_status gather_host(bre_ctx *c, int64_t nseg, const float *o, const float *p, const float *d, const float *tmax,
+                       const int32_t *pixel, float R, int64_t npix, float *accum, float *seg_rgb, int32_t *seg_counts,
+                       bool film_stays) {
+    if (!c) return BRE_ERR_INVALID_ARG;
+    if (nseg < 0 || npix < 0) return fail(c, BRE_ERR_INVALID_ARG, "bre_gather: negative size");
+    if (c->film_classes > 1 && accum)
+        return fail(c, BRE_ERR_STATE, "bre_gather: BRE_OPT_FILM_CLASSES is for caller device films (bre_gather_device)");
+    if (nseg > 0 && (!o || !p || !d || !tmax))
+        return fail(c, BRE_ERR_INVALID_ARG, "bre_gather: null segment array");
+    if (accum && !pixel) return fail(c, BRE_ERR_INVALID_ARG, "bre_gather: accum_rgb given without seg_pixel");
+    if (accum && pixel) {
+        for (int64_t s = 0; s < nseg; ++s)
+            if (pixel[s] < 0 || pixel[s] >= npix)
+                return fail(c, BRE_ERR_INVALID_ARG, "bre_gather: seg_pixel[%lld]=%d out of [0,%lld)", (long long)s,
+                            pixel[s], (long long)npix);
+    }
+    BRE_TRY(set_device(c));
+    const size_t S = (size_t)nseg, P = (size_t)npix;
+    if (film_stays && accum && npix > 0) {
+        float *film = nullptr;
+        HIPCHK(c, c->g_accum.get(P * 3, &film));
+        HIPCHK(c, fill_words(c, film, P * 3 * sizeof(float)));
+    }
+    if (nseg == 0) {
+        // nothing to copy or launch, but the stats describe this gather, not the one before it
+        // (bre_gather_device with no segments reports the same through gather_device)
+        c->stats.n_segments = 0;
+        if (c->counters) {
+            c->stats.candidates = c->stats.contributions = 0;
+            c->stats.node_visits = c->stats.leaf_visits = c->stats.beam_evals = 0;
+            c->stats.ccp_wave_evals = c->stats.prefilter_rejects = c->stats.useful_beam_evals = 0;
+            c->stats.max_stack_depth = c->stats.queued_pairs = 0;
+        }
+        return BRE_OK;
+    }
+    SegArrays &g = c->g;
+    HIPCHK(c, g.ensure(S, pixel != nullptr));
+    HIPCHK(c, g.upload(S, o, p, d, tmax, pixel, c->stream));
+    float *daccum = nullptr, *dseg = nullptr;
+    int32_t *dcnt = nullptr;
+    if (accum && npix > 0) {
+        HIPCHK(c, c->g_accum.get(P * 3, &daccum));
+        if (!film_stays)
+            HIPCHK(c, hipMemcpyAsync(daccum, accum, P * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    }
+    if (seg_rgb) HIPCHK(c, c->g_seg_rgb.get(S * 3, &dseg));
+    if (seg_counts) HIPCHK(c, c->g_counts.get(S * 2, &dcnt));
+    BRE_TRY(gather_segments(c, nseg, g.o, g.p, g.d, g.t, pixel ? g.pix.as<int32_t>() : nullptr, R, npix, daccum, dseg,
+                            dcnt));
+    if (daccum && !film_stays) HIPCHK(c, hipMemcpyAsync(accum, daccum, P * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (dseg) HIPCHK(c, hipMemcpyAsync(seg_rgb, dseg, S * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (dcnt) HIPCHK(c, hipMemcpyAsync(seg_counts, dcnt, S * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    return check_flags(c);
+}
+
+}  // namespace bre
+
 extern "C" {
 
 bre_status bre_gather_camera(bre_ctx *c, float R, float *d_accum) {
@@ -438,50 +497,7 @@ bre_status bre_gather_device(bre_ctx *c, int64_t nseg, const float *o, const flo
 bre_status bre_gather(bre_ctx *c, int64_t nseg, const float *o, const float *p, const float *d, const float *tmax,
                       const int32_t *pixel, float R, int64_t npix, float *accum, float *seg_rgb,
                       int32_t *seg_counts) {
-    if (!c) return BRE_ERR_INVALID_ARG;
-    if (nseg < 0 || npix < 0) return fail(c, BRE_ERR_INVALID_ARG, "bre_gather: negative size");
-    if (c->film_classes > 1 && accum)
-        return fail(c, BRE_ERR_STATE, "bre_gather: BRE_OPT_FILM_CLASSES is for caller device films (bre_gather_device)");
-    if (nseg > 0 && (!o || !p || !d || !tmax))
-        return fail(c, BRE_ERR_INVALID_ARG, "bre_gather: null segment array");
-    if (accum && !pixel) return fail(c, BRE_ERR_INVALID_ARG, "bre_gather: accum_rgb given without seg_pixel");
-    if (accum && pixel) {
-        for (int64_t s = 0; s < nseg; ++s)
-            if (pixel[s] < 0 || pixel[s] >= npix)
-                return fail(c, BRE_ERR_INVALID_ARG, "bre_gather: seg_pixel[%lld]=%d out of [0,%lld)", (long long)s,
-                            pixel[s], (long long)npix);
-    }
-    BRE_TRY(set_device(c));
-    const size_t S = (size_t)nseg, P = (size_t)npix;
-    if (nseg == 0) {
-        // nothing to copy or launch, but the stats describe this gather, not the one before it
-        // (bre_gather_device with no segments reports the same through gather_device)
-        c->stats.n_segments = 0;
-        if (c->counters) {
-            c->stats.candidates = c->stats.contributions = 0;
-            c->stats.node_visits = c->stats.leaf_visits = c->stats.beam_evals = 0;
-            c->stats.ccp_wave_evals = c->stats.prefilter_rejects = c->stats.useful_beam_evals = 0;
-            c->stats.max_stack_depth = c->stats.queued_pairs = 0;
-        }
-        return BRE_OK;
-    }
-    SegArrays &g = c->g;
-    HIPCHK(c, g.ensure(S, pixel != nullptr));
-    HIPCHK(c, g.upload(S, o, p, d, tmax, pixel, c->stream));
-    float *daccum = nullptr, *dseg = nullptr;
-    int32_t *dcnt = nullptr;
-    if (accum && npix > 0) {
-        HIPCHK(c, c->g_accum.get(P * 3, &daccum));
-        HIPCHK(c, hipMemcpyAsync(daccum, accum, P * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    }
-    if (seg_rgb) HIPCHK(c, c->g_seg_rgb.get(S * 3, &dseg));
-    if (seg_counts) HIPCHK(c, c->g_counts.get(S * 2, &dcnt));
-    BRE_TRY(gather_segments(c, nseg, g.o, g.p, g.d, g.t, pixel ? g.pix.as<int32_t>() : nullptr, R, npix, daccum, dseg,
-                            dcnt));
-    if (daccum) HIPCHK(c, hipMemcpyAsync(accum, daccum, P * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    if (dseg) HIPCHK(c, hipMemcpyAsync(seg_rgb, dseg, S * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    if (dcnt) HIPCHK(c, hipMemcpyAsync(seg_counts, dcnt, S * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    return check_flags(c);
+    return gather_host(c, nseg, o, p, d, tmax, pixel, R, npix, accum, seg_rgb, seg_counts, false);
 }
 
 bre_status bre_film_add(bre_ctx *c, int64_t n_floats, float *d_src, float *d_dst, int32_t clear_src) {

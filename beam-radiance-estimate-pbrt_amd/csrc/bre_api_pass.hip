@@ -129,14 +129,6 @@ bre_status upload_scene(bre_ctx *c, const bre_scene *scene) {
     return BRE_OK;
 }
 
-bre_status check_params(bre_ctx *c, const bre_render_params *rp) {
-    if (!rp) return fail(c, BRE_ERR_INVALID_ARG, "bre_render: null params");
-    if (rp->width < 1 || rp->height < 1 || rp->start_iteration < 0 ||
-        rp->end_iteration < rp->start_iteration || rp->max_depth < 1 || rp->max_depth > BRE_MAX_DEPTH)
-        return fail(c, BRE_ERR_INVALID_ARG, "bre_render: bad parameters");
-    return BRE_OK;
-}
-
 struct FinalImage {
     float *dst;
     size_t n;
@@ -148,6 +140,26 @@ int keep_final_image(int32_t, const float *img, void *user) {
 }
 
 }  // namespace
+
+namespace bre {
+
+bre_status check_params(bre_ctx *c, const bre_render_params *rp) {
+    if (!rp) return fail(c, BRE_ERR_INVALID_ARG, "bre_render: null params");
+    if (rp->width < 1 || rp->height < 1 || rp->start_iteration < 0 ||
+        rp->end_iteration < rp->start_iteration || rp->max_depth < 1 || rp->max_depth > BRE_MAX_DEPTH)
+        return fail(c, BRE_ERR_INVALID_ARG, "bre_render: bad parameters");
+    return BRE_OK;
+}
+
+// photonbeam.cpp:564: write at the last iteration and whenever (iter + 1) % writeFrequency == 0,
+// negative frequencies included (-k fires every k iterations); the reference's default
+// 1 << 31 wraps to INT32_MIN and never fires, and 0 (a division by zero there) means never
+bool image_due(int32_t it, int32_t end_iteration, int32_t write_frequency) {
+    const bool periodic = write_frequency != 0 && write_frequency != INT32_MIN && (it + 1) % write_frequency == 0;
+    return it + 1 == end_iteration || periodic;
+}
+
+}  // namespace bre
 
 extern "C" {
 
@@ -345,13 +357,7 @@ bre_status bre_render_progressive(bre_ctx *c, const bre_scene *scene, const bre_
     for (int it = rp->start_iteration; st == BRE_OK && it < rp->end_iteration; ++it) {
         st = bre_render_iteration(c, scene, rp, it, ld);
         if (st != BRE_OK) break;
-        // photonbeam.cpp:564: write at the last iteration and whenever (iter + 1) % writeFrequency == 0,
-        // negative frequencies included (-k fires every k iterations); the reference's default
-        // 1 << 31 wraps to INT32_MIN and never fires, and 0 (a division by zero there) means never
-        const bool periodic = write_frequency != 0 && write_frequency != INT32_MIN &&
-                              (it + 1) % write_frequency == 0;
-        const bool write = (it + 1 == rp->end_iteration) || periodic;
-        if (!write || !on_image) continue;
+        if (!image_due(it, rp->end_iteration, write_frequency) || !on_image) continue;
         h.resize((size_t)npix * 3);
         img.resize(h.size());
         if (hipMemcpyAsync(h.data(), ld, h.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||

@@ -168,7 +168,7 @@ struct bre_ctx {
     int64_t partial_cap = (int64_t)4 << 30;                                            // 109, in bytes
     int beam_key = 2, margin = 1, tile_axis = 1, split_records = 0, film_compose = 1;  // 110 .. 114
     int photon_single = 1, pass_priority = 1, kernel_readback = BRE_KERNEL_READBACK;   // 116 .. 118
-    int slot_passes = 1, coarse_keys = 0;                                              // 119, 121
+    int slot_passes = 1, coarse_keys = 0, stage_all = 0;                               // 119, 121, 122
     // beam set
     int64_t nbeams = 0, nvalid = 0, nnodes = 0;
     bre::BeamSet bset;  // the built set's radius layout (BeamRec)
@@ -237,6 +237,15 @@ struct HostSpan {
 bre_status read_small(bre_ctx *c, std::initializer_list<HostSpan> spans);
 bre_status counters_block(bre_ctx *c, DevCounters **out);
 bre_status check_flags(bre_ctx *c);
+// bre_api_gather.hip: bre_gather; with film_stays the film starts at zero on the device (accum_rgb is only
+// the "a film is wanted" flag), stays there as c->g_accum and is not copied back (bre_gather_sharded)
+bre_status gather_host(bre_ctx *c, int64_t nseg, const float *o, const float *p, const float *d, const float *tmax,
+                       const int32_t *pixel, float R, int64_t npix, float *accum, float *seg_rgb, int32_t *seg_counts,
+                       bool film_stays);
+// bre_api_pass.hip
+bre_status check_params(bre_ctx *c, const bre_render_params *rp);
+// the write schedule of bre_render_progressive: is an image due after iteration `it`?
+bool image_due(int32_t it, int32_t end_iteration, int32_t write_frequency);
 // bre_api_build.hip
 bre_status build(bre_ctx *c, int64_t n, const float *start, const float *end, const float *radius, const float *power);
 

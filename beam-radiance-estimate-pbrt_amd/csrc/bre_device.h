@@ -293,6 +293,16 @@ hipError_t launch_seg_classes(int64_t n, int block, int classes, const int32_t *
 hipError_t launch_film_add(int64_t m, float *src, float *dst, int clear, hipStream_t st);
 // out[i] = sum over the classes of in[c][i] in class order, i < m
 hipError_t launch_resolve_classes(int64_t m, int classes, const float *in, float *out, hipStream_t st);
+// The film collective: dst[i] = (accumulate ? dst[i] + sum : sum), sum = ((src[0][i] + src[1][i]) + src[2][i]) + ...
+// over the n sources in table order, i < m (float32 adds in that order; one-wave workgroups, 16-byte loads
+// and stores where every base is 16-byte aligned).  The sources are device pointers readable on the
+// stream's device; dst may be one of them.
+constexpr int kFilmSources = 8;
+struct FilmSources {
+    const float *src[kFilmSources];
+    int n;
+};
+hipError_t launch_film_sum(const FilmSources &t, int64_t m, float *dst, int accumulate, hipStream_t st);
 
 hipError_t launch_sort_segments(const SegSort &s, hipStream_t st);
 hipError_t launch_packet_pick(int64_t n, int64_t m, int rank, int count, int chunk, const float *o, const float *p,

@@ -371,7 +371,54 @@ __global__ __launch_bounds__(kBlock) void k_film_add(int64_t m, float *src, floa
     }
 }
 
+// The film collective of the multi-context calls (bre_api_shard.hip): the sources of the by-value table
+// added in table order, ((s_0 + s_1) + s_2) + ..., float32 adds with no contraction and no reassociation
+// (one thread owns an element and adds serially).  acc == 0 stores that sum itself (bre_resolve_classes'
+// operation when the table holds the class planes), acc != 0 stores dst + sum.  dst may be one of the
+// sources: every source element is read before dst's is stored.  V = float4 where every base is 16-byte
+// aligned (the launcher's choice; a plane's base c * 3 * npix floats is not for every film), m then counts
+// float4s.
+template <typename V>
+__device__ __forceinline__ V film_add2(V a, V b);
+template <>
+__device__ __forceinline__ float film_add2<float>(float a, float b) { return a + b; }
+template <>
+__device__ __forceinline__ float4 film_add2<float4>(float4 a, float4 b) {
+    return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
+}
+template <typename V>
+__global__ __launch_bounds__(kBlock) void k_film_sum(FilmSources t, int64_t m, V *dst, int acc) {
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < m; i += (int64_t)gridDim.x * kBlock) {
+        V v = reinterpret_cast<const V *>(t.src[0])[i];
+        for (int k = 1; k < t.n; ++k) v = film_add2(v, reinterpret_cast<const V *>(t.src[k])[i]);
+        dst[i] = acc ? film_add2(dst[i], v) : v;
+    }
+}
+
 }  // namespace
+
+hipError_t launch_film_sum(const FilmSources &t, int64_t m, float *dst, int accumulate, hipStream_t st) {
+    if (m <= 0) return hipSuccess;
+    if (t.n < 1 || t.n > kFilmSources) return hipErrorInvalidValue;
+    bool aligned = (reinterpret_cast<uintptr_t>(dst) & 15) == 0;
+    for (int k = 0; k < t.n; ++k) aligned = aligned && (reinterpret_cast<uintptr_t>(t.src[k]) & 15) == 0;
+    const auto grid = [](int64_t n) { return dim3((unsigned)std::min<int64_t>((n + 4 * kBlock - 1) / (4 * kBlock), 1 << 20)); };
+    const int64_t m4 = aligned ? m / 4 : 0;
+    if (m4 > 0) {
+        hipLaunchKernelGGL(k_film_sum<float4>, grid(m4), dim3(kBlock), 0, st, t, m4, reinterpret_cast<float4 *>(dst),
+                           accumulate);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    if (m4 * 4 < m) {
+        // the whole film (unaligned bases), or the last m % 4 floats behind the float4s
+        FilmSources r = t;
+        for (int k = 0; k < r.n; ++k) r.src[k] += m4 * 4;
+        hipLaunchKernelGGL(k_film_sum<float>, grid(m - m4 * 4), dim3(kBlock), 0, st, r, m - m4 * 4, dst + m4 * 4,
+                           accumulate);
+    }
+    return hipGetLastError();
+}
 
 hipError_t launch_film_add(int64_t m, float *src, float *dst, int clear, hipStream_t st) {
     if (m <= 0) return hipSuccess;

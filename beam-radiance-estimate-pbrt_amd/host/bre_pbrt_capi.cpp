@@ -93,11 +93,17 @@ bre_status bre_pbrt_get_film(const bre_pbrt *p, int32_t *xres, int32_t *yres, fl
 
 bre_status bre_pbrt_render(const bre_pbrt *p, int32_t device, int32_t quick, const char *outfile,
                            int32_t write_files, float *image_rgb) {
+    return bre_pbrt_render_devices(p, &device, 1, quick, outfile, write_files, image_rgb);
+}
+
+bre_status bre_pbrt_render_devices(const bre_pbrt *p, const int32_t *devices, int32_t n_devices, int32_t quick,
+                                   const char *outfile, int32_t write_files, float *image_rgb) {
     if (!p || !p->ok) return BRE_ERR_INVALID_ARG;
+    if (!devices || n_devices < 1 || n_devices > 8) return BRE_ERR_INVALID_ARG;
     if (p->scene.integratorName != "photonbeam") return BRE_ERR_INVALID_ARG;
     FilmDesc film = p->scene.film;
     if (outfile) film.filename = outfile;
-    PhotonBeamIntegrator integ(params_of(p, quick), film, device);
+    PhotonBeamIntegrator integ(params_of(p, quick), film, std::vector<int>(devices, devices + n_devices));
     if (!integ.Context()) return BRE_ERR_NO_DEVICE;
     integ.writeFiles = write_files != 0;
     if (!integ.Render(p->scene.scene)) return BRE_ERR_STATE;

@@ -143,15 +143,32 @@ void ResolveImage(const std::vector<float> &pixelLd, int iteration, std::vector<
 }
 
 PhotonBeamIntegrator::PhotonBeamIntegrator(const PhotonBeamParams &params, const FilmDesc &film, int device)
+    : PhotonBeamIntegrator(params, film, std::vector<int>{device}) {}
+
+PhotonBeamIntegrator::PhotonBeamIntegrator(const PhotonBeamParams &params, const FilmDesc &film,
+                                           const std::vector<int> &devices)
     : params_(params), film_(film) {
-    const bre_status st = bre_create(device, &ctx_);
-    if (st != BRE_OK) {
-        ctx_ = nullptr;
-        err_ = "bre_create failed with status " + std::to_string((int)st);
+    if (devices.empty()) err_ = "no device given";
+    for (int dev : devices) {
+        bre_ctx *c = nullptr;
+        const bre_status st = bre_create(dev, &c);
+        if (st != BRE_OK) {
+            err_ = "bre_create failed with status " + std::to_string((int)st);
+            break;
+        }
+        ctxs_.push_back(c);
     }
+    if (ctxs_.size() != devices.size()) {
+        // all or nothing: Context() is null and Render fails
+        for (bre_ctx *c : ctxs_) bre_destroy(c);
+        ctxs_.clear();
+    }
+    ctx_ = ctxs_.empty() ? nullptr : ctxs_[0];
 }
 
-PhotonBeamIntegrator::~PhotonBeamIntegrator() { bre_destroy(ctx_); }
+PhotonBeamIntegrator::~PhotonBeamIntegrator() {
+    for (bre_ctx *c : ctxs_) bre_destroy(c);
+}
 
 std::string PfmFilename(const std::string &filename) {
     const size_t dot = filename.find_last_of('.');
@@ -198,7 +215,11 @@ bool PhotonBeamIntegrator::Render(const bre_scene &scene) {
     written_ = 0;
     // the reference's default 1 << 31 is INT_MIN, which never divides iter + 1: "at the end only"
     const int32_t wf = params_.writeFrequency;  // the reference's (iter + 1) % writeFrequency, negatives included
-    const bre_status st = bre_render_progressive(ctx_, &scene, &rp, wf, &PhotonBeamIntegrator::OnImage, this);
+    // several devices: the same render split over them (one context each, bre.h)
+    const bre_status st =
+        ctxs_.size() > 1 ? bre_render_progressive_sharded(ctxs_.data(), (int)ctxs_.size(), &scene, &rp, wf,
+                                                          &PhotonBeamIntegrator::OnImage, this)
+                         : bre_render_progressive(ctx_, &scene, &rp, wf, &PhotonBeamIntegrator::OnImage, this);
     if (st != BRE_OK) {
         if (err_.empty()) err_ = bre_last_error(ctx_);
         return false;
@@ -208,12 +229,17 @@ bool PhotonBeamIntegrator::Render(const bre_scene &scene) {
 
 std::unique_ptr<PhotonBeamIntegrator> CreatePhotonBeamIntegrator(const ParamSet &params, const FilmDesc &film,
                                                                  bool quickRender, int device) {
+    return CreatePhotonBeamIntegrator(params, film, quickRender, std::vector<int>{device});
+}
+
+std::unique_ptr<PhotonBeamIntegrator> CreatePhotonBeamIntegrator(const ParamSet &params, const FilmDesc &film,
+                                                                 bool quickRender, const std::vector<int> &devices) {
     PhotonBeamParams::Lookup lk;
     lk.findInt = [&](const char *n, int d) { return params.FindOneInt(n, d); };
     lk.findFloat = [&](const char *n, float d) { return params.FindOneFloat(n, d); };
     lk.findBool = [&](const char *n, bool d) { return params.FindOneBool(n, d); };
     const PhotonBeamParams p = PhotonBeamParams::FromLookup(lk, quickRender, film.xres * film.yres);
-    return std::unique_ptr<PhotonBeamIntegrator>(new PhotonBeamIntegrator(p, film, device));
+    return std::unique_ptr<PhotonBeamIntegrator>(new PhotonBeamIntegrator(p, film, devices));
 }
 
 }  // namespace bre_host

@@ -135,13 +135,18 @@ float BeamRadiusAt(const PhotonBeamParams &p, int iteration);
 void ResolveImage(const std::vector<float> &pixelLd, int iteration, std::vector<float> &rgb);
 
 // Mirror of pbrt::PhotonBeamIntegrator (photonbeam.h:18-60) with Render (photonbeam.cpp:329-586)
-// running on the GPU through bre_render_progressive: per iteration the photon pass, BVH build,
+// running on the GPU through bre_render_progressive (bre_render_progressive_sharded with a device list
+// of more than one entry): per iteration the photon pass, BVH build,
 // camera pass and gather stay in HBM; at the reference's write schedule (:564-584) the image
 // L = Ld / (iter + 1) goes through Film::SetImage + Film::WriteImage (FilmFinalize) and is
 // written to the film's file as PFM.
 class PhotonBeamIntegrator {
   public:
     PhotonBeamIntegrator(const PhotonBeamParams &params, const FilmDesc &film, int device = 0);
+    // One libbre context per entry of `devices` (a repeated ordinal puts several contexts on one device).
+    // With more than one entry Render splits the render over them through bre_render_progressive_sharded:
+    // the reference's ParallelFor2D over camera tiles (photonbeam.cpp:444-557) as a split over GPUs.
+    PhotonBeamIntegrator(const PhotonBeamParams &params, const FilmDesc &film, const std::vector<int> &devices);
     ~PhotonBeamIntegrator();
     PhotonBeamIntegrator(const PhotonBeamIntegrator &) = delete;
     PhotonBeamIntegrator &operator=(const PhotonBeamIntegrator &) = delete;
@@ -162,7 +167,8 @@ class PhotonBeamIntegrator {
     static int OnImage(int32_t iteration, const float *L, void *self);
     PhotonBeamParams params_;
     FilmDesc film_;
-    bre_ctx *ctx_ = nullptr;
+    std::vector<bre_ctx *> ctxs_;  // one per device, all created or none
+    bre_ctx *ctx_ = nullptr;       // ctxs_[0]
     std::vector<float> image_;
     int written_ = 0;
     std::string err_;
@@ -172,6 +178,9 @@ class PhotonBeamIntegrator {
 // the camera's film supplies the pixel count for photonsperiteration's default.
 std::unique_ptr<PhotonBeamIntegrator> CreatePhotonBeamIntegrator(const ParamSet &params, const FilmDesc &film,
                                                                  bool quickRender = false, int device = 0);
+// The same on several GPUs (one context per entry of `devices`).
+std::unique_ptr<PhotonBeamIntegrator> CreatePhotonBeamIntegrator(const ParamSet &params, const FilmDesc &film,
+                                                                 bool quickRender, const std::vector<int> &devices);
 
 // The PFM name the film is written to: the film's filename with a .pfm extension (this build
 // writes PFM only; pbrt picks the writer by extension, imageio.cpp WriteImage).

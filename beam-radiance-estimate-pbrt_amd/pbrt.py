@@ -24,7 +24,7 @@ CLI_PATH = os.path.join(HERE, "host", "bre_pbrt")
 
 EXPORTS = ["bre_pbrt_parse_file", "bre_pbrt_parse_string", "bre_pbrt_free", "bre_pbrt_messages",
            "bre_pbrt_get_scene", "bre_pbrt_get_render_params", "bre_pbrt_get_film", "bre_pbrt_render",
-           "bre_film_finalize", "bre_write_pfm", "bre_read_pfm"]
+           "bre_pbrt_render_devices", "bre_film_finalize", "bre_write_pfm", "bre_read_pfm"]
 
 _HOST = None
 
@@ -49,6 +49,7 @@ def load_host_library(path: str = HOST_LIB_PATH) -> ctypes.CDLL:
     lib.bre_pbrt_get_film.argtypes = [P, ctypes.POINTER(I32), ctypes.POINTER(I32), ctypes.POINTER(F),
                                       ctypes.c_char_p, I32]
     lib.bre_pbrt_render.argtypes = [P, I32, I32, ctypes.c_char_p, I32, P]
+    lib.bre_pbrt_render_devices.argtypes = [P, ctypes.POINTER(I32), I32, I32, ctypes.c_char_p, I32, P]
     lib.bre_film_finalize.argtypes = [I64, P, F, P]
     lib.bre_write_pfm.argtypes = [ctypes.c_char_p, P, I32, I32]
     lib.bre_read_pfm.argtypes = [ctypes.c_char_p, P, I64, ctypes.POINTER(I32), ctypes.POINTER(I32)]
@@ -87,16 +88,25 @@ class PbrtScene:
         assert self._lib.bre_pbrt_get_film(self._h, ctypes.byref(w), ctypes.byref(h), ctypes.byref(sc), buf, 4096) == 0
         self.film = dict(xres=w.value, yres=h.value, scale=sc.value, filename=buf.value.decode())
 
-    def render(self, device: int = 0, outfile: str | None = None, write_files: bool = True) -> np.ndarray:
-        """PhotonBeamIntegrator::Render on GPU `device`; returns the last film image (H, W, 3)."""
+    def render(self, device: int = 0, outfile: str | None = None, write_files: bool = True,
+               devices=None) -> np.ndarray:
+        """PhotonBeamIntegrator::Render on GPU `device`, or split over the GPUs of `devices` (a list of
+        ordinals, one context each; bre_pbrt_render_devices); returns the last film image (H, W, 3)."""
         if not self.ok:
             raise PbrtError(self.messages)
         img = np.zeros((self.film["yres"], self.film["xres"], 3), np.float32)
-        st = self._lib.bre_pbrt_render(self._h, int(device), int(self.quick),
-                                       outfile.encode() if outfile else None, int(write_files),
-                                       img.ctypes.data_as(ctypes.c_void_p))
+        out = outfile.encode() if outfile else None
+        if devices is None:
+            fn = "bre_pbrt_render"
+            st = self._lib.bre_pbrt_render(self._h, int(device), int(self.quick), out, int(write_files),
+                                           img.ctypes.data_as(ctypes.c_void_p))
+        else:
+            fn = "bre_pbrt_render_devices"
+            dev = (ctypes.c_int32 * len(devices))(*[int(d) for d in devices])
+            st = self._lib.bre_pbrt_render_devices(self._h, dev, len(devices), int(self.quick), out, int(write_files),
+                                                   img.ctypes.data_as(ctypes.c_void_p))
         if st != 0:
-            raise PbrtError(f"bre_pbrt_render failed with status {st}")
+            raise PbrtError(f"{fn} failed with status {st}")
         return img
 
     def close(self):

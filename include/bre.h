@@ -261,10 +261,11 @@ bre_status bre_set_gather_events(bre_ctx *ctx, void *start_event, void *end_even
    bre_gather_sharded: bre_gather semantics for host segments.  Context i gathers packet shard i of
    n_ctx of the coherence-sorted segment order (BRE_OPT_SHARD_MODE 1, BRE_OPT_SHARD_BLOCK 1; each
    context's own shard options are restored afterwards), so every device gets the same mix of cheap
-   and costly packets.  The devices' films are summed on the host in context order and added (+=)
-   into accum_rgb; per-segment outputs (each entry is gathered by exactly one context) are merged the
-   same way.  The first failing context's status is returned, its message prefixed with the context
-   index in bre_last_error(ctxs[0]). */
+   and costly packets.  The devices' films stay on their devices and are added in context order on
+   context 0's device (the film collective of bre_render_sharded below); that one film is downloaded and
+   added (+=) into accum_rgb.  Per-segment outputs (each entry is gathered by exactly one context) are
+   merged on the host in the same order.  The first failing context's status is returned, its message
+   prefixed with the context index in bre_last_error(ctxs[0]). */
 bre_status bre_set_beams_sharded(bre_ctx *const *ctxs, int n_ctx, int64_t n, const float *start_xyz,
                                  const float *end_xyz, const float *radius, const float *power_end_rgb);
 bre_status bre_gather_sharded(bre_ctx *const *ctxs, int n_ctx, int64_t nseg, const float *seg_o_xyz,
@@ -331,6 +332,38 @@ bre_status bre_render(bre_ctx *ctx, const bre_scene *scene, const bre_render_par
 typedef int (*bre_image_fn)(int32_t iteration, const float *image_rgb, void *user);
 bre_status bre_render_progressive(bre_ctx *ctx, const bre_scene *scene, const bre_render_params *params,
                                   int32_t write_frequency, bre_image_fn on_image, void *user);
+
+/* ---- the integrator on several GPUs ----
+   bre_render / bre_render_progressive over ctxs[0 .. n_ctx), n_ctx in 1..8, distinct contexts, one per GPU
+   (several on one device are allowed: tests).  The reference's ParallelFor2D over camera tiles
+   (photonbeam.cpp:444-557) becomes a split over devices with the photon map replicated: every context
+   traces every photon and walks the whole camera pass, and gathers packet shard i of n_ctx of the
+   coherence-sorted segments (BRE_OPT_SHARD_MODE 1, BRE_OPT_SHARD_BLOCK 1).  The write schedule,
+   L = Ld / (iter + 1), start_iteration, photons_per_iteration <= 0 and the empty iteration range are those
+   of the single-context calls; on_image runs on the caller's thread.
+   Each context is driven by one host thread for the whole call (context 0 by the caller's) and adds every
+   iteration into a film of its own, on its device; the contexts meet only at a written image.  There
+   context 0 brings the films together on its device (a film of another device is copied there with
+   hipMemcpyPeerAsync, ordered by HIP events), adds them with one kernel and downloads the one finished Ld.
+   When n_ctx divides 8 the contexts render BRE_OPT_FILM_CLASSES 8 films, plane c is taken from context
+   c % n_ctx and Ld is the planes added in class order (bre_resolve_classes' order): the image is the same
+   bits for 1, 2, 4 and 8 contexts.  For any other n_ctx the films have one plane and
+   Ld = ((film_0 + film_1) + film_2) + ... in context order: the same bits from run to run, and the
+   1-context image to float summation order.
+   Each context's shard options and BRE_OPT_FILM_CLASSES are set for the call and restored afterwards; its
+   other options (stream, kernel, counters ...) apply as usual.  What cannot work -- class-plane films on a
+   context whose BRE_OPT_KERNEL is 2 or 5 -- is refused before any launch with the single-context status
+   and the message prefixed "context i:", every context unchanged.  A failure during the call (a HIP error,
+   a device error flag, on_image returning non-zero: BRE_ERR_STATE) stops every context at its next
+   iteration boundary; the first failing context's status is returned, its message prefixed with the
+   context index in bre_last_error(ctxs[0]), and every context stays usable.
+   bre_get_stats(ctxs[i]) afterwards describes context i's own last iteration (its packet shard's
+   segments), not the whole render's. */
+bre_status bre_render_sharded(bre_ctx *const *ctxs, int n_ctx, const bre_scene *scene,
+                              const bre_render_params *params, float *image_rgb);
+bre_status bre_render_progressive_sharded(bre_ctx *const *ctxs, int n_ctx, const bre_scene *scene,
+                                          const bre_render_params *params, int32_t write_frequency,
+                                          bre_image_fn on_image, void *user);
 
 /* ---- integrator helpers (photonbeam.cpp:354-356, 562, 578) ---- */
 /* R_i for iteration i: R_{k+1} = R_k * (k + alpha) / (k + 1), R_0 = initial, in float. */

@@ -9,7 +9,7 @@
  *   RenderOptions::MakeIntegrator "photonbeam"                bre_pbrt_get_render_params
  *     (api.cpp:1463-1471) -> CreatePhotonBeamIntegrator
  *     (photonbeam.cpp:589-611)
- *   pbrtWorldEnd -> integrator->Render(*scene)                bre_pbrt_render
+ *   pbrtWorldEnd -> integrator->Render(*scene)                bre_pbrt_render / bre_pbrt_render_devices
  *     (api.cpp:1361-1380, photonbeam.cpp:329-586)
  *   Film::SetImage + Film::WriteImage (film.cpp:132-210)      bre_film_finalize
  *   WriteImagePFM / ReadImagePFM (imageio.cpp:437-482)        bre_write_pfm / bre_read_pfm
@@ -57,6 +57,11 @@ bre_status bre_pbrt_get_film(const bre_pbrt *p, int32_t *xres, int32_t *yres, fl
    (float[3*xres*yres], may be NULL). */
 bre_status bre_pbrt_render(const bre_pbrt *p, int32_t device, int32_t quick, const char *outfile,
                            int32_t write_files, float *image_rgb);
+/* The same on the n_devices (1..8) GPUs of `devices`, one libbre context each (a repeated ordinal puts
+   several contexts on one device): with more than one the render is split over them by
+   bre_render_progressive_sharded (bre.h), with exactly one it is bre_pbrt_render on that device. */
+bre_status bre_pbrt_render_devices(const bre_pbrt *p, const int32_t *devices, int32_t n_devices, int32_t quick,
+                                   const char *outfile, int32_t write_files, float *image_rgb);
 /* Film::SetImage(L) + Film::WriteImage's per-pixel conversion with the film's scale. */
 bre_status bre_film_finalize(int64_t npix, const float *L_rgb, float scale, float *out_rgb);
 /* PFM file IO (rows top-first in memory, bottom-first on disk, little endian). bre_read_pfm
