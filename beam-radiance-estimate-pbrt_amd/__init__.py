@@ -44,7 +44,7 @@ EXPORTS = [
     "bre_render_iteration", "bre_render",
     "bre_render_progressive", "bre_shard_segments", "bre_set_beams_sharded", "bre_gather_sharded",
     "bre_device_check", "bre_resolve_classes", "bre_film_add", "bre_set_gather_after", "bre_set_gather_events",
-    "bre_render_sharded", "bre_render_progressive_sharded",
+    "bre_render_sharded", "bre_render_progressive_sharded", "bre_set_lights",
 ]
 # bre_image_fn: int on_image(int32 iteration, const float *image_rgb, void *user)
 IMAGE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_int32, ctypes.POINTER(ctypes.c_float), ctypes.c_void_p)
@@ -126,6 +126,9 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.bre_resolve_image.restype = I32
     lib.bre_trace_photons.argtypes = [P, P, I64, I32, I32, F, ctypes.POINTER(I64)]
     lib.bre_trace_photons.restype = I32
+    if hasattr(lib, "bre_set_lights"):  # (absent from earlier libraries loaded for A/B timing)
+        lib.bre_set_lights.argtypes = [P, P, I32]
+        lib.bre_set_lights.restype = I32
     lib.bre_get_beams.argtypes = [P, I64, P, P, P, P, ctypes.POINTER(I64)]
     lib.bre_get_beams.restype = I32
     lib.bre_scene_cornell.argtypes = [P, F, F, F]
@@ -323,6 +326,17 @@ class BeamGather:
             assert t.is_cuda and t.is_contiguous() and str(t.dtype) == "torch.float32"
         self._keep = [start, end, radius, power]
         self._check(self.lib.bre_set_beams_device(self.h, n, _ptr(start), _ptr(end), _ptr(radius), _ptr(power)))
+
+    # ---- lights ----
+    def set_lights(self, lights=()):
+        """bre_set_lights: the point and spot lights (scene.Light: scene.point_light, scene.spot_light,
+        a parsed scene's .lights) every later pass and render of this context adds to its scene; an
+        empty list clears them."""
+        from .scene import Light
+
+        lights = list(lights)
+        arr = (Light * max(len(lights), 1))(*lights)
+        self._check(self.lib.bre_set_lights(self.h, arr if lights else None, len(lights)))
 
     # ---- photon pass ----
     def trace_photons(self, scene, n_photons: int, iteration: int = 0, max_depth: int = 5,

@@ -2,6 +2,7 @@
 // scene upload with its geometry cache, bre_trace_photons, bre_camera_pass, bre_get_segments and the
 // bre_render* loops over them.
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <vector>
 
@@ -29,7 +30,8 @@ bre_status check_medium(bre_ctx *c, const bre_scene *scene, const char *fn) {
     return BRE_OK;
 }
 
-// Triangle count in range and at least one area light (the passes need scene.lights non-empty)
+// Triangle count in range and at least one light: an emitting triangle, or a delta light of the context
+// (the passes need scene.lights non-empty); every delta light's order within the triangle count
 bre_status check_scene(bre_ctx *c, const bre_scene *scene, const char *fn) {
     if (!scene) return fail(c, BRE_ERR_INVALID_ARG, "%s: null scene", fn);
     const int cap = scene->triangles_ext ? BRE_MAX_SCENE_TRIANGLES : BRE_MAX_TRIANGLES;
@@ -39,16 +41,16 @@ bre_status check_scene(bre_ctx *c, const bre_scene *scene, const char *fn) {
     const bre_triangle *tri = scene_triangles(scene);
     int64_t lights = 0;
     for (int i = 0; i < scene->n_triangles; ++i) lights += tri[i].emit != 0;
-    if (lights == 0) return fail(c, BRE_ERR_INVALID_ARG, "%s: the scene has no area light", fn);
+    if (lights == 0 && c->lights.empty()) return fail(c, BRE_ERR_INVALID_ARG, "%s: the scene has no area light", fn);
+    for (size_t k = 0; k < c->lights.size(); ++k)
+        if (c->lights[k].order > scene->n_triangles)
+            return fail(c, BRE_ERR_INVALID_ARG, "%s: light %d has order %d, the scene has %d triangles", fn, (int)k,
+                        c->lights[k].order, scene->n_triangles);
     return BRE_OK;
 }
 
-// 64-bit hash of the scene's triangles (the geometry cache key of upload_scene)
-uint64_t hash_triangles(const bre_scene *s) {
-    const bre_triangle *tri = scene_triangles(s);
-    const size_t bytes = (size_t)s->n_triangles * sizeof(bre_triangle);
-    const unsigned char *p = reinterpret_cast<const unsigned char *>(tri);
-    uint64_t h = 0x9e3779b97f4a7c15ull ^ (uint64_t)s->n_triangles;
+uint64_t hash_bytes(uint64_t h, const void *data, size_t bytes) {
+    const unsigned char *p = static_cast<const unsigned char *>(data);
     size_t i = 0;
     for (; i + 8 <= bytes; i += 8) {
         uint64_t w;
@@ -57,6 +59,15 @@ uint64_t hash_triangles(const bre_scene *s) {
         h ^= h >> 29;
     }
     for (; i < bytes; ++i) h = (h ^ p[i]) * 0x100000001b3ull;
+    return h;
+}
+
+// 64-bit hash of the scene's triangles and the context's lights (the geometry cache key of
+// upload_scene); without lights it is the hash of the triangles alone
+uint64_t hash_geometry(const bre_scene *s, const std::vector<bre_light> &lights) {
+    uint64_t h = hash_bytes(0x9e3779b97f4a7c15ull ^ (uint64_t)s->n_triangles, scene_triangles(s),
+                            (size_t)s->n_triangles * sizeof(bre_triangle));
+    if (!lights.empty()) h = hash_bytes(h ^ (uint64_t)lights.size(), lights.data(), lights.size() * sizeof(bre_light));
     return h | 1ull;  // never 0 (= no scene)
 }
 
@@ -78,15 +89,17 @@ bre_status upload_scene(bre_ctx *c, const bre_scene *scene) {
         }
         dd = c->grid_dens.as<float>();
     }
-    const uint64_t h = hash_triangles(scene);
+    const uint64_t h = hash_geometry(scene, c->lights);
     // the geometry is reused only when the hash AND the bytes match (a hash collision between two
-    // scenes must not trace against the stale BVH and lights)
+    // scenes must not trace against the stale BVH and lights); the lights' bytes follow the triangles'
     const size_t tri_bytes = (size_t)scene->n_triangles * sizeof(bre_triangle);
-    const bool same = h == c->sc_hash && c->sc_bytes.size() == tri_bytes &&
-                      (tri_bytes == 0 || memcmp(c->sc_bytes.data(), scene_triangles(scene), tri_bytes) == 0);
+    const size_t light_bytes = c->lights.size() * sizeof(bre_light);
+    const bool same = h == c->sc_hash && c->sc_bytes.size() == tri_bytes + light_bytes &&
+                      (tri_bytes == 0 || memcmp(c->sc_bytes.data(), scene_triangles(scene), tri_bytes) == 0) &&
+                      (light_bytes == 0 || memcmp(c->sc_bytes.data() + tri_bytes, c->lights.data(), light_bytes) == 0);
     if (!same) {
         HostScene hs;
-        prepare_geometry(scene, &hs);
+        prepare_geometry(scene, &hs, c->lights.data(), (int)c->lights.size());
         if (hs.depth > kSceneStack)
             return fail(c, BRE_ERR_INVALID_ARG, "scene BVH depth %d exceeds the %d-entry traversal stack (as in "
                         "BVHAccel::Intersect)", hs.depth, kSceneStack);
@@ -101,6 +114,7 @@ bre_status upload_scene(bre_ctx *c, const bre_scene *scene) {
         HIPCHK(c, up(c->sc_light_tri, hs.light_tri.data(), hs.light_tri.size() * sizeof(int32_t)));
         HIPCHK(c, up(c->sc_light_func, hs.light_func.data(), hs.light_func.size() * sizeof(float)));
         HIPCHK(c, up(c->sc_light_cdf, hs.light_cdf.data(), hs.light_cdf.size() * sizeof(float)));
+        HIPCHK(c, up(c->sc_dlights, hs.dlights.data(), hs.dlights.size() * sizeof(DLight)));
         HIPCHK(c, hipStreamSynchronize(c->stream));  // the host vectors go out of scope
         c->sc_head = hs.head;
         c->sc_head.t = c->sc_tris.as<PTri>();
@@ -109,9 +123,12 @@ bre_status upload_scene(bre_ctx *c, const bre_scene *scene) {
         c->sc_head.light_tri = c->sc_light_tri.as<int32_t>();
         c->sc_head.light_func = c->sc_light_func.as<float>();
         c->sc_head.light_cdf = c->sc_light_cdf.as<float>();
+        c->sc_head.dlights = c->sc_dlights.as<DLight>();
         c->sc_hash = h;
         const unsigned char *tb = reinterpret_cast<const unsigned char *>(scene_triangles(scene));
         c->sc_bytes.assign(tb, tb + tri_bytes);
+        const unsigned char *lb = reinterpret_cast<const unsigned char *>(c->lights.data());
+        c->sc_bytes.insert(c->sc_bytes.end(), lb, lb + light_bytes);
     }
     DevScene ds;
     memcpy(&ds, &c->sc_head, sizeof(DevScene));  // padding bytes included: the record compares bytewise
@@ -162,6 +179,26 @@ bool image_due(int32_t it, int32_t end_iteration, int32_t write_frequency) {
 }  // namespace bre
 
 extern "C" {
+
+bre_status bre_set_lights(bre_ctx *c, const bre_light *lights, int32_t n) {
+    if (!c) return BRE_ERR_INVALID_ARG;
+    if (n < 0 || n > BRE_MAX_LIGHTS)
+        return fail(c, BRE_ERR_INVALID_ARG, "bre_set_lights: light count must be in 0..%d", BRE_MAX_LIGHTS);
+    if (n > 0 && !lights) return fail(c, BRE_ERR_INVALID_ARG, "bre_set_lights: null lights");
+    for (int k = 0; k < n; ++k) {
+        const bre_light &l = lights[k];
+        if (l.type != BRE_LIGHT_POINT && l.type != BRE_LIGHT_SPOT)
+            return fail(c, BRE_ERR_INVALID_ARG, "bre_set_lights: light %d has unknown type %d", k, l.type);
+        if (l.order < 0) return fail(c, BRE_ERR_INVALID_ARG, "bre_set_lights: light %d has a negative order", k);
+        bool finite = std::isfinite(l.cone_total_deg) && std::isfinite(l.cone_falloff_start_deg);
+        for (int j = 0; j < 3; ++j) finite = finite && std::isfinite(l.I[j]);
+        for (int j = 0; j < 16; ++j)
+            finite = finite && std::isfinite(l.light_to_world[j]) && std::isfinite(l.world_to_light[j]);
+        if (!finite) return fail(c, BRE_ERR_INVALID_ARG, "bre_set_lights: light %d has a non-finite field", k);
+    }
+    c->lights.assign(lights, lights + n);
+    return BRE_OK;
+}
 
 bre_status bre_trace_photons(bre_ctx *c, const bre_scene *scene, int64_t n_photons, int32_t iteration,
                              int32_t max_depth, float beam_radius, int64_t *n_beams) {

@@ -200,6 +200,12 @@ bre_status check_render_sharded(bre_ctx *const *ctxs, int n_ctx, const bre_scene
     BRE_TRY(check_ctxs(ctxs, n_ctx));
     if (!scene) return fail(ctxs[0], BRE_ERR_INVALID_ARG, "%s: null scene", fn);
     BRE_TRY(check_params(ctxs[0], rp));
+    // the contexts' films are summed: every context must light the scene alike (bre_set_lights)
+    for (int i = 1; i < n_ctx; ++i) {
+        const std::vector<bre_light> &a = ctxs[0]->lights, &b = ctxs[i]->lights;
+        if (a.size() != b.size() || (!a.empty() && memcmp(a.data(), b.data(), a.size() * sizeof(bre_light)) != 0))
+            return fail(ctxs[0], BRE_ERR_INVALID_ARG, "context %d: %s: its lights (bre_set_lights) differ from context 0's", i, fn);
+    }
     if (!class_films(n_ctx) || !rp->render_media) return BRE_OK;
     for (int i = 0; i < n_ctx; ++i) {
         const bre_ctx *c = ctxs[i];

@@ -306,33 +306,52 @@ __device__ __forceinline__ float power_heuristic(float fpdf, float gpdf) {
     return (f * f) / (f * f + g * g);
 }
 
-// EstimateDirect (integrator.cpp:108-214) for the area light on triangle `li`, handleMedia = true
+// EstimateDirect (integrator.cpp:108-214), handleMedia = true, for light `li` of the merged table: the
+// area light on triangle li (>= 0), or the delta light ~li (PointLight / SpotLight).  A delta light's
+// Sample_Li (point.cpp:44-53, spot.cpp:53-62) gives wi = Normalize(pLight - p), pdf 1 and
+// Li = I * Falloff(-wi) / DistanceSquared(pLight, p); its shadow ray is SpawnRayTo an Interaction with
+// zero normal and zero error (interaction.h:73-78), so OffsetRayOrigin leaves pLight + 0; it has no MIS
+// weight and no BSDF-sampling half (IsDeltaLight, integrator.cpp:155, 167).
 __device__ void estimate_direct(const DevScene &S, HaltonDev &hs, f3 p, f3 perr, const PTri &q, f3 wo, int li,
                                 float usx, float usy, float ulx, float uly, float Ld[3]) {
-    const PTri &L = S.t[li];
+    const bool delta = li < 0;
+    const PTri &L = S.t[delta ? 0 : li];
     Ld[0] = Ld[1] = Ld[2] = 0.f;
     float scat_pdf = 0.f;
-    // DiffuseAreaLight::Sample_Li (diffuse.cpp:68-81) -> Shape::Sample(ref, u) (shape.cpp:56-70)
-    const ShapeSample ps = sample_tri(L, ulx, uly);
-    const f3 sp = ps.p;
-    float light_pdf = ps.pdf;
-    f3 w = sub3(sp, p);
-    if (lensq3(w) == 0) {
-        light_pdf = 0;
-    } else {
-        w = normalize3(w);
-        light_pdf *= lensq3(sub3(p, sp)) / fabsf(dot3(ps.n, neg3(w)));
-        if (isinf(light_pdf)) light_pdf = 0.f;
-    }
     f3 wi = mk(0, 0, 0);
     float Li[3] = {0.f, 0.f, 0.f};
-    if (light_pdf == 0 || lensq3(sub3(sp, p)) == 0) {
-        light_pdf = 0;
+    ShapeSample ps;
+    float light_pdf;
+    if (delta) {
+        const DLight &D = S.dlights[~li];
+        ps.p = D.p;
+        ps.perr = ps.n = mk(0, 0, 0);
+        light_pdf = 1.f;
+        wi = normalize3(sub3(D.p, p));
+        const float fo = light_falloff(D, neg3(wi));
+        const float dist2 = lensq3(sub3(D.p, p));
+        for (int c = 0; c < 3; ++c) Li[c] = (D.I[c] * fo) / dist2;
     } else {
-        wi = normalize3(sub3(sp, p));
-        if (dot3(ps.n, neg3(wi)) > 0)
-            for (int c = 0; c < 3; ++c) Li[c] = L.Le[c];
+        // DiffuseAreaLight::Sample_Li (diffuse.cpp:68-81) -> Shape::Sample(ref, u) (shape.cpp:56-70)
+        ps = sample_tri(L, ulx, uly);
+        light_pdf = ps.pdf;
+        f3 w = sub3(ps.p, p);
+        if (lensq3(w) == 0) {
+            light_pdf = 0;
+        } else {
+            w = normalize3(w);
+            light_pdf *= lensq3(sub3(p, ps.p)) / fabsf(dot3(ps.n, neg3(w)));
+            if (isinf(light_pdf)) light_pdf = 0.f;
+        }
+        if (light_pdf == 0 || lensq3(sub3(ps.p, p)) == 0) {
+            light_pdf = 0;
+        } else {
+            wi = normalize3(sub3(ps.p, p));
+            if (dot3(ps.n, neg3(wi)) > 0)
+                for (int c = 0; c < 3; ++c) Li[c] = L.Le[c];
+        }
     }
+    const f3 sp = ps.p;
     if (light_pdf > 0 && !black3(Li)) {
         float f[3];
         bsdf_f(q, wo, wi, f);
@@ -354,11 +373,12 @@ __device__ void estimate_direct(const DevScene &S, HaltonDev &hs, f3 p, f3 perr,
                 for (int c = 0; c < 3; ++c) Li[c] = Li[c] * (1.f * tr[c]);
             }
             if (!black3(Li)) {
-                const float wgt = power_heuristic(light_pdf, scat_pdf);
+                const float wgt = delta ? 1.f : power_heuristic(light_pdf, scat_pdf);
                 for (int c = 0; c < 3; ++c) Ld[c] = Ld[c] + f[c] * Li[c] * wgt / light_pdf;
             }
         }
     }
+    if (delta) return;
     // BSDF sampling
     {
         float f[3];
@@ -447,7 +467,7 @@ __global__ __launch_bounds__(kCamBlock, 6) void k_camera(const DevScene *__restr
     for (int depth = 0; depth < max_depth; ++depth) {
         float tmax = __builtin_huge_valf();
         Hit hit;
-        if (!intersect_scene(S, o, d, tmax, hit)) break;  // area lights: Le(ray) = 0
+        if (!intersect_scene(S, o, d, tmax, hit)) break;  // area and delta lights: Le(ray) = 0
         float mb[3] = {1.f, 1.f, 1.f};
         if (S.medium) medium_tr_any(S, hs, o, d, tmax, mb);
         if (render_media) {
@@ -479,7 +499,8 @@ __global__ __launch_bounds__(kCamBlock, 6) void k_camera(const DevScene *__restr
         hs.get2d(ulx, uly);
         hs.get2d(usx, usy);
         float ed[3];
-        estimate_direct(S, hs, hit.p, hit.perr, q, normalize3(wo), S.light_tri[ln], usx, usy, ulx, uly, ed);
+        const int lt = S.light_tri[ln];
+        estimate_direct(S, hs, hit.p, hit.perr, q, normalize3(wo), lt, usx, usy, ulx, uly, ed);
         for (int c = 0; c < 3; ++c) Ld[c] = Ld[c] + beta[c] * (ed[c] / light_pdf);
         if (depth < max_depth - 1) {
             float ux, uy, pdf = 0.f, f[3];

@@ -200,9 +200,11 @@ struct bre_ctx {
     bre::DevMem ph_scene, ph_counts, ph_offsets, ph_tmp, grid_dens;
     bre::BeamArrays ph_s;  // single-trace photon pass: per-photon beam slots
     // scene geometry on the device (upload_scene): triangles, BVHAccel nodes + primitive order, lights
-    bre::DevMem sc_tris, sc_nodes, sc_prims, sc_light_tri, sc_light_func, sc_light_cdf;
-    uint64_t sc_hash = 0;                   // hash of the uploaded triangles (0: none)
-    std::vector<unsigned char> sc_bytes;    // the uploaded triangles' bytes: a hash match is confirmed by memcmp
+    bre::DevMem sc_tris, sc_nodes, sc_prims, sc_light_tri, sc_light_func, sc_light_cdf, sc_dlights;
+    std::vector<bre_light> lights;          // bre_set_lights: the delta lights every pass adds to its scene
+    uint64_t sc_hash = 0;                   // hash of the uploaded triangles and lights (0: none)
+    std::vector<unsigned char> sc_bytes;    // the uploaded triangles' bytes, then the lights': a hash match is
+                                            // confirmed by memcmp
     bre::DevScene sc_head;                  // geometry fields of the uploaded scene
     bre::DevScene ph_scene_host;            // the record last copied to ph_scene
     std::vector<unsigned char> grid_bytes;  // the density grid last copied to grid_dens

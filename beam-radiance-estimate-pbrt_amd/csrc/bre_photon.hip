@@ -52,13 +52,63 @@ void prepare_medium(const bre_scene *s, DevScene *dp, const float *d_density) {
     d.g = s->g;
 }
 
-void prepare_geometry(const bre_scene *s, HostScene *out) {
+// PointLight / SpotLight constructors (point.h, spot.cpp:44-51) and Light's (light.cpp:46-55)
+DLight prepare_light(const bre_light &l) {
+    DLight D{};
+    const float *m = l.light_to_world;
+    // pLight = LightToWorld(Point3f(0, 0, 0)), Transform::operator()(Point3f) (transform.h:223-233)
+    const float x = 0.f, y = 0.f, z = 0.f;
+    const float xp = m[0] * x + m[1] * y + m[2] * z + m[3];
+    const float yp = m[4] * x + m[5] * y + m[6] * z + m[7];
+    const float zp = m[8] * x + m[9] * y + m[10] * z + m[11];
+    const float wp = m[12] * x + m[13] * y + m[14] * z + m[15];
+    D.p = wp == 1 ? mk(xp, yp, zp) : div3(mk(xp, yp, zp), wp);
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) {
+            D.l2w[3 * r + c] = l.light_to_world[4 * r + c];
+            D.w2l[3 * r + c] = l.world_to_light[4 * r + c];
+        }
+    for (int k = 0; k < 3; ++k) D.I[k] = l.I[k];
+    D.spot = l.type == BRE_LIGHT_SPOT;
+    if (D.spot) {  // std::cos(Radians(.)), pbrt.h:295
+        D.cos_total = bre_cosf((kPi / 180) * l.cone_total_deg);
+        D.cos_start = bre_cosf((kPi / 180) * l.cone_falloff_start_deg);
+    }
+    return D;
+}
+
+// Power().y(): 4 * Pi * I (point.cpp:55); I * 2 * Pi * (1 - .5f * (cosFalloffStart + cosTotalWidth))
+// (spot.cpp:75-77)
+static float light_power_y(const DLight &D) {
+    float pw[3];
+    for (int k = 0; k < 3; ++k)
+        pw[k] = D.spot ? D.I[k] * 2 * kPi * (1 - .5f * (D.cos_start + D.cos_total)) : D.I[k] * (4 * kPi);
+    return lum3(pw);
+}
+
+void prepare_geometry(const bre_scene *s, HostScene *out, const bre_light *lights, int n_lights) {
     DevScene &d = out->head;
     d.n_tris = s->n_triangles;
     const bre_triangle *tri = scene_triangles(s);
     out->tris.resize((size_t)s->n_triangles);
     out->light_tri.clear();
     out->light_func.clear();
+    // scene.lights in declaration order: a delta light comes before the area lights of the triangles
+    // with index >= its order; equal orders keep their array order (a stable sort by order)
+    out->dlights.resize((size_t)n_lights);
+    std::vector<int> by_order((size_t)n_lights);
+    for (int k = 0; k < n_lights; ++k) {
+        out->dlights[(size_t)k] = prepare_light(lights[k]);
+        by_order[(size_t)k] = k;
+    }
+    std::stable_sort(by_order.begin(), by_order.end(), [&](int a, int b) { return lights[a].order < lights[b].order; });
+    size_t next = 0;
+    const auto delta_up_to = [&](int i) {
+        for (; next < by_order.size() && lights[by_order[next]].order <= i; ++next) {
+            out->light_tri.push_back(~by_order[next]);
+            out->light_func.push_back(light_power_y(out->dlights[(size_t)by_order[next]]));
+        }
+    };
     for (int i = 0; i < s->n_triangles; ++i) {
         const bre_triangle &t = tri[i];
         PTri &T = out->tris[(size_t)i];
@@ -85,6 +135,7 @@ void prepare_geometry(const bre_scene *s, HostScene *out) {
         T.absorb = (t.kd[0] == 0 && t.kd[1] == 0 && t.kd[2] == 0) ? 1 : 0;
         T.emit = t.emit != 0;
         if (T.emit) {
+            delta_up_to(i);
             out->light_tri.push_back(i);
             // DiffuseAreaLight::Power() = (twoSided ? 2 : 1) * Lemit * area * Pi (diffuse.cpp:64-66), .y()
             float pw[3];
@@ -92,6 +143,7 @@ void prepare_geometry(const bre_scene *s, HostScene *out) {
             out->light_func.push_back(lum3(pw));
         }
     }
+    delta_up_to(s->n_triangles);
     const int nl = (int)out->light_tri.size();
     d.n_lights = nl;
     // Distribution1D(func, n) (sampling.h:57-69)
@@ -110,9 +162,9 @@ void prepare_geometry(const bre_scene *s, HostScene *out) {
     d.stack_depth = out->depth;
 }
 
-void prepare_scene(const bre_scene *s, HostScene *out, const float *d_density) {
+void prepare_scene(const bre_scene *s, HostScene *out, const float *d_density, const bre_light *lights, int n_lights) {
     out->head = DevScene{};
-    prepare_geometry(s, out);
+    prepare_geometry(s, out, lights, n_lights);
     prepare_medium(s, &out->head, d_density);
 }
 
@@ -151,30 +203,52 @@ __global__ __launch_bounds__(kPhotonBlock, 6) void k_photons(const DevScene *__r
     const int64_t w = MODE == 1 ? offsets[i] : (MODE == 2 ? i * (int64_t)over : 0);
     int cnt = 0;
 
-    // ---- emission, photonbeam.cpp:393-418: a light by power, DiffuseAreaLight::Sample_Le ----
+    // ---- emission, photonbeam.cpp:393-418: a light by power, then its Sample_Le (DiffuseAreaLight on a
+    // triangle, PointLight or SpotLight); the five draws are the same whatever the light ----
     float light_pdf;
     const int ln = sample_light(S, pcg_float(rng), light_pdf);  // lightSample
     float u0x, u0y, u1x, u1y;
     pcg_2d(rng, u0x, u0y);
     pcg_2d(rng, u1x, u1y);
     (void)pcg_float(rng);  // uLightTime
-    const PTri &L = S.t[S.light_tri[ln]];
-    const ShapeSample ps = sample_tri(L, u0x, u0y);
-    const float pdf_pos = ps.pdf;
-    const f3 wl = cosine_hemisphere(u1x, u1y);
-    const float pdf_dir = wl.z * kInvPi;
-    f3 v1, v2;
-    coord_system(ps.n, v1, v2);
-    f3 d = add3(add3(scale3(v1, wl.x), scale3(v2, wl.y)), scale3(ps.n, wl.z));
-    f3 o = offset_origin(ps.p, ps.perr, ps.n, d);
-    const bool front = dot3(ps.n, d) > 0;  // DiffuseAreaLight::L, one-sided
+    const int lt = S.light_tri[ln];
+    f3 o, d;
     float beta[3];
-    bool alive = !(pdf_pos == 0 || pdf_dir == 0 || !front || black3(L.Le));
-    if (alive) {
-        const float ad = fabsf(dot3(ps.n, d));
-        const float den = light_pdf * pdf_pos * pdf_dir;
-        for (int c = 0; c < 3; ++c) beta[c] = (ad * L.Le[c]) / den;
-        alive = !black3(beta);
+    bool alive;
+    if (lt >= 0) {
+        const PTri &L = S.t[lt];
+        const ShapeSample ps = sample_tri(L, u0x, u0y);
+        const float pdf_pos = ps.pdf;
+        const f3 wl = cosine_hemisphere(u1x, u1y);
+        const float pdf_dir = wl.z * kInvPi;
+        f3 v1, v2;
+        coord_system(ps.n, v1, v2);
+        d = add3(add3(scale3(v1, wl.x), scale3(v2, wl.y)), scale3(ps.n, wl.z));
+        o = offset_origin(ps.p, ps.perr, ps.n, d);
+        const bool front = dot3(ps.n, d) > 0;  // DiffuseAreaLight::L, one-sided
+        alive = !(pdf_pos == 0 || pdf_dir == 0 || !front || black3(L.Le));
+        if (alive) {
+            const float ad = fabsf(dot3(ps.n, d));
+            const float den = light_pdf * pdf_pos * pdf_dir;
+            for (int c = 0; c < 3; ++c) beta[c] = (ad * L.Le[c]) / den;
+            alive = !black3(beta);
+        }
+    } else {
+        // PointLight / SpotLight::Sample_Le: the ray leaves pLight itself, nLight = d, pdfPos = 1; a
+        // direction the two matrices push outside the cone has Falloff 0 and the photon ends (:412)
+        const DLight &D = S.dlights[~lt];
+        float pdf_dir, fo;
+        light_sample_le(D, u0x, u0y, d, pdf_dir, fo);
+        o = D.p;
+        float Le[3];
+        for (int c = 0; c < 3; ++c) Le[c] = D.I[c] * fo;
+        alive = !(pdf_dir == 0 || black3(Le));
+        if (alive) {
+            const float ad = fabsf(dot3(d, d));
+            const float den = light_pdf * 1.f * pdf_dir;
+            for (int c = 0; c < 3; ++c) beta[c] = (ad * Le[c]) / den;
+            alive = !black3(beta);
+        }
     }
 
     // ---- TracePhotonBeamRecursive as a state machine ----

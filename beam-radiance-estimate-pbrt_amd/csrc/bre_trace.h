@@ -165,18 +165,32 @@ struct SceneNode {
 static_assert(sizeof(SceneNode) == 32, "SceneNode is BVHAccel's 32-B LinearBVHNode");
 constexpr int kSceneStack = 64;  // BVHAccel::Intersect's nodesToVisit[64]: the deepest tree accepted
 
+// A delta light (bre_light: PointLight, src/lights/point.cpp; SpotLight, src/lights/spot.cpp) as its
+// constructor leaves it: pLight = LightToWorld(Point3f(0, 0, 0)), the 3x3 blocks of LightToWorld and
+// WorldToLight (vectors only ever go through them), I, and the two cosines (host, bre_fmath.h).
+static_assert(sizeof(bre_light) == 156, "bre_light has no padding: the geometry cache compares its bytes");
+struct DLight {
+    f3 p;
+    float l2w[9], w2l[9];  // row-major
+    float I[3];
+    float cos_total, cos_start;  // cosTotalWidth, cosFalloffStart
+    int spot;                    // 1: SpotLight, 0: PointLight
+};
+
 struct DevScene {
     int n_tris, n_lights, medium, n_nodes;  // medium: BRE_MEDIUM_NONE / _HOMOGENEOUS / _GRID
     int stack_depth;                        // traversal stack entries per thread (the tree depth)
     float sigma_t[3];
     float g;
     // the triangles in scene order, the BVHAccel over them (nodes + primitive order) and
-    // scene.lights (the emitting triangles, in order) with the Distribution1D of their Power().y()
+    // scene.lights (the emitting triangles and the context's delta lights, merged by bre_light.order)
+    // with the Distribution1D of their Power().y()
     // (ComputeLightPowerDistribution, integrator.cpp:217-225; sampling.h:55-69): device arrays
     const PTri *t;
     const SceneNode *nodes;
     const int32_t *prims;       // BVH primitive slot -> triangle index
-    const int32_t *light_tri;
+    const int32_t *light_tri;   // per light: >= 0 the emitting triangle, < 0 the delta light ~value of dlights
+    const DLight *dlights;
     const float *light_func;
     const float *light_cdf;     // n_lights + 1
     float light_func_int;
@@ -195,16 +209,21 @@ struct HostScene {
     std::vector<SceneNode> nodes;
     std::vector<int32_t> prims;
     std::vector<int32_t> light_tri;
+    std::vector<DLight> dlights;
     std::vector<float> light_func, light_cdf;
     int depth = 0;  // deepest node of the BVH (root = 1)
 };
 
 // host: derive the per-triangle constants, the light distribution and the scene BVH exactly as
 // oracle/ora_pbrt.h make_scene does; `d_density` is the device copy of s->grid_density (grid media)
-void prepare_scene(const bre_scene *s, HostScene *out, const float *d_density = nullptr);
+void prepare_scene(const bre_scene *s, HostScene *out, const float *d_density = nullptr,
+                   const bre_light *lights = nullptr, int n_lights = 0);
 // the two halves of prepare_scene: the triangles, lights and BVH (out->head's geometry fields and
 // the arrays), and the medium fields of a DevScene
-void prepare_geometry(const bre_scene *s, HostScene *out);
+// (`lights`: the context's delta lights, each with order <= s->n_triangles)
+void prepare_geometry(const bre_scene *s, HostScene *out, const bre_light *lights = nullptr, int n_lights = 0);
+// a bre_light as the PointLight / SpotLight constructor leaves it
+DLight prepare_light(const bre_light &l);
 void prepare_medium(const bre_scene *s, DevScene *d, const float *d_density);
 // host: the scene's BVHAccel (bvh.cpp: SAH, 12 buckets, maxPrimsInNode 4, depth-first layout) over
 // the triangles' world bounds; returns the tree depth
@@ -372,6 +391,44 @@ BRE_TD int sample_light(const DevScene &S, float u, float &pdf) {
     const int off = find_interval(S.n_lights + 1, [&](int i) { return cdf[i] <= u; });
     pdf = (S.light_func_int > 0) ? S.light_func[off] / (S.light_func_int * (float)S.n_lights) : 0.f;
     return off;
+}
+
+// ---- delta lights (src/lights/point.cpp, src/lights/spot.cpp) ----
+// Transform::operator()(Vector3f) through a 3x3 block, transform.h:236-242
+BRE_TD f3 xform_vec3(const float *m, f3 v) {
+    return mk(m[0] * v.x + m[1] * v.y + m[2] * v.z, m[3] * v.x + m[4] * v.y + m[5] * v.z,
+              m[6] * v.x + m[7] * v.y + m[8] * v.z);
+}
+// SpotLight::Falloff, spot.cpp:64-73 (a PointLight has none: 1)
+BRE_TD float light_falloff(const DLight &D, f3 w) {
+    if (!D.spot) return 1.f;
+    const float cos_t = normalize3(xform_vec3(D.w2l, w)).z;
+    if (cos_t < D.cos_total) return 0.f;
+    if (cos_t > D.cos_start) return 1.f;
+    const float delta = (cos_t - D.cos_total) / (D.cos_start - D.cos_total);
+    return (delta * delta) * (delta * delta);
+}
+// Sample_Le of a delta light from uLight0 (point.cpp:61-71: UniformSampleSphere, sampling.cpp:98-103;
+// spot.cpp:83-93: UniformSampleCone and UniformConePdf, sampling.cpp:132-142).  The ray starts at
+// D.p; d is not normalised (a spot's goes through LightToWorld); nLight = d, pdfPos = 1.
+BRE_TD void light_sample_le(const DLight &D, float u0, float u1, f3 &d, float &pdf_dir, float &fo) {
+    float s, c;
+    if (D.spot) {
+        const float cos_t = (1.f - u0) + u0 * D.cos_total;
+        const float sin_t = sqrtf(1.f - cos_t * cos_t);
+        const float phi = u1 * 2 * kPi;
+        bre_sincosf(phi, &s, &c);
+        d = xform_vec3(D.l2w, mk(c * sin_t, s * sin_t, cos_t));
+        pdf_dir = 1 / (2 * kPi * (1 - D.cos_total));
+    } else {
+        const float z = 1 - 2 * u0;
+        const float r = sqrtf(smax(0.f, 1.f - z * z));
+        const float phi = 2 * kPi * u1;
+        bre_sincosf(phi, &s, &c);
+        d = mk(r * c, r * s, z);
+        pdf_dir = kInv4Pi;
+    }
+    fo = light_falloff(D, d);
 }
 
 // Sampler draws: the photon pass draws from PCG32 (AwesomeHaltonSampler past its 1000 Halton

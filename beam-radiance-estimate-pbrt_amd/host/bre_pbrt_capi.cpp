@@ -49,6 +49,31 @@ bre_status bre_pbrt_get_scene(const bre_pbrt *p, bre_scene *out) {
     return BRE_OK;
 }
 
+bre_status bre_pbrt_get_lights(const bre_pbrt *p, int32_t capacity, bre_light *out, int32_t *n) {
+    if (!p || !p->ok || capacity < 0) return BRE_ERR_INVALID_ARG;
+    const int32_t have = (int32_t)p->scene.lights.size();
+    if (n) *n = have;
+    const int32_t k = capacity < have ? capacity : have;
+    if (k > 0 && !out) return BRE_ERR_INVALID_ARG;
+    for (int32_t i = 0; i < k; ++i) out[i] = p->scene.lights[(size_t)i];
+    return BRE_OK;
+}
+
+bre_status bre_pbrt_make_spot_light(const float from[3], const float to[3], const float I[3], float coneangle,
+                                    float conedeltaangle, const float *ctm, const float *ctm_inv, int32_t order,
+                                    bre_light *out) {
+    if (!from || !to || !I || !out) return BRE_ERR_INVALID_ARG;
+    Xform l2w = Xform::Identity();
+    if (ctm) {
+        float m[4][4];
+        memcpy(m, ctm, sizeof(m));
+        l2w = Xform::FromMatrix(m);
+        if (ctm_inv) memcpy(l2w.mInv, ctm_inv, sizeof(l2w.mInv));  // the inverse the caller tracked
+    }
+    MakeSpotLight(l2w, from, to, I, coneangle, conedeltaangle, order, out);
+    return BRE_OK;
+}
+
 static PhotonBeamParams params_of(const bre_pbrt *p, int32_t quick) {
     PhotonBeamParams::Lookup lk;
     const ParamSet &ps = p->scene.integratorParams;
@@ -106,7 +131,7 @@ bre_status bre_pbrt_render_devices(const bre_pbrt *p, const int32_t *devices, in
     PhotonBeamIntegrator integ(params_of(p, quick), film, std::vector<int>(devices, devices + n_devices));
     if (!integ.Context()) return BRE_ERR_NO_DEVICE;
     integ.writeFiles = write_files != 0;
-    if (!integ.Render(p->scene.scene)) return BRE_ERR_STATE;
+    if (!integ.Render(p->scene.scene, p->scene.lights)) return BRE_ERR_STATE;
     if (image_rgb && !integ.Image().empty())
         memcpy(image_rgb, integ.Image().data(), integ.Image().size() * sizeof(float));
     return BRE_OK;

@@ -316,6 +316,36 @@ bool Xform::IsIdentity() const {
     return true;
 }
 
+void MakeSpotLight(const Xform &l2w, const float from[3], const float to[3], const float I[3], float coneangle,
+                   float conedelta, int order, bre_light *out) {
+    const float ft[3] = {to[0] - from[0], to[1] - from[1], to[2] - from[2]};
+    float dir[3], du[3], dv[3];
+    Normalize3(ft, dir);
+    // CoordinateSystem(dir, &du, &dv), geometry.h:1020-1027
+    if (std::abs(dir[0]) > std::abs(dir[1])) {
+        const float inv = 1 / std::sqrt(dir[0] * dir[0] + dir[2] * dir[2]);
+        du[0] = -dir[2] * inv, du[1] = 0 * inv, du[2] = dir[0] * inv;
+    } else {
+        const float inv = 1 / std::sqrt(dir[1] * dir[1] + dir[2] * dir[2]);
+        du[0] = 0 * inv, du[1] = dir[2] * inv, du[2] = -dir[1] * inv;
+    }
+    Cross3(dir, du, dv);
+    const float rows[4][4] = {{du[0], du[1], du[2], 0}, {dv[0], dv[1], dv[2], 0}, {dir[0], dir[1], dir[2], 0}, {0, 0, 0, 1}};
+    const Xform dirToZ = Xform::FromMatrix(rows);
+    const Xform light2world = l2w * Xform::Translate(from[0], from[1], from[2]) * dirToZ.Inverse();
+    memset(out, 0, sizeof(*out));
+    out->type = BRE_LIGHT_SPOT;
+    for (int k = 0; k < 3; ++k) out->I[k] = I[k];
+    for (int i = 0; i < 4; ++i)
+        for (int j = 0; j < 4; ++j) {
+            out->light_to_world[4 * i + j] = light2world.m[i][j];
+            out->world_to_light[4 * i + j] = light2world.mInv[i][j];
+        }
+    out->cone_total_deg = coneangle;
+    out->cone_falloff_start_deg = coneangle - conedelta;
+    out->order = order;
+}
+
 // ---------------------------------------------------------------------------------------------
 // Tokenizer (pbrtlex.ll)
 
@@ -507,6 +537,7 @@ class Parser {
     std::map<std::string, MediumDef> media_;
     std::map<std::string, Material> namedMaterials_;
     std::vector<ShapeRec> shapes_;
+    std::vector<std::string> lightOutside_;  // per entry of out_->lights: its outside medium
     bool inWorld_ = false, worldEnded_ = false;
     bool cameraLookAtOk_ = false;
     float camLook_[9];
@@ -1040,6 +1071,26 @@ bool Parser::Run(Lexer &lx, int depth) {
                     MakeMaterial(lx, line, type, ps, &m);
                     namedMaterials_[n] = m;
                 }
+            } else if (w == "LightSource" && n == "spot") {
+                // CreateSpotLight (spot.cpp:104-124) with the current transform; the light sits in the
+                // graphics state's outside medium (MakeLight, api.cpp)
+                float I[3] = {1, 1, 1}, sc[3] = {1, 1, 1}, from[3] = {0, 0, 0}, to[3] = {0, 0, 1};
+                ps.FindOneSpectrum("I", I);
+                ps.FindOneSpectrum("scale", sc);
+                const float coneangle = ps.FindOneFloat("coneangle", 30.f);
+                const float conedelta = ps.FindOneFloat("conedeltaangle", 5.f);
+                ps.FindOnePoint3f("from", from);
+                ps.FindOnePoint3f("to", to);
+                for (int k = 0; k < 3; ++k) I[k] = I[k] * sc[k];
+                bre_light L;
+                MakeSpotLight(ctm_, from, to, I, coneangle, conedelta, (int)shapes_.size(), &L);
+                if ((int)out_->lights.size() >= BRE_MAX_LIGHTS) {
+                    Error(lx, line, "more than BRE_MAX_LIGHTS (%d) light sources", BRE_MAX_LIGHTS);
+                } else {
+                    out_->lights.push_back(L);
+                    lightOutside_.push_back(gs_.outside);
+                }
+                ReportUnused(lx, line, ps);
             } else if (w == "LightSource") {
                 Error(lx, line, "LightSource \"%s\" is not supported (diffuse area lights only)", n.c_str());
             } else if (w == "AreaLightSource") {
@@ -1085,7 +1136,7 @@ bool Parser::Finish() {
         return fatal("more than BRE_MAX_SCENE_TRIANGLES (" + std::to_string(BRE_MAX_SCENE_TRIANGLES) + ") triangles");
     int nemit = 0;
     for (size_t i = 0; i < shapes_.size(); ++i) nemit += shapes_[i].tri.emit != 0;
-    if (nemit == 0) return fatal("the scene has no diffuse area light");
+    if (nemit == 0 && o.lights.empty()) return fatal("the scene has no diffuse area light");
     // The camera medium is the outside medium of the graphics state at WorldEnd (api.cpp:651-655).
     const std::string M = gs_.outside;
     const MediumDef *med = nullptr;
@@ -1105,6 +1156,10 @@ bool Parser::Finish() {
             return fatal("shape " + std::to_string(i) + " has MediumInterface \"" + s.inside + "\" \"" + s.outside +
                          "\"; the GPU scene model has one medium (\"" + M + "\") filling all space");
     }
+    for (size_t i = 0; i < lightOutside_.size(); ++i)
+        if (lightOutside_[i] != M)
+            return fatal("light " + std::to_string(i) + " is declared in medium \"" + lightOutside_[i] +
+                         "\"; the GPU scene model has one medium (\"" + M + "\") filling all space");
     bre_scene &sc = o.scene;
     memset(&sc, 0, sizeof(sc));
     sc.n_triangles = (int32_t)shapes_.size();

@@ -24,6 +24,9 @@
 //   * media: "homogeneous" or "heterogeneous" (GridDensityMedium); the scene model has ONE medium
 //     filling all space, so every shape's inside/outside medium and the camera medium must be
 //     that medium (or all empty = vacuum).
+//   * LightSource "spot" ("I" x "scale", "from", "to", "coneangle", "conedeltaangle"): a bre_light with
+//     CreateSpotLight's transform, in PbrtScene::lights; its outside medium must be the scene's medium.
+//     Every other LightSource is reported as unsupported.
 //   * Camera "perspective" ("fov", lensradius 0) whose CTM is Identity followed by one LookAt.
 //   * Film "image" (xresolution, yresolution, filename, scale); Integrator "photonbeam".
 //   * Sampler / PixelFilter / Accelerator are accepted and ignored: the photon-beam integrator
@@ -110,6 +113,7 @@ struct PbrtScene {
     std::vector<bre_triangle> triangles;  // the triangles when there are more than BRE_MAX_TRIANGLES
     // Re-point scene.grid_density / scene.triangles_ext at this object's vectors (after a copy).
     void Bind();
+    std::vector<bre_light> lights;    // LightSource "spot" statements, in declaration order (bre_set_lights)
     FilmDesc film;
     std::string integratorName;       // "photonbeam" expected
     ParamSet integratorParams;        // CreatePhotonBeamIntegrator's ParamSet
@@ -118,6 +122,12 @@ struct PbrtScene {
     int errors = 0, warnings = 0;
     std::string messages;             // Error()/Warning() text, one message per line
 };
+
+// CreateSpotLight (src/lights/spot.cpp:104-124): light2world = l2w * Translate(from) * Inverse(dirToZ) with
+// dirToZ from CoordinateSystem(Normalize(to - from)), world_to_light the tracked inverse of the product;
+// falloffStart = coneangle - conedelta.  I is "I" * "scale"; order = triangles declared before the light.
+void MakeSpotLight(const Xform &l2w, const float from[3], const float to[3], const float I[3], float coneangle,
+                   float conedelta, int order, bre_light *out);
 
 // Parse a .pbrt file / string (pbrtParseFile / pbrtParseString).  Returns false only on a fatal
 // problem (unreadable file, syntax error, no renderable scene); per-statement problems are

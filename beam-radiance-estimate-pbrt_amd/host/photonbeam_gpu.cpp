@@ -197,8 +197,13 @@ int PhotonBeamIntegrator::OnImage(int32_t, const float *L, void *user) {
     return 0;
 }
 
-bool PhotonBeamIntegrator::Render(const bre_scene &scene) {
+bool PhotonBeamIntegrator::Render(const bre_scene &scene, const std::vector<bre_light> &lights) {
     if (!ctx_) return false;
+    for (bre_ctx *c : ctxs_)
+        if (bre_set_lights(c, lights.data(), (int32_t)lights.size()) != BRE_OK) {
+            err_ = bre_last_error(c);
+            return false;
+        }
     bre_render_params rp;
     memset(&rp, 0, sizeof(rp));
     rp.width = film_.xres;

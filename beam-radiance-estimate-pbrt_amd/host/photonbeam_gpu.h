@@ -152,7 +152,8 @@ class PhotonBeamIntegrator {
     PhotonBeamIntegrator &operator=(const PhotonBeamIntegrator &) = delete;
 
     // Integrator::Render(const Scene &): false (with LastError) on any failure.
-    bool Render(const bre_scene &scene);
+    // `lights`: the scene's point and spot lights, set on every context (bre_set_lights) before the render.
+    bool Render(const bre_scene &scene, const std::vector<bre_light> &lights = {});
     // The last image handed to the film, after WriteImage's conversion (top row first, 3 floats
     // per pixel), and how many times the film was written.
     const std::vector<float> &Image() const { return image_; }

@@ -16,14 +16,14 @@ import os
 import numpy as np
 
 from . import load_library
-from .scene import RenderParams, Scene
+from .scene import Light, RenderParams, Scene
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 HOST_LIB_PATH = os.path.join(HERE, "libbre_host.so")
 CLI_PATH = os.path.join(HERE, "host", "bre_pbrt")
 
 EXPORTS = ["bre_pbrt_parse_file", "bre_pbrt_parse_string", "bre_pbrt_free", "bre_pbrt_messages",
-           "bre_pbrt_get_scene", "bre_pbrt_get_render_params", "bre_pbrt_get_film", "bre_pbrt_render",
+           "bre_pbrt_get_scene", "bre_pbrt_get_lights", "bre_pbrt_make_spot_light", "bre_pbrt_get_render_params", "bre_pbrt_get_film", "bre_pbrt_render",
            "bre_pbrt_render_devices", "bre_film_finalize", "bre_write_pfm", "bre_read_pfm"]
 
 _HOST = None
@@ -45,6 +45,8 @@ def load_host_library(path: str = HOST_LIB_PATH) -> ctypes.CDLL:
     lib.bre_pbrt_messages.argtypes = [P, ctypes.POINTER(I32), ctypes.POINTER(I32)]
     lib.bre_pbrt_messages.restype = ctypes.c_char_p
     lib.bre_pbrt_get_scene.argtypes = [P, P]
+    lib.bre_pbrt_get_lights.argtypes = [P, I32, P, ctypes.POINTER(I32)]
+    lib.bre_pbrt_make_spot_light.argtypes = [P, P, P, F, F, P, P, I32, P]
     lib.bre_pbrt_get_render_params.argtypes = [P, I32, P, ctypes.POINTER(I32)]
     lib.bre_pbrt_get_film.argtypes = [P, ctypes.POINTER(I32), ctypes.POINTER(I32), ctypes.POINTER(F),
                                       ctypes.c_char_p, I32]
@@ -79,6 +81,12 @@ class PbrtScene:
             return
         self.scene = Scene()
         assert self._lib.bre_pbrt_get_scene(self._h, ctypes.byref(self.scene)) == 0
+        n = ctypes.c_int32()
+        assert self._lib.bre_pbrt_get_lights(self._h, 0, None, ctypes.byref(n)) == 0
+        arr = (Light * max(n.value, 1))()
+        assert self._lib.bre_pbrt_get_lights(self._h, n.value, arr, ctypes.byref(n)) == 0
+        self.lights = [arr[i] for i in range(n.value)]  # LightSource "spot", for BeamGather.set_lights
+        self._lights_ref = arr
         self.params = RenderParams()
         wf = ctypes.c_int32()
         assert self._lib.bre_pbrt_get_render_params(self._h, int(quick), ctypes.byref(self.params), ctypes.byref(wf)) == 0
@@ -134,6 +142,22 @@ def parse_file(path: str, quick: bool = False) -> PbrtScene:
 
 def parse_string(text: str, quick: bool = False) -> PbrtScene:
     return _parse("bre_pbrt_parse_string", text.encode(), quick)
+
+
+def make_spot_light(frm, to, I, coneangle: float = 30.0, conedelta: float = 5.0, order: int = 0, ctm=None,
+                    ctm_inv=None) -> Light:
+    """bre_pbrt_make_spot_light: the bre_light CreateSpotLight (spot.cpp:104-124) builds for these
+    parameters under the current transform `ctm` (4x4 row-major, None = identity; `ctm_inv` its tracked
+    inverse, None = computed), by the parser's code."""
+    F3 = ctypes.c_float * 3
+    out = Light()
+    mat = lambda a: None if a is None else (ctypes.c_float * 16)(*[float(v) for v in np.asarray(a, np.float32).reshape(-1)])  # noqa: E731
+    m, mi = mat(ctm), mat(ctm_inv)
+    st = load_host_library().bre_pbrt_make_spot_light(F3(*frm), F3(*to), F3(*I), float(coneangle), float(conedelta), m, mi,
+                                                      int(order), ctypes.byref(out))
+    if st != 0:
+        raise PbrtError(f"bre_pbrt_make_spot_light failed with status {st}")
+    return out
 
 
 def film_finalize(L: np.ndarray, scale: float = 1.0) -> np.ndarray:

@@ -33,6 +33,43 @@ class Scene(ctypes.Structure):
         return ctypes.string_at(ctypes.addressof(self), ctypes.sizeof(self))
 
 
+LIGHT_POINT, LIGHT_SPOT = 1, 2
+MAX_LIGHTS = 1024
+
+
+class Light(ctypes.Structure):
+    """bre_light: a PointLight or SpotLight (row-major 4x4 transforms, `order` = triangles declared before it)."""
+    _fields_ = [("type", ctypes.c_int32), ("I", F3), ("light_to_world", ctypes.c_float * 16),
+                ("world_to_light", ctypes.c_float * 16), ("cone_total_deg", ctypes.c_float),
+                ("cone_falloff_start_deg", ctypes.c_float), ("order", ctypes.c_int32)]
+
+    def to_bytes(self) -> bytes:
+        return ctypes.string_at(ctypes.addressof(self), ctypes.sizeof(self))
+
+
+def point_light(p, I, order: int = 0) -> Light:
+    """LightSource "point" at `p` under an identity CTM: LightToWorld = Translate(p) (point.cpp:80-88)."""
+    L = Light()
+    L.type = LIGHT_POINT
+    L.I = _f3(I)
+    for i in range(4):
+        L.light_to_world[5 * i] = L.world_to_light[5 * i] = 1.0
+    for k in range(3):
+        L.light_to_world[4 * k + 3] = float(p[k])
+        L.world_to_light[4 * k + 3] = -float(p[k])
+    L.order = int(order)
+    return L
+
+
+def spot_light(frm, to, I, coneangle: float = 30.0, conedelta: float = 5.0, order: int = 0, ctm=None,
+               ctm_inv=None) -> Light:
+    """LightSource "spot" (spot.cpp:104-124), built by the host library's parser code
+    (bre_pbrt_make_spot_light) so that the matrices are the reference's."""
+    from .pbrt import make_spot_light
+
+    return make_spot_light(frm, to, I, coneangle, conedelta, order, ctm, ctm_inv)
+
+
 class RenderParams(ctypes.Structure):
     """bre_render_params: CreatePhotonBeamIntegrator's parameters (photonbeam.cpp:589-611)."""
     _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("iterations", ctypes.c_int32),

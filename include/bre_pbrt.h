@@ -42,6 +42,19 @@ const char *bre_pbrt_messages(const bre_pbrt *p, int32_t *n_errors, int32_t *n_w
    BRE_MAX_TRIANGLES triangles) triangles_ext point into the parsed scene and stay valid until
    bre_pbrt_free. */
 bre_status bre_pbrt_get_scene(const bre_pbrt *p, bre_scene *out);
+/* The scene's LightSource "spot" statements as bre_light (bre_scene.h), in declaration order, for
+   bre_set_lights: at most `capacity` are written to `out`, *n (may be NULL) receives their number.
+   bre_pbrt_render sets them on every context it makes. */
+bre_status bre_pbrt_get_lights(const bre_pbrt *p, int32_t capacity, bre_light *out, int32_t *n);
+/* A spot light as CreateSpotLight (src/lights/spot.cpp:104-124) builds it, by the code the parser uses:
+   light_to_world = CTM * Translate(from) * Inverse(dirToZ), world_to_light the tracked inverse,
+   cone_falloff_start_deg = coneangle - conedeltaangle.  I is "I" times "scale"; ctm is a row-major 4x4
+   current transform or NULL for the identity, ctm_inv the inverse tracked with it or NULL for
+   Inverse(ctm) as Transform(Matrix4x4) computes it; order as bre_light.order.  (A point light needs only
+   Translate(from): fill its bre_light by hand.) */
+bre_status bre_pbrt_make_spot_light(const float from[3], const float to[3], const float I[3], float coneangle,
+                                    float conedeltaangle, const float *ctm, const float *ctm_inv, int32_t order,
+                                    bre_light *out);
 /* CreatePhotonBeamIntegrator's parameters for the film of the scene (quick != 0 is pbrt's
    --quick); *write_frequency (may be NULL) receives "imagewritefrequency" as given (default 1 << 31 =
    INT32_MIN, never periodic; bre_render_progressive applies the reference's (iter + 1) % k test). */

@@ -22,6 +22,12 @@
  *                       emitting mesh, api.cpp), in triangle order = scene.lights order.  The photon
  *                       pass picks one by power (ComputeLightPowerDistribution,
  *                       integrator.cpp:217-225); the camera pass uniformly (UniformSampleOneLight).
+ *   - point and spot lights (bre_light below; PointLight, src/lights/point.cpp, and SpotLight,
+ *                       src/lights/spot.cpp), set on the context with bre_set_lights and merged with
+ *                       the area lights into scene.lights by their `order`.  The photon pass emits from
+ *                       them with their Sample_Le, the camera pass lights surfaces with their Sample_Li
+ *                       (no MIS, a shadow ray to the light's position); a scene lit only by them needs
+ *                       no emitting triangle.
  *   - an optional medium filling all of space (every ray -- camera, photon, spawned -- travels
  *                       in it) with a Henyey-Greenstein phase function (src/core/medium.cpp:194-213):
  *                       BRE_MEDIUM_HOMOGENEOUS = HomogeneousMedium (src/media/homogeneous.cpp:44-77),
@@ -61,7 +67,8 @@ typedef struct bre_triangle {
 
 typedef struct bre_scene {
     int32_t n_triangles;   /* 1 .. BRE_MAX_TRIANGLES inline, or 1 .. BRE_MAX_SCENE_TRIANGLES through
-                              triangles_ext; at least one with emit != 0 */
+                              triangles_ext; at least one with emit != 0 unless the context holds
+                              lights (bre_set_lights) */
     int32_t has_medium;    /* BRE_MEDIUM_NONE (vacuum) / _HOMOGENEOUS / _GRID, filling all space */
     float sigma_a[3];      /* medium sigma_a (already multiplied by "scale") */
     float sigma_s[3];      /* medium sigma_s */
@@ -86,6 +93,26 @@ typedef struct bre_scene {
        equal-distance hits resolve in the reference's order. */
     const bre_triangle *triangles_ext;
 } bre_scene;
+
+/* Delta lights: pbrt's PointLight (src/lights/point.cpp) and SpotLight (src/lights/spot.cpp).  They are
+   not part of bre_scene (its layout is fixed): a context holds them (bre_set_lights, bre.h) and every
+   pass or render that takes a bre_scene uses the scene's triangles plus the context's lights. */
+#define BRE_LIGHT_POINT 1
+#define BRE_LIGHT_SPOT 2
+#define BRE_MAX_LIGHTS 1024 /* delta lights accepted by bre_set_lights */
+
+typedef struct bre_light {
+    int32_t type;               /* BRE_LIGHT_POINT / BRE_LIGHT_SPOT */
+    float I[3];                 /* "I", already multiplied by "scale" */
+    float light_to_world[16];   /* LightToWorld, row-major 4x4 (a point light: Translate(from) * CTM) */
+    float world_to_light[16];   /* its inverse as the reference tracks it (Transform::mInv), row-major;
+                                   SpotLight::Falloff goes through it */
+    float cone_total_deg;       /* spot: "coneangle" (totalWidth, degrees) */
+    float cone_falloff_start_deg; /* spot: "coneangle" - "conedeltaangle" (falloffStart, degrees) */
+    int32_t order;              /* the number of scene triangles declared before this light: in
+                                   scene.lights the light comes before the area lights of the triangles
+                                   with index >= order; lights of equal order keep their array order */
+} bre_light;
 
 /* PhotonBeamIntegrator parameters (CreatePhotonBeamIntegrator, photonbeam.cpp:589-611). */
 typedef struct bre_render_params {
