@@ -7,8 +7,7 @@
 namespace bre {
 
 // Build the BVH from device arrays (start/end/radius/power) of n beams.
-bre_status build(bre_ctx *c, int64_t n, const float *start, const float *end, const float *radius,
-                 const float *power) {
+bre_status build(bre_ctx *c, int64_t n, const BeamView &in) {
     c->nbeams = n;
     c->nvalid = 0;
     c->bset = BeamSet{};
@@ -25,10 +24,7 @@ bre_status build(bre_ctx *c, int64_t n, const float *start, const float *end, co
                     (long long)n);
     const size_t N = (size_t)n;
     BuildBuffers b;
-    b.start = start;
-    b.end = end;
-    b.radius = radius;
-    b.power = power;
+    b.in = in;
     b.n = n;
     b.sqrt_mode = c->sqrt_mode;
     b.slot = c->slot_passes;
@@ -38,13 +34,13 @@ bre_status build(bre_ctx *c, int64_t n, const float *start, const float *end, co
     HIPCHK(c, c->cent.get(N * 3, &b.cent));
     HIPCHK(c, c->cbounds.get(12, &b.cbounds));
     HIPCHK(c, c->nvalid_buf.get(3, &b.nvalid));
-    HIPCHK(c, c->keys.get(N, &b.keys));
-    HIPCHK(c, c->keys_alt.get(N, &b.keys_alt));
-    HIPCHK(c, c->vals.get(N, &b.vals));
-    HIPCHK(c, c->vals_alt.get(N, &b.vals_alt));
-    HIPCHK(c, c->sort_tmp.ensure(sort_temp_bytes(n)));
-    b.sort_tmp = c->sort_tmp.ptr;
-    b.sort_tmp_bytes = c->sort_tmp.cap;
+    HIPCHK(c, c->sort.reserve(N, 8, sort_temp_bytes(n)));
+    b.keys = c->sort.keys.as<unsigned long long>();
+    b.keys_alt = c->sort.keys_alt.as<unsigned long long>();
+    b.vals = c->sort.vals;
+    b.vals_alt = c->sort.vals_alt;
+    b.sort_tmp = c->sort.tmp.ptr;
+    b.sort_tmp_bytes = c->sort.tmp.cap;
     if (c->timing) HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
     HIPCHK(c, launch_prep(b, c->stream));
     // tree keys 1 / 2 (the tile kernel's tree): the first sort only groups equal centroids (a hash key,
@@ -139,7 +135,7 @@ bre_status bre_set_beams(bre_ctx *c, int64_t n, const float *start, const float 
         HIPCHK(c, c->in.upload((size_t)n, start, end, radius, power, c->stream));
     }
     c->beams_kept = false;
-    BRE_TRY(build(c, n, c->in.start, c->in.end, c->in.radius, c->in.power));
+    BRE_TRY(build(c, n, c->in.view()));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->beams_kept = true;
     return BRE_OK;
@@ -153,7 +149,7 @@ bre_status bre_set_beams_device(bre_ctx *c, int64_t n, const float *start, const
         return fail(c, BRE_ERR_INVALID_ARG, "bre_set_beams_device: null array");
     BRE_TRY(set_device(c));
     c->beams_kept = false;
-    return build(c, n, start, end, radius, power);
+    return build(c, n, BeamView{start, end, radius, power});
 }
 
 bre_status bre_get_beams(bre_ctx *c, int64_t capacity, float *start, float *end, float *radius, float *power,

@@ -95,8 +95,8 @@ bre_status check_read_tree(bre_ctx *c, int64_t n, float *y) {
     float *keys = y + 8, *idx = keys + 2 * nv, *box = idx + nv, *nodes = box + 6 * nv, *lp = nodes + 16 * nn,
           *nodes4 = lp + nleaf;
     std::vector<BeamRec> recs((size_t)nv);
-    HIPCHK(c, hipMemcpyAsync(keys, c->keys_alt.ptr, (size_t)nv * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(idx, c->vals_alt.ptr, (size_t)nv * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(keys, c->sort.keys_alt.ptr, (size_t)nv * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(idx, c->sort.vals_alt.ptr, (size_t)nv * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(recs.data(), c->recs.ptr, (size_t)nv * sizeof(BeamRec), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(nodes, c->nodes.ptr, (size_t)nn * sizeof(Node), hipMemcpyDeviceToHost, c->stream));
     if (nleaf > 1)

@@ -53,8 +53,8 @@ bre_status gather_chunk(bre_ctx *c, const GatherArgs &a) {
     cb.parents = c->recs.as<BeamRec>();
     cb.bset = c->bset;
     cb.nparents = np;
-    cb.seg_o = a.o;
-    cb.seg_p = a.p;
+    cb.seg_o = a.seg.o;
+    cb.seg_p = a.seg.p;
     cb.nseg = a.nseg;
     cb.R = a.R;
     cb.len_factor = (float)c->chunk_len / 100.f;
@@ -89,19 +89,19 @@ bre_status gather_chunk(bre_ctx *c, const GatherArgs &a) {
     HIPCHK(c, c->ch_slo.get(C, &slo));
     HIPCHK(c, c->ch_shi.get(C, &shi));
     HIPCHK(c, c->ch_par.get(C, &par));
-    HIPCHK(c, c->keys.get(C, &bb.keys));
-    HIPCHK(c, c->keys_alt.get(C, &bb.keys_alt));
-    HIPCHK(c, c->vals.get(C, &bb.vals));
-    HIPCHK(c, c->vals_alt.get(C, &bb.vals_alt));
     const size_t sb = sort_temp_bytes(total);
-    HIPCHK(c, c->sort_tmp.ensure(sb + 16));
+    HIPCHK(c, c->sort.reserve(C, 8, sb + 16));
+    bb.keys = c->sort.keys.as<unsigned long long>();
+    bb.keys_alt = c->sort.keys_alt.as<unsigned long long>();
+    bb.vals = c->sort.vals;
+    bb.vals_alt = c->sort.vals_alt;
     HIPCHK(c, c->ch_recs.get(C, &recs));
     HIPCHK(c, c->ch_cpar.get(C, &cpar));
     HIPCHK(c, c->ch_nodes.get((size_t)nnodes, &bb.nodes));
     HIPCHK(c, c->leaf_parent.get((size_t)nleaf, &bb.leaf_parent));
     HIPCHK(c, c->visit.get((size_t)nnodes, &bb.visit));
     HIPCHK(c, launch_chunk_emit(cb, bb.box, bb.cent, slo, shi, par, c->stream));
-    bb.sort_tmp = c->sort_tmp.ptr;
+    bb.sort_tmp = c->sort.tmp.ptr;
     bb.sort_tmp_bytes = sb;
     bb.recs = reinterpret_cast<BeamRec *>(recs);  // same leading lo / hi layout
     bb.nodes_cap = c->ch_nodes.cap / sizeof(Node);
@@ -113,16 +113,10 @@ bre_status gather_chunk(bre_ctx *c, const GatherArgs &a) {
     HIPCHK(c, launch_hierarchy(bb, total, c->stream));
     ChunkGatherArgs g;
     g.nseg = a.nseg;
-    g.o = a.o;
-    g.p = a.p;
-    g.d = a.d;
-    g.tmax = a.tmax;
-    g.pixel = a.pixel;
+    g.seg = a.seg;
     g.R = a.R;
     g.npix = a.npix;
-    g.accum = a.accum;
-    g.seg_rgb = a.seg_rgb;
-    g.seg_counts = a.seg_counts;
+    g.out = a.out;
     g.chunks = recs;
     g.chunk_parent = cpar;
     g.parents = c->recs.as<BeamRec>();
@@ -146,23 +140,16 @@ bre_status gather_chunk(bre_ctx *c, const GatherArgs &a) {
 int tscan_for(float maxd) { return maxd >= 0.015f ? 3 : (maxd >= 0.008f ? 4 : 5); }
 
 // One kernel family on nseg device segments; the caller (gather_segments_core) has checked the arguments.
-bre_status gather_device(bre_ctx *c, int64_t nseg, const float *o, const float *p, const float *d, const float *tmax,
-                         const int32_t *pixel, float R, int64_t npix, float *accum, float *seg_rgb,
-                         int32_t *seg_counts, const int32_t *seg_index = nullptr) {
+bre_status gather_device(bre_ctx *c, int64_t nseg, const SegView &seg, float R, int64_t npix, const GatherOut &out,
+                         const int32_t *seg_index = nullptr) {
     DevCounters *ctr = nullptr;
     BRE_TRY(counters_block(c, &ctr));
     GatherArgs a{};
     a.nseg = nseg;
-    a.o = o;
-    a.p = p;
-    a.d = d;
-    a.tmax = tmax;
-    a.pixel = pixel;
+    a.seg = seg;
     a.R = R;
     a.npix = npix;
-    a.accum = accum;
-    a.seg_rgb = seg_rgb;
-    a.seg_counts = seg_counts;
+    a.out = out;
     a.seg_index = seg_index;
     a.recs = c->recs.as<BeamRec>();
     a.pow = c->pow.as<float4>();
@@ -184,7 +171,7 @@ bre_status gather_device(bre_ctx *c, int64_t nseg, const float *o, const float *
         HIPCHK(c, launch_zero_outputs(a, c->stream));
         return BRE_OK;
     }
-    int kernel = c->kernel;
+    const int kernel = c->kernel;
     // work-root shards split the tile kernel's work roots: kernels 2 and 5 have none, and would gather
     // every segment against every beam on every shard (films summing to count x the image)
     if (c->shard_mode == 2 && c->shard_count > 1 && (kernel == 2 || kernel == 5))
@@ -193,20 +180,20 @@ bre_status gather_device(bre_ctx *c, int64_t nseg, const float *o, const float *
         if (seg_index) return fail(c, BRE_ERR_STATE, "kernel 5 gathers in the caller's order only");
         return gather_chunk(c, a);
     }
-    if (kernel == 0) kernel = 4;  // the tile kernel on the tile tree built for kernel 0
     if (kernel == 2 && seg_index) return fail(c, BRE_ERR_STATE, "kernel 2 gathers in the caller's order only");
     if (kernel == 2) {
         if (c->timing) HIPCHK(c, hipEventRecord(c->ev[2], c->stream));
-        HIPCHK(c, launch_gather(a, kernel, c->counters, c->stream));
+        HIPCHK(c, launch_gather_thread(a, c->counters, c->stream));
         if (c->timing) HIPCHK(c, hipEventRecord(c->ev[3], c->stream));
         return read_counters(c, a.ctr);
     }
+    // Kernels 0 and 4: the tile kernel, each on the tile tree built for it.
     // The tile kernel keeps S partial sums per segment (12 B each, + 8 B of counts when asked for).
     // A gather of many segments runs as consecutive launches over whole-packet ranges, so that the
     // partials stay within partial_cap (4 GiB: C2's ~0.6M segments in one launch, C4's ~9.6M in 7)
     // and the grid within HIP's 2^32 work items.  Every segment's sum is still its subtrees'
     // partials added in root order by k_reduce: the per-segment results do not depend on the split.
-    const bool want_cnt = c->counters || seg_counts;
+    const bool want_cnt = c->counters || out.seg_counts;
     // work-root shards (BRE_OPT_SHARD_MODE 2): this shard takes every count-th work root of the
     // size-ordered list (rank, rank + count, ...) for ALL segments, so its waves sweep whole subtrees
     // with every packet, as one GPU does; the per-segment sums are this shard's subtrees' share
@@ -261,18 +248,12 @@ bre_status gather_device(bre_ctx *c, int64_t nseg, const float *o, const float *
         ac.user_start = off == 0 ? c->user_ev[0] : nullptr;
         ac.user_end = off + chunk >= nseg ? c->user_ev[1] : nullptr;
         ac.nseg = std::min(chunk, nseg - off);
-        ac.o = o + 3 * off;
-        ac.p = p + 3 * off;
-        ac.d = d + 3 * off;
-        ac.tmax = tmax + off;
-        ac.pixel = pixel ? pixel + off : nullptr;
-        if (seg_index) {
+        ac.seg = seg.slice(off);
+        if (seg_index)
             ac.seg_index = seg_index + off;  // outputs are addressed through the index
-        } else {
-            ac.seg_rgb = seg_rgb ? seg_rgb + 3 * off : nullptr;
-            ac.seg_counts = seg_counts ? seg_counts + 2 * off : nullptr;
-        }
-        HIPCHK(c, launch_gather(ac, kernel, c->counters, c->stream));
+        else
+            ac.out = out.slice(off);
+        HIPCHK(c, launch_gather_tile(ac, c->counters, c->stream));
     }
     c->tile_ev_valid = true;
     if (c->timing) HIPCHK(c, hipEventRecord(c->ev[3], c->stream));
@@ -286,28 +267,26 @@ bre_status gather_device(bre_ctx *c, int64_t nseg, const float *o, const float *
 // (bre_shard_segments): the other entries of the per-segment outputs are zeroed, and the shards'
 // films and outputs sum to the one-shard results.  Used by bre_gather_camera (the camera pass's
 // segments), bre_gather_device and bre_gather (the caller's segments).
-bre_status gather_segments_core(bre_ctx *c, int64_t n, const float *o, const float *p, const float *d, const float *t,
-                                const int32_t *pix, float R, int64_t npix, float *d_accum, float *d_seg_rgb,
-                                int32_t *d_seg_counts) {
+bre_status gather_segments_core(bre_ctx *c, int64_t n, const SegView &seg, float R, int64_t npix,
+                                const GatherOut &out) {
     const bool pshard = c->shard_mode == 1 && c->shard_count > 1;
     const bool sortable = c->kernel == 0 || c->kernel == 4;  // kernels 2 / 5 write in the caller's order
-    const bool seg_out = d_seg_rgb || d_seg_counts;
+    const bool seg_out = out.seg_rgb || out.seg_counts;
     if (n < 0 || npix < 0) return fail(c, BRE_ERR_INVALID_ARG, "bre_gather: negative size");
-    if (n > 0 && (!o || !p || !d || !t)) return fail(c, BRE_ERR_INVALID_ARG, "bre_gather: null segment array");
-    if (d_accum && !pix) return fail(c, BRE_ERR_INVALID_ARG, "bre_gather: accum_rgb given without seg_pixel");
+    if (n > 0 && (!seg.o || !seg.p || !seg.d || !seg.t))
+        return fail(c, BRE_ERR_INVALID_ARG, "bre_gather: null segment array");
+    if (out.accum && !seg.pix) return fail(c, BRE_ERR_INVALID_ARG, "bre_gather: accum_rgb given without seg_pixel");
     if (pshard && seg_out) {
         if (!sortable) return fail(c, BRE_ERR_STATE, "packet shards with per-segment outputs need kernel 0 or 4");
         // every entry is defined: the other shards' segments read 0 here
         GatherArgs z{};
         z.nseg = n;
-        z.seg_rgb = d_seg_rgb;
-        z.seg_counts = d_seg_counts;
+        z.out = out;
         HIPCHK(c, launch_zero_outputs(z, c->stream));
     }
     // packet sharding: this shard gathers the chunks c = rank (mod count) of BRE_OPT_SHARD_BLOCK
     // consecutive 64-segment packets of the (sorted) order, copied into contiguous arrays first
-    const auto pick = [&](const float *o, const float *p, const float *d, const float *t, const int32_t *pix,
-                          const int32_t *index) -> bre_status {
+    const auto pick = [&](const SegView &from, const int32_t *index) -> bre_status {
         const int64_t m = bre_shard_segments(n, c->shard_rank, c->shard_count, c->shard_block);
         c->stats.n_segments = m;
         if (m == 0) return BRE_OK;
@@ -315,39 +294,37 @@ bre_status gather_segments_core(bre_ctx *c, int64_t n, const float *o, const flo
         int32_t *sp_index = nullptr;
         HIPCHK(c, sp.ensure((size_t)m));
         if (seg_out) HIPCHK(c, c->sp_index.get((size_t)m, &sp_index));
-        HIPCHK(c, launch_packet_pick(n, m, c->shard_rank, c->shard_count, c->shard_block, o, p, d, t, pix, index, sp.o,
-                                     sp.p, sp.d, sp.t, sp.pix, sp_index, c->stream));
-        return gather_device(c, m, sp.o, sp.p, sp.d, sp.t, pix ? sp.pix.as<int32_t>() : nullptr, R, npix, d_accum,
-                             d_seg_rgb, d_seg_counts, sp_index);
+        const PacketPick pk{n, m, c->shard_rank, c->shard_count, c->shard_block, from, index, sp.out(), sp_index};
+        HIPCHK(c, launch_packet_pick(pk, c->stream));
+        SegView picked = sp.view();
+        if (!from.pix) picked.pix = nullptr;
+        return gather_device(c, m, picked, R, npix, out, sp_index);
     };
     if (!c->sort_segments || n < 2 || (!sortable && seg_out)) {
-        if (pshard) return pick(o, p, d, t, pix, nullptr);
-        return gather_device(c, n, o, p, d, t, pix, R, npix, d_accum, d_seg_rgb, d_seg_counts);
+        if (pshard) return pick(seg, nullptr);
+        return gather_device(c, n, seg, R, npix, out);
     }
     const size_t N = (size_t)n;
-    SegSort ss{n, o, p, d, t, pix};
+    SegSort ss{n, seg};
     HIPCHK(c, c->ss_bounds.get(8, &ss.bounds));
-    HIPCHK(c, c->ss_keys.get(N, &ss.keys));
-    HIPCHK(c, c->ss_keys_alt.get(N, &ss.keys_alt));
-    HIPCHK(c, c->ss_vals.get(N, &ss.vals));
-    HIPCHK(c, c->ss_vals_alt.get(N, &ss.vals_alt));
     ss.tmp_bytes = seg_sort_temp_bytes(n);
-    HIPCHK(c, c->ss_tmp.ensure(ss.tmp_bytes + 16));
-    ss.tmp = c->ss_tmp.ptr;
+    HIPCHK(c, c->ss_sort.reserve(N, 8, ss.tmp_bytes + 16));
+    ss.keys = c->ss_sort.keys.as<unsigned long long>();
+    ss.keys_alt = c->ss_sort.keys_alt.as<unsigned long long>();
+    ss.vals = c->ss_sort.vals;
+    ss.vals_alt = c->ss_sort.vals_alt;
+    ss.tmp = c->ss_sort.tmp.ptr;
     HIPCHK(c, c->ss.ensure(N));
-    ss.o2 = c->ss.o;
-    ss.p2 = c->ss.p;
-    ss.d2 = c->ss.d;
-    ss.t2 = c->ss.t;
-    ss.pix2 = c->ss.pix;
+    ss.out = c->ss.out();
     ss.key_mode = c->sort_key;
     ss.slot = c->slot_passes;
     ss.key_lo = c->coarse_keys ? 12 : 0;
     HIPCHK(c, launch_sort_segments(ss, c->stream));
     // ss.vals_alt[i] = the caller's index of sorted segment i (the sort's permutation)
-    if (pshard) return pick(ss.o2, ss.p2, ss.d2, ss.t2, ss.pix2, ss.vals_alt);
-    return gather_device(c, n, ss.o2, ss.p2, ss.d2, ss.t2, pix ? ss.pix2 : nullptr, R, npix, d_accum, d_seg_rgb,
-                         d_seg_counts, seg_out ? ss.vals_alt : nullptr);
+    SegView sorted = ss.out;
+    if (pshard) return pick(sorted, ss.vals_alt);
+    if (!seg.pix) sorted.pix = nullptr;
+    return gather_device(c, n, sorted, R, npix, out, seg_out ? ss.vals_alt : nullptr);
 }
 
 // A gather of n caller-order segments.  With a film (d_accum) the production kernels (0 / 4) add to it
@@ -357,10 +334,9 @@ bre_status gather_segments_core(bre_ctx *c, int64_t n, const float *o, const flo
 // as the reference's pixel.Ld += does (photonbeam.cpp:477-504) -- with one thread per pixel and no
 // float atomics, so the film is the same bits on every run.  Kernels 2 and 5 (cross-checks) add by
 // float atomics.
-bre_status gather_segments(bre_ctx *c, int64_t n, const float *o, const float *p, const float *d, const float *t,
-                           const int32_t *pix, float R, int64_t npix, float *d_accum, float *d_seg_rgb,
-                           int32_t *d_seg_counts) {
+bre_status gather_segments(bre_ctx *c, int64_t n, const SegView &seg, float R, int64_t npix, const GatherOut &out) {
     const bool sortable = c->kernel == 0 || c->kernel == 4;
+    float *const d_accum = out.accum;
     if (c->film_classes > 1 && d_accum && (!sortable || !c->film_compose))
         return fail(c, BRE_ERR_STATE, "BRE_OPT_FILM_CLASSES needs the deterministic compose of kernels 0 / 4");
     // work-root shards gather every segment against a subset of the subtrees: each rank's sums are partial in
@@ -369,20 +345,20 @@ bre_status gather_segments(bre_ctx *c, int64_t n, const float *o, const float *p
         return fail(c, BRE_ERR_STATE, "BRE_OPT_FILM_CLASSES needs packet shards (BRE_OPT_SHARD_MODE 1), not work-root shards");
     if (c->film_classes > 1 && d_accum && (uint64_t)BRE_FILM_CLASSES * (uint64_t)(npix + 1) > 0xffffffffull)
         return fail(c, BRE_ERR_INVALID_ARG, "BRE_OPT_FILM_CLASSES: the film is too large for the class keys");
-    if (!d_accum || !sortable || n <= 0 || !pix || c->nvalid == 0 || !c->film_compose)
-        return gather_segments_core(c, n, o, p, d, t, pix, R, npix, d_accum, d_seg_rgb, d_seg_counts);
+    if (!d_accum || !sortable || n <= 0 || !seg.pix || c->nvalid == 0 || !c->film_compose)
+        return gather_segments_core(c, n, seg, R, npix, out);
     const size_t N = (size_t)n;
-    float *segbuf = d_seg_rgb;
+    float *segbuf = out.seg_rgb;
     if (!segbuf) HIPCHK(c, c->px_seg.get(N * 3, &segbuf));
-    BRE_TRY(gather_segments_core(c, n, o, p, d, t, pix, R, npix, nullptr, segbuf, d_seg_counts));
-    PixelCompose pc{n, pix, segbuf, npix, d_accum, nullptr, c->film_classes};
-    HIPCHK(c, c->px_keys.get(N, &pc.keys));
-    HIPCHK(c, c->px_keys_alt.get(N, &pc.keys_alt));
-    HIPCHK(c, c->px_vals.get(N, &pc.vals));
-    HIPCHK(c, c->px_vals_alt.get(N, &pc.vals_alt));
+    BRE_TRY(gather_segments_core(c, n, seg, R, npix, GatherOut{nullptr, segbuf, out.seg_counts}));
+    PixelCompose pc{n, seg.pix, segbuf, npix, d_accum, nullptr, c->film_classes};
     pc.tmp_bytes = pixel_sort_temp_bytes(n);
-    HIPCHK(c, c->px_tmp.ensure(pc.tmp_bytes + 16));
-    pc.tmp = c->px_tmp.ptr;
+    HIPCHK(c, c->px_sort.reserve(N, 4, pc.tmp_bytes + 16));
+    pc.keys = c->px_sort.keys.as<unsigned int>();
+    pc.keys_alt = c->px_sort.keys_alt.as<unsigned int>();
+    pc.vals = c->px_sort.vals;
+    pc.vals_alt = c->px_sort.vals_alt;
+    pc.tmp = c->px_sort.tmp.ptr;
     // the flags word of the counter block (a packet shard with no segments never reached the gather's
     // counters_block, so make sure it exists)
     if (!c->counters_buf.ptr) {
@@ -397,8 +373,8 @@ bre_status gather_segments(bre_ctx *c, int64_t n, const float *o, const float *p
         uint8_t *cls = nullptr;
         HIPCHK(c, c->px_cls.get(N, &cls));
         const bool sorted = c->sort_segments && n >= 2;
-        HIPCHK(c, launch_seg_classes(n, c->shard_block, c->film_classes, sorted ? c->ss_vals_alt.as<int32_t>() : nullptr,
-                                     cls, c->stream));
+        HIPCHK(c, launch_seg_classes(n, c->shard_block, c->film_classes,
+                                     sorted ? c->ss_sort.vals_alt.as<int32_t>() : nullptr, cls, c->stream));
         pc.cls = cls;
     }
     HIPCHK(c, launch_pixel_compose(pc, c->stream));
@@ -406,25 +382,26 @@ bre_status gather_segments(bre_ctx *c, int64_t n, const float *o, const float *p
 }
 
 // The camera segments of the last camera pass against the beam set (gather_segments).
-bre_status gather_camera(bre_ctx *c, float R, float *d_accum, float *d_seg_rgb, int32_t *d_seg_counts) {
+bre_status gather_camera(bre_ctx *c, float R, const GatherOut &out) {
     if (c->cam_npix == 0) return fail(c, BRE_ERR_STATE, "bre_gather_camera: no camera pass yet");
     BRE_TRY(set_device(c));
-    return gather_segments(c, c->cam_nseg, c->seg.o, c->seg.p, c->seg.d, c->seg.t, c->seg.pix, R, c->cam_npix, d_accum,
-                           d_seg_rgb, d_seg_counts);
+    return gather_segments(c, c->cam_nseg, c->seg.view(), R, c->cam_npix, out);
 }
 
 }  // namespace
 
 namespace bre {
 
-bre_status gather_host(bre_ctx *c, int64_t nseg, const float *o, const float *p, const float *d, const float *tmax,
-                       const int32_t *pixel, float R, int64_t npix, float *accum, float *seg_rgb, int32_t *seg_counts,
+bre_status gather_host(bre_ctx *c, int64_t nseg, const SegView &seg, float R, int64_t npix, const GatherOut &out,
                        bool film_stays) {
     if (!c) return BRE_ERR_INVALID_ARG;
+    const int32_t *const pixel = seg.pix;
+    float *const accum = out.accum, *const seg_rgb = out.seg_rgb;
+    int32_t *const seg_counts = out.seg_counts;
     if (nseg < 0 || npix < 0) return fail(c, BRE_ERR_INVALID_ARG, "bre_gather: negative size");
     if (c->film_classes > 1 && accum)
         return fail(c, BRE_ERR_STATE, "bre_gather: BRE_OPT_FILM_CLASSES is for caller device films (bre_gather_device)");
-    if (nseg > 0 && (!o || !p || !d || !tmax))
+    if (nseg > 0 && (!seg.o || !seg.p || !seg.d || !seg.t))
         return fail(c, BRE_ERR_INVALID_ARG, "bre_gather: null segment array");
     if (accum && !pixel) return fail(c, BRE_ERR_INVALID_ARG, "bre_gather: accum_rgb given without seg_pixel");
     if (accum && pixel) {
@@ -454,7 +431,7 @@ bre_status gather_host(bre_ctx *c, int64_t nseg, const float *o, const float *p,
     }
     SegArrays &g = c->g;
     HIPCHK(c, g.ensure(S, pixel != nullptr));
-    HIPCHK(c, g.upload(S, o, p, d, tmax, pixel, c->stream));
+    HIPCHK(c, g.upload(S, seg.o, seg.p, seg.d, seg.t, pixel, c->stream));
     float *daccum = nullptr, *dseg = nullptr;
     int32_t *dcnt = nullptr;
     if (accum && npix > 0) {
@@ -464,8 +441,9 @@ bre_status gather_host(bre_ctx *c, int64_t nseg, const float *o, const float *p,
     }
     if (seg_rgb) HIPCHK(c, c->g_seg_rgb.get(S * 3, &dseg));
     if (seg_counts) HIPCHK(c, c->g_counts.get(S * 2, &dcnt));
-    BRE_TRY(gather_segments(c, nseg, g.o, g.p, g.d, g.t, pixel ? g.pix.as<int32_t>() : nullptr, R, npix, daccum, dseg,
-                            dcnt));
+    SegView staged = g.view();
+    if (!pixel) staged.pix = nullptr;
+    BRE_TRY(gather_segments(c, nseg, staged, R, npix, GatherOut{daccum, dseg, dcnt}));
     if (daccum && !film_stays) HIPCHK(c, hipMemcpyAsync(accum, daccum, P * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     if (dseg) HIPCHK(c, hipMemcpyAsync(seg_rgb, dseg, S * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     if (dcnt) HIPCHK(c, hipMemcpyAsync(seg_counts, dcnt, S * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
@@ -478,12 +456,12 @@ extern "C" {
 
 bre_status bre_gather_camera(bre_ctx *c, float R, float *d_accum) {
     if (!c) return BRE_ERR_INVALID_ARG;
-    return gather_camera(c, R, d_accum, nullptr, nullptr);
+    return gather_camera(c, R, GatherOut{d_accum, nullptr, nullptr});
 }
 
 bre_status bre_gather_camera_segments(bre_ctx *c, float R, float *d_accum, float *d_seg_rgb, int32_t *d_seg_counts) {
     if (!c) return BRE_ERR_INVALID_ARG;
-    return gather_camera(c, R, d_accum, d_seg_rgb, d_seg_counts);
+    return gather_camera(c, R, GatherOut{d_accum, d_seg_rgb, d_seg_counts});
 }
 
 bre_status bre_gather_device(bre_ctx *c, int64_t nseg, const float *o, const float *p, const float *d,
@@ -491,13 +469,14 @@ bre_status bre_gather_device(bre_ctx *c, int64_t nseg, const float *o, const flo
                              float *seg_rgb, int32_t *seg_counts) {
     if (!c) return BRE_ERR_INVALID_ARG;
     BRE_TRY(set_device(c));
-    return gather_segments(c, nseg, o, p, d, tmax, pixel, R, npix, accum, seg_rgb, seg_counts);
+    return gather_segments(c, nseg, SegView{o, p, d, tmax, pixel}, R, npix, GatherOut{accum, seg_rgb, seg_counts});
 }
 
 bre_status bre_gather(bre_ctx *c, int64_t nseg, const float *o, const float *p, const float *d, const float *tmax,
                       const int32_t *pixel, float R, int64_t npix, float *accum, float *seg_rgb,
                       int32_t *seg_counts) {
-    return gather_host(c, nseg, o, p, d, tmax, pixel, R, npix, accum, seg_rgb, seg_counts, false);
+    return gather_host(c, nseg, SegView{o, p, d, tmax, pixel}, R, npix, GatherOut{accum, seg_rgb, seg_counts},
+                       false);
 }
 
 bre_status bre_film_add(bre_ctx *c, int64_t n_floats, float *d_src, float *d_dst, int32_t clear_src) {

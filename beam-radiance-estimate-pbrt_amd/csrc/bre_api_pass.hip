@@ -235,11 +235,11 @@ bre_status bre_trace_photons(bre_ctx *c, const bre_scene *scene, int64_t n_photo
     BeamArrays &slots = c->ph_s, &in = c->in;
     if (cap > 0) {
         HIPCHK(c, slots.ensure(N * (size_t)cap));
-        HIPCHK(c, launch_photons(ds, sdepth, n_photons, seq0, max_depth, beam_radius, counts, nullptr, slots.start,
-                                 slots.end, slots.radius, slots.power, 2, cap, c->stream));
+        HIPCHK(c, launch_photons(ds, sdepth, n_photons, seq0, max_depth, beam_radius, counts, nullptr, slots.out(), 2, cap,
+                                 c->stream));
     } else {
-        HIPCHK(c, launch_photons(ds, sdepth, n_photons, seq0, max_depth, beam_radius, counts, nullptr, nullptr, nullptr,
-                                 nullptr, nullptr, 0, 0, c->stream));
+        HIPCHK(c, launch_photons(ds, sdepth, n_photons, seq0, max_depth, beam_radius, counts, nullptr, BeamOut{}, 0, 0,
+                                 c->stream));
     }
     HIPCHK(c, launch_count_scan(c->ph_tmp.ptr, c->ph_tmp.cap, counts, offsets, n_photons, c->stream,
                                 c->slot_passes != 0));
@@ -248,11 +248,10 @@ bre_status bre_trace_photons(bre_ctx *c, const bre_scene *scene, int64_t n_photo
     if (total > 0) {
         HIPCHK(c, in.ensure((size_t)total));
         if (cap > 0)
-            HIPCHK(c, launch_photon_slots(n_photons, cap, counts, offsets, slots.start, slots.end, slots.radius,
-                                          slots.power, in.start, in.end, in.radius, in.power, c->stream));
+            HIPCHK(c, launch_photon_slots(n_photons, cap, counts, offsets, slots.view(), in.out(), c->stream));
         // every photon (two-trace form), or only those with more beams than slots
-        HIPCHK(c, launch_photons(ds, sdepth, n_photons, seq0, max_depth, beam_radius, counts, offsets, in.start, in.end,
-                                 in.radius, in.power, 1, cap, c->stream));
+        HIPCHK(c, launch_photons(ds, sdepth, n_photons, seq0, max_depth, beam_radius, counts, offsets, in.out(), 1, cap,
+                                 c->stream));
     }
     float photon_ms = 0.f;
     if (c->timing) {
@@ -261,7 +260,7 @@ bre_status bre_trace_photons(bre_ctx *c, const bre_scene *scene, int64_t n_photo
         HIPCHK(c, hipEventElapsedTime(&photon_ms, c->ev[0], c->ev[1]));
     }
     c->beams_kept = false;
-    BRE_TRY(build(c, total, in.start, in.end, in.radius, in.power));
+    BRE_TRY(build(c, total, in.view()));
     c->beams_kept = true;
     c->stats.n_photons = n_photons;
     c->stats.photon_ms = photon_ms;
@@ -310,7 +309,7 @@ bre_status bre_camera_pass(bre_ctx *c, const bre_scene *scene, int32_t width, in
     HIPCHK(c, c->cam_tmp.ensure(camera_scan_temp_bytes((int64_t)S) + 16));
     HIPCHK(c, c->cam_flags.get(1, &cam_flags));
     HIPCHK(c, fill_words(c, cam_flags, sizeof(unsigned int)));
-    CamSlots cs{c->cs.o, c->cs.p, c->cs.d, c->cs.t, c->cs.pix, valid};
+    CamSlots cs{c->cs.out(), valid};
     if (c->timing) HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
     HIPCHK(c, launch_camera(c->ph_scene.as<DevScene>(), c->sc_head.stack_depth, c->cam_dev.as<DevCamera>(),
                             c->cam_perms.as<uint16_t>(),
@@ -330,8 +329,7 @@ bre_status bre_camera_pass(bre_ctx *c, const bre_scene *scene, int32_t width, in
     const size_t N = (size_t)(n > 0 ? n : 1);
     HIPCHK(c, c->seg.ensure(N));
     HIPCHK(c, c->seg_depth.get(N, &depth));
-    HIPCHK(c, launch_camera_compact(cs, nslots, max_depth, offs, c->seg.o, c->seg.p, c->seg.d, c->seg.t, c->seg.pix,
-                                    depth, c->stream));
+    HIPCHK(c, launch_camera_compact(cs, nslots, max_depth, offs, c->seg.out(), depth, c->stream));
     float ms = 0.f;
     if (c->timing) {
         HIPCHK(c, hipEventRecord(c->ev[1], c->stream));

@@ -247,8 +247,9 @@ bre_status bre_gather_sharded(bre_ctx *const *ctxs, int n_ctx, int64_t nseg, con
             const size_t k = (size_t)i;
             if (seg_rgb) rgb[k].assign(S * 3, 0.f);
             if (seg_counts) cnt[k].assign(S * 2, 0);
-            BRE_TRY(gather_host(ctxs[i], nseg, o, p, d, tmax, pixel, R, npix, F ? accum : nullptr,
-                                seg_rgb ? rgb[k].data() : nullptr, seg_counts ? cnt[k].data() : nullptr, true));
+            const GatherOut out{F ? accum : nullptr, seg_rgb ? rgb[k].data() : nullptr,
+                                seg_counts ? cnt[k].data() : nullptr};
+            BRE_TRY(gather_host(ctxs[i], nseg, SegView{o, p, d, tmax, pixel}, R, npix, out, true));
             return F ? coll.mark(i) : BRE_OK;
         });
     }

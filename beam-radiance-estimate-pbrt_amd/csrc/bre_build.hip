@@ -31,19 +31,12 @@
 #include <algorithm>
 
 #include "bre_device.h"
+#include "bre_lane.h"
 #include "bre_math.h"
 
 namespace bre {
 
 namespace {
-
-__device__ __forceinline__ unsigned int f2ord(float f) {
-    unsigned int u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float ord2f(unsigned int u) {
-    return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
-}
 
 __device__ __forceinline__ bool finite6(const float *b) {
     bool ok = true;
@@ -524,7 +517,7 @@ hipError_t launch_prep(const BuildBuffers &b, hipStream_t s) {
     // grid-stride over 512 blocks: each block's reduction ends in 14 same-address atomics, which the L2
     // serialises (~70 ns each): 2048 blocks cost ~0.2 ms of them at C2
     const unsigned prep_grid = (unsigned)std::min<int64_t>((int64_t)grid_for(b.n), 512);
-    hipLaunchKernelGGL(k_prep, dim3(prep_grid), dim3(kBlock), 0, s, b.start, b.end, b.radius, b.n, b.sqrt_mode,
+    hipLaunchKernelGGL(k_prep, dim3(prep_grid), dim3(kBlock), 0, s, b.in.start, b.in.end, b.in.radius, b.n, b.sqrt_mode,
                        b.box, b.cent, b.cbounds, b.nvalid);
     return hipGetLastError();
 }
@@ -547,7 +540,7 @@ hipError_t launch_tree_key(const BuildBuffers &b, int64_t nvalid, hipStream_t s)
     if (nvalid > 0)
         hipLaunchKernelGGL(k_group, dim3(grid_for(nvalid)), dim3(kBlock), 0, s, b.box, b.cent, b.keys_alt, b.vals_alt,
                            nvalid, b.gbox);
-    hipLaunchKernelGGL(k_morton_se, dim3(grid_for(b.n)), dim3(kBlock), 0, s, b.box, b.cent, b.start, b.end,
+    hipLaunchKernelGGL(k_morton_se, dim3(grid_for(b.n)), dim3(kBlock), 0, s, b.box, b.cent, b.in.start, b.in.end,
                        b.cbounds + 6, b.n, b.beam_key == 2 ? 1 : 0, b.keys, b.vals);
     return hipGetLastError();
 }
@@ -572,10 +565,10 @@ hipError_t launch_sort(const BuildBuffers &b, hipStream_t s, int end_bit, int be
 hipError_t launch_pack(const BuildBuffers &b, int64_t nvalid, hipStream_t s) {
     if (nvalid == 0) return hipSuccess;
     if (b.beam_key >= 1)
-        hipLaunchKernelGGL(k_pack<true>, dim3(grid_for(nvalid)), dim3(kBlock), 0, s, b.start, b.end, b.radius, b.power,
+        hipLaunchKernelGGL(k_pack<true>, dim3(grid_for(nvalid)), dim3(kBlock), 0, s, b.in.start, b.in.end, b.in.radius, b.in.power,
                            b.box, b.cent, b.keys_alt, b.vals_alt, nvalid, b.gbox, b.recs, b.pow, b.uniform_radius);
     else
-        hipLaunchKernelGGL(k_pack<false>, dim3(grid_for(nvalid)), dim3(kBlock), 0, s, b.start, b.end, b.radius, b.power,
+        hipLaunchKernelGGL(k_pack<false>, dim3(grid_for(nvalid)), dim3(kBlock), 0, s, b.in.start, b.in.end, b.in.radius, b.in.power,
                            b.box, b.cent, b.keys_alt, b.vals_alt, nvalid, nullptr, b.recs, b.pow, b.uniform_radius);
     return hipGetLastError();
 }

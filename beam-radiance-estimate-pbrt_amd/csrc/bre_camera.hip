@@ -558,7 +558,7 @@ hipError_t launch_camera(const DevScene *scene, int stack_depth, const DevCamera
     if (nslots == 0) return hipSuccess;
     hipLaunchKernelGGL(k_camera, dim3((unsigned)(nslots / kCamBlock)), dim3(kCamBlock),
                        scene_stack_bytes(stack_depth, kCamBlock), stream, scene, cam, perms,
-                       iteration, max_depth, render_surfaces, render_media, nslots, s.o, s.p, s.d, s.t, s.pix,
+                       iteration, max_depth, render_surfaces, render_media, nslots, s.seg.o, s.seg.p, s.seg.d, s.seg.t, s.seg.pix,
                        s.valid, surface, flags, shard_rank, shard_count, shard_block, classes < 1 ? 1 : classes);
     return hipGetLastError();
 }
@@ -579,13 +579,13 @@ hipError_t launch_camera_scan(void *tmp, size_t tmp_bytes, const CamSlots &s, in
                                    stream);
 }
 
-hipError_t launch_camera_compact(const CamSlots &s, int64_t nslots, int max_depth, const int64_t *offs, float *o,
-                                 float *p, float *d, float *t, int32_t *pix, int32_t *depth, hipStream_t stream) {
+hipError_t launch_camera_compact(const CamSlots &s, int64_t nslots, int max_depth, const int64_t *offs,
+                                 const SegOut &out, int32_t *depth, hipStream_t stream) {
     const int64_t total = nslots * max_depth;
     if (total == 0) return hipSuccess;
     const unsigned blocks = (unsigned)((total + 63) / 64);  // one-wave workgroups (bre_slot.hip)
-    hipLaunchKernelGGL(k_compact, dim3(blocks), dim3(64), 0, stream, total, s.valid, offs, s.o, s.p, s.d, s.t,
-                       s.pix, o, p, d, t, pix, depth, nslots);
+    hipLaunchKernelGGL(k_compact, dim3(blocks), dim3(64), 0, stream, total, s.valid, offs, s.seg.o, s.seg.p,
+                       s.seg.d, s.seg.t, s.seg.pix, out.o, out.p, out.d, out.t, out.pix, depth, nslots);
     return hipGetLastError();
 }
 

@@ -48,14 +48,6 @@ constexpr int kChunkBlock = 128;
 constexpr int kChunkStack = 64;
 constexpr int kMaxChunksPerBeam = 1 << 16;
 
-__device__ __forceinline__ unsigned int f2ord(float f) {
-    unsigned int u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float ord2f(unsigned int u) {
-    return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
-}
-
 __device__ __forceinline__ void wave_minmax_atomic(unsigned int mn[3], unsigned int mx[3], bool any,
                                                    unsigned int *bounds) {
 #pragma unroll
@@ -473,9 +465,9 @@ hipError_t launch_gather_chunk(const ChunkGatherArgs &a, bool counters, hipStrea
     if (a.nseg == 0) return hipSuccess;
     const dim3 grid(grid_of(a.nseg, kChunkBlock));
 #define BRE_LAUNCH_CHUNK(C, P)                                                                                     \
-    hipLaunchKernelGGL((k_gather_chunk<C, P>), grid, dim3(kChunkBlock), 0, s, a.nseg, a.o, a.p, a.d, a.tmax,       \
-                       a.pixel, a.R, a.npix, a.accum, a.seg_rgb, a.seg_counts, a.chunks, a.chunk_parent, a.parents, \
-                       a.pow, a.nodes, a.nchunks, a.leaf_size, a.ctr)
+    hipLaunchKernelGGL((k_gather_chunk<C, P>), grid, dim3(kChunkBlock), 0, s, a.nseg, a.seg.o, a.seg.p, a.seg.d,   \
+                       a.seg.t, a.seg.pix, a.R, a.npix, a.out.accum, a.out.seg_rgb, a.out.seg_counts, a.chunks,    \
+                       a.chunk_parent, a.parents, a.pow, a.nodes, a.nchunks, a.leaf_size, a.ctr)
     if (counters) {
         if (a.prefilter) BRE_LAUNCH_CHUNK(true, true);
         else BRE_LAUNCH_CHUNK(true, false);

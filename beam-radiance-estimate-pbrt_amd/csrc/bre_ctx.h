@@ -85,6 +85,8 @@ struct BeamArrays {
         if (e == hipSuccess) e = hipMemcpyAsync(hp, power, n * 3 * sizeof(float), hipMemcpyDeviceToHost, s);
         return e;
     }
+    BeamView view() const { return {start, end, radius, power}; }
+    BeamOut out() const { return {start, end, radius, power}; }
 };
 
 // Camera segments: o, p and d hold 3 floats per segment, t (tmax) 1, pix the pixel index
@@ -115,6 +117,22 @@ struct SegArrays {
         if (e == hipSuccess) e = hipMemcpyAsync(hd, d, n * 3 * sizeof(float), hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipMemcpyAsync(ht, t, n * sizeof(float), hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipMemcpyAsync(hpix, pix, n * sizeof(int32_t), hipMemcpyDeviceToHost, s);
+        return e;
+    }
+    SegView view() const { return {o, p, d, t, pix}; }
+    SegOut out() const { return {o, p, d, t, pix}; }
+};
+
+// The double-buffered keys and values of a radix sort and its temporary storage
+struct SortScratch {
+    DevMem keys, keys_alt, tmp;
+    DevArr<int32_t> vals, vals_alt;
+    hipError_t reserve(size_t n, size_t key_bytes, size_t tmp_bytes) {
+        hipError_t e = keys.ensure(n * key_bytes);
+        if (e == hipSuccess) e = keys_alt.ensure(n * key_bytes);
+        if (e == hipSuccess) e = vals.reserve(n);
+        if (e == hipSuccess) e = vals_alt.reserve(n);
+        if (e == hipSuccess) e = tmp.ensure(tmp_bytes);
         return e;
     }
 };
@@ -174,12 +192,13 @@ struct bre_ctx {
     bre::BeamSet bset;  // the built set's radius layout (BeamRec)
     int built_leaf_size = 1;
     int built_key_lo = 0;           // BuildBuffers::key_lo of the current build (bre_device_check kind 11)
-    bool build_scratch_ok = false;  // keys_alt / vals_alt / leaf_parent still hold the current build's (kind 11)
+    bool build_scratch_ok = false;  // sort.keys_alt / sort.vals_alt / leaf_parent still hold the current build's (kind 11)
     int roots_split = -1;           // split the roots buffer was computed for (-1: stale)
     bool nodes4_ok = false;         // nodes4 holds the 4-wide view of the current tree
     bool beams_kept = false;        // `in` holds the current beam set (bre_get_beams)
     bre::BeamArrays in;             // staging for host-pointer uploads, and the photon pass's beams
-    bre::DevMem box, cent, cbounds, nvalid_buf, keys, keys_alt, vals, vals_alt, sort_tmp, leaf_parent, visit, gbox;
+    bre::DevMem box, cent, cbounds, nvalid_buf, leaf_parent, visit, gbox;
+    bre::SortScratch sort;  // the build's sort; reused by kernel 5's chunk index (gather_chunk)
     bre::DevMem recs, pow, nodes;
     // gather
     bre::SegArrays g;  // staging of the host-pointer API; g.pix only with a seg_pixel array
@@ -190,12 +209,14 @@ struct bre_ctx {
         ch_recs, ch_cpar, ch_nodes;
     int64_t n_chunks = 0;
     // coherence sort of the segments before the gather (bre_sort.hip)
-    bre::DevMem ss_bounds, ss_keys, ss_keys_alt, ss_vals, ss_vals_alt, ss_tmp;
+    bre::DevMem ss_bounds;
+    bre::SortScratch ss_sort;
     bre::SegArrays ss;
     bre::SegArrays sp;    // this packet shard's segments (contiguous)
     bre::DevMem sp_index;  // only with per-segment outputs
     // deterministic per-pixel compose; px_cls the film class per segment (BRE_OPT_FILM_CLASSES)
-    bre::DevMem px_seg, px_keys, px_keys_alt, px_vals, px_vals_alt, px_tmp, px_cls;
+    bre::DevMem px_seg, px_cls;
+    bre::SortScratch px_sort;
     // photon pass
     bre::DevMem ph_scene, ph_counts, ph_offsets, ph_tmp, grid_dens;
     bre::BeamArrays ph_s;  // single-trace photon pass: per-photon beam slots
@@ -241,15 +262,15 @@ bre_status counters_block(bre_ctx *c, DevCounters **out);
 bre_status check_flags(bre_ctx *c);
 // bre_api_gather.hip: bre_gather; with film_stays the film starts at zero on the device (accum_rgb is only
 // the "a film is wanted" flag), stays there as c->g_accum and is not copied back (bre_gather_sharded)
-bre_status gather_host(bre_ctx *c, int64_t nseg, const float *o, const float *p, const float *d, const float *tmax,
-                       const int32_t *pixel, float R, int64_t npix, float *accum, float *seg_rgb, int32_t *seg_counts,
+// (seg and out are host arrays here)
+bre_status gather_host(bre_ctx *c, int64_t nseg, const SegView &seg, float R, int64_t npix, const GatherOut &out,
                        bool film_stays);
 // bre_api_pass.hip
 bre_status check_params(bre_ctx *c, const bre_render_params *rp);
 // the write schedule of bre_render_progressive: is an image due after iteration `it`?
 bool image_due(int32_t it, int32_t end_iteration, int32_t write_frequency);
 // bre_api_build.hip
-bre_status build(bre_ctx *c, int64_t n, const float *start, const float *end, const float *radius, const float *power);
+bre_status build(bre_ctx *c, int64_t n, const BeamView &in);
 
 #define HIPCHK(ctx, call)                                                                                    \
     do {                                                                                                     \

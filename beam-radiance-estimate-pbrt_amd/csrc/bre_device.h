@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "bre_views.h"
+
 namespace bre {
 
 // One beam in BVH (sorted) order: 64 B, one cache line.  Everything the per-pair test needs.
@@ -57,6 +59,9 @@ static_assert(sizeof(Node4) == 128, "Node4 must be two 64-B lines");
 constexpr int kStackDepth = 128;     // wave-uniform traversal stack (entries per wave)
 constexpr int kThreadStackDepth = 64;  // per-thread stack of the thread-per-segment kernel
 constexpr int kMaxSplit = 1024;         // max work roots (subtrees) per gather
+// the kernels around the gather run in one-wave workgroups (bre_slot.hip: they then fit the slots a
+// concurrent gather's retiring waves free, so the pipelined pass chain runs inside the other gather)
+constexpr int kPassBlock = 64;
 
 // DevCounters::flags bits.  The host reads the word at every synchronising call and turns a set bit
 // into an error (bre_api.hip: check_flags), whatever the counters option.
@@ -81,7 +86,7 @@ struct DevCounters {
 
 struct BuildBuffers {
     // inputs (device)
-    const float *start, *end, *radius, *power;
+    BeamView in;
     int64_t n;
     int sqrt_mode;
     int leaf_size;
@@ -165,13 +170,10 @@ struct alignas(16) TileAxis {
 
 struct GatherArgs {
     int64_t nseg;
-    const float *o, *p, *d, *tmax;
-    const int32_t *pixel;
+    SegView seg;
     float R;
     int64_t npix;
-    float *accum;          // may be null
-    float *seg_rgb;        // may be null
-    int32_t *seg_counts;   // may be null
+    GatherOut out;         // each may be null
     const int32_t *seg_index;  // may be null: seg_rgb / seg_counts entry of gathered segment s is seg_index[s]
     const BeamRec *recs;
     const float4 *pow;
@@ -229,12 +231,10 @@ hipError_t launch_chunk_pack(const ChunkBuild &c, int64_t nchunks, const int32_t
                              int32_t *out_parent, hipStream_t s);
 struct ChunkGatherArgs {
     int64_t nseg;
-    const float *o, *p, *d, *tmax;
-    const int32_t *pixel;
+    SegView seg;
     float R;
     int64_t npix;
-    float *accum, *seg_rgb;
-    int32_t *seg_counts;
+    GatherOut out;
     const ChunkRec *chunks;
     const int32_t *chunk_parent;
     const BeamRec *parents;
@@ -250,15 +250,13 @@ hipError_t launch_gather_chunk(const ChunkGatherArgs &a, bool counters, hipStrea
 // coherence sort of a gather's segments (bre_sort.hip): 5-D Morton of (origin, direction)
 struct SegSort {
     int64_t n;
-    const float *o, *p, *d, *t;
-    const int32_t *pix;
+    SegView in;
     unsigned int *bounds;  // 6
     unsigned long long *keys, *keys_alt;
     int32_t *vals, *vals_alt;
     void *tmp;
     size_t tmp_bytes;
-    float *o2, *p2, *d2, *t2;  // sorted copies
-    int32_t *pix2;
+    SegOut out;  // sorted copies
     int key_mode;  // 0: Morton of (origin, octahedral direction); 1: Morton of (origin, end point);
                    // 2 / 3: the segment's line (dominant-axis class + slopes + plane crossing [+ midpoint]);
                    // 4: Hilbert order of (origin, end point) (the default, bre_math.h hilbert_key)
@@ -305,9 +303,17 @@ struct FilmSources {
 hipError_t launch_film_sum(const FilmSources &t, int64_t m, float *dst, int accumulate, hipStream_t st);
 
 hipError_t launch_sort_segments(const SegSort &s, hipStream_t st);
-hipError_t launch_packet_pick(int64_t n, int64_t m, int rank, int count, int chunk, const float *o, const float *p,
-                              const float *d, const float *t, const int32_t *pix, const int32_t *index, float *o2,
-                              float *p2, float *d2, float *t2, int32_t *pix2, int32_t *index2, hipStream_t st);
+// a packet shard's segments (bre_sort.hip): of n segments, the m in chunks `rank` mod `count` of `chunk`
+// consecutive packets, copied to `out`; index (may be null) / index2: the caller's index of each segment
+struct PacketPick {
+    int64_t n, m;
+    int rank, count, chunk;
+    SegView in;
+    const int32_t *index;
+    SegOut out;
+    int32_t *index2;
+};
+hipError_t launch_packet_pick(const PacketPick &k, hipStream_t st);
 
 // device self-check of the shared scalar primitives (bre_check.hip, bre_device_check)
 hipError_t launch_device_check(int kind, int64_t n, const float *x, int n_aux, const float *aux, float *y,
@@ -326,13 +332,18 @@ hipError_t slot_sort_pairs(void *tmp, const unsigned long long *k0, unsigned lon
 hipError_t slot_sort_pairs(void *tmp, const unsigned int *k0, unsigned int *k1, const int32_t *v0, int32_t *v1,
                            int64_t n, int begin_bit, int end_bit, hipStream_t s);
 
-// gather kernels (bre_gather.hip)
+// work roots and the 4-wide view (bre_roots.hip)
 size_t roots_scratch_bytes();
 hipError_t launch_roots(const Node *nodes, int S, int32_t *roots, void *scratch, hipStream_t s);
 hipError_t launch_collapse4(const Node *nodes, int64_t nnodes, Node4 *out, hipStream_t s);
 hipError_t launch_roots_shard(const int32_t *roots, int S, int rank, int count, int S2, int32_t *out,
                               hipStream_t s);
-hipError_t launch_gather(const GatherArgs &a, int kernel, bool counters, hipStream_t s);
+// kernel 2 (bre_thread.hip)
+hipError_t launch_gather_thread(const GatherArgs &a, bool counters, hipStream_t s);
+// the tile-axis pass of one tile launch (bre_tileaxis.hip)
+hipError_t launch_tile_axis(const GatherArgs &a, hipStream_t s);
+// the tile kernel and the kernels around it (bre_gather.hip)
+hipError_t launch_gather_tile(const GatherArgs &a, bool counters, hipStream_t s);
 hipError_t launch_zero_outputs(const GatherArgs &a, hipStream_t s);
 
 }  // namespace bre

@@ -1,4 +1,4 @@
-// bre_gather.hip — the beam-radiance gather on gfx950.
+// bre_gather.hip — the beam-radiance gather on gfx950: the tile kernel and the small kernels around it.
 //
 // One launch replaces the reference's per-segment loop body (photonbeam.cpp:494-508) for every
 // camera segment of an iteration: PhotonBeamBVH::Intersect (photonbeambvh.cpp:685-723) becomes a
@@ -15,9 +15,11 @@
 //                    contribute, and those run the reference's box test + ComputeClosestPoints +
 //                    kernel 64 pairs at a time with every lane busy.  Kernel 0 builds the tile tree
 //                    with BRE_OPT_TILE_LEAF beams per leaf, kernel 4 with BRE_OPT_LEAF_SIZE.
-//   2                k_gather_thread — classic thread-per-segment traversal with a per-thread LDS
-//                    stack: a structurally independent implementation kept as a cross-check.
+//   2                k_gather_thread (bre_thread.hip) — classic thread-per-segment traversal with a
+//                    per-thread LDS stack: a structurally independent implementation kept as a cross-check.
 //   5                the capsule-chunk index (bre_chunk.hip).
+// The tile kernel's work roots and 4-wide view are bre_roots.hip's, its per-gather tile axes
+// bre_tileaxis.hip's.
 // Kernels 1, 3 and 6 of round 1 (depth-first wave packets, packet-proxy traversal and its
 // hand-over mode) were slower than kernel 0 on every measured workload and are removed.
 #include <hip/hip_runtime.h>
@@ -31,8 +33,6 @@
 namespace bre {
 
 namespace {
-
-constexpr int kThreadBlock = 128;  // 2 waves, 32 KiB LDS stack
 
 // The timing ablations of rounds 2-5 (BRE_ABLATE 2-5: no exact stage, no prefilter scan, traversal
 // only, one racy accumulation round; BRE_NO_QCOUNT / BRE_NO_TAX) are not in the production source since
@@ -96,83 +96,6 @@ struct Prof {
     unsigned long long leaves = 0, beams = 0, ccp_waves = 0, rejects = 0, useful = 0, queued = 0;
 };
 
-__device__ __forceinline__ int lanes_below(unsigned long long m) {
-    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-}
-
-// ---------------------------------------------------------------------------------------------
-// Kernel 2 helpers: evaluate one beam record for one lane — reference box test, closest points,
-// kernel (photonbeam.cpp:495-507) — and write the lane's results.
-template <bool COUNT>
-__device__ __forceinline__ void eval_beam(const Lane &L, bool lane_on, const BeamV &r, const float4 *__restrict__ pw,
-                                          int64_t bi, float R, float &cr, float &cg, float &cb, int &cand,
-                                          int &contrib) {
-    // candidate: the reference's own slab test on the beam's (group) box.  For a lane whose 1/d has
-    // no infinite component, node_test(box, inv) is the same decision (bre_math.h); lanes with an
-    // axis-parallel direction (inf, possible NaN paths) take the literal statement.
-    float te;
-    bool hit = lane_on & node_test(r.box, L.o, L.invs, L.tmax, te);
-    if (L.has_inf) hit = lane_on & slab_test(r.box, L.o, L.inv, L.n0, L.n1, L.n2, L.tmax, nullptr);
-    if (COUNT) cand += hit;
-    if (!hit) return;
-    const float maxd = R + r.radius;  // MaxDistance = currentBeamRadius + beam->radius
-    float dist;
-    const bool ok = closest_distance(L.o, L.p, L.au, L.mag_a, r.b0, r.bu, r.mag_b, dist);
-    if (ok & (dist < maxd)) {
-        const float rr = dist / maxd;
-        const float w = sqrtf(1.0f - rr * rr);
-        const float4 pv = pw[bi];
-        cr += pv.x * w;
-        cg += pv.y * w;
-        cb += pv.z * w;
-        ++contrib;
-    }
-}
-
-template <bool COUNT>
-__device__ __forceinline__ void finish_lane(int64_t s, bool valid, float cr, float cg, float cb, int cand, int contrib,
-                                            unsigned long long visits, const int32_t *__restrict__ pixel, int64_t npix,
-                                            float *__restrict__ accum, float *__restrict__ seg_rgb,
-                                            int32_t *__restrict__ seg_counts, DevCounters *ctr) {
-    if (valid) {
-        if (seg_rgb) {
-            seg_rgb[3 * s] = cr;
-            seg_rgb[3 * s + 1] = cg;
-            seg_rgb[3 * s + 2] = cb;
-        }
-        if (accum) {
-            const int32_t px = pixel[s];
-            if (px < 0 || px >= npix) {
-                atomicOr(&ctr->flags, kFlagPixel);
-            } else if (cr != 0.f || cg != 0.f || cb != 0.f) {
-                atomicAdd(&accum[3 * (int64_t)px], cr);
-                atomicAdd(&accum[3 * (int64_t)px + 1], cg);
-                atomicAdd(&accum[3 * (int64_t)px + 2], cb);
-            }
-        }
-        if (seg_counts) {
-            seg_counts[2 * s] = COUNT ? cand : -1;
-            seg_counts[2 * s + 1] = contrib;
-        }
-    }
-    if (COUNT) {
-        unsigned long long c = valid ? (unsigned long long)cand : 0ull;
-        unsigned long long k = valid ? (unsigned long long)contrib : 0ull;
-        unsigned long long v = visits;
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            c += __shfl_xor(c, off);
-            k += __shfl_xor(k, off);
-            v += __shfl_xor(v, off);
-        }
-        if ((threadIdx.x & 63) == 0) {
-            atomicAdd(&ctr->candidates, c);
-            atomicAdd(&ctr->contributions, k);
-            atomicAdd(&ctr->node_visits, v);
-        }
-    }
-}
-
 // ---------------------------------------------------------------------------------------------
 // Packet bundle for the packet-level line-distance reject.  A line C (point co, unit direction cu)
 // and delta >= the distance of every valid lane's segment END POINTS from C.  The distance to a line
@@ -192,19 +115,6 @@ struct Bundle {
     f3 q;         // co x cu (the separable line reject, bundle_far_sep)
     float col1;   // |co|_1
 };
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
-    return v;
-}
-__device__ __forceinline__ float readlane_f(float v, int i) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), i)); }
-__device__ __forceinline__ float uniform_f(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
 
 // The whole packet's bundle, wave-uniform (kept in SGPRs).  All lanes must call.
 __device__ __forceinline__ Bundle make_bundle(const Lane &L, bool valid) {
@@ -347,199 +257,6 @@ __device__ __forceinline__ bool bundle_far_sep(const Bundle &K, f3 b0, f3 bu, f3
     const float b1 = fabsf(b0.x) + fabsf(b0.y) + fabsf(b0.z);
     const float thr = (maxd + K.delta) * 1.000001f + 1.93e-5f * (b1 + K.col1) + 2.5e-6f * K.omax + 2.4e-7f * mag_b + 1e-6f;
     return (u >= 0.0101f) & ((t * t) > (thr * thr) * u);
-}
-
-// ---------------------------------------------------------------------------------------------
-// Per-lane tile line reject (option 112 = 1).  A contributing pair (lane i, beam j) has the reference's
-// pA on segment i (to rounding) and pB on beam j's line with |pA - pB| < maxd_j, so pB lies in the box
-// of the launch's segments grown by maxd_j.  k_tile_axis gives every tile an axis line such that every
-// beam LINE of the tile, clipped to that box (plus a margin), lies within rho of it (distance to a line
-// is convex along a line, so the clipped piece's two end points bound it).  Then
-//   D(line_i, axis) <= d(pA, axis) <= |pA - pB| + d(pB, axis) < maxd_j + rho,
-// so a lane whose segment LINE is farther than rho + maxd_max from the axis line has no pair in the
-// tile that can contribute.  The test is the scan's own separable line-distance test
-// (scan_keep_mask) with the axis as a pseudo-beam whose threshold is rho + Ab' (Ab' with the tile's
-// largest |b0|_1 and |B|, so the scan's rounding analysis covers every beam of the tile): per leaf
-// visit one 14-VALU test per lane, before the tile is staged.  Lanes it rejects are taken off the tile
-// (fewer lanes on: more tiles take the transposed scan), and a tile no lane keeps is not staged at all.
-// Only the production instantiation tests (the counting one box-tests every beam of a visited tile for
-// C); the rejected pairs never contribute, so the queues differ only by non-contributing pairs and
-// every per-segment sum is bit-identical (tests/test_prefilter_options_gpu.py).
-__device__ __forceinline__ unsigned int ord_u(float f) {
-    const unsigned int u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float ord_f(unsigned int u) {
-    return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
-}
-
-__global__ void k_segbox_init(unsigned int *__restrict__ b) {
-    if (threadIdx.x < 6) b[threadIdx.x] = threadIdx.x < 3 ? 0xffffffffu : 0u;
-}
-
-// box of the launch's finite segment end points (6 ordered uints: min xyz, max xyz).  Grid-stride
-// over a bounded grid, reduced per wave and then per block in LDS: one set of six atomics per block
-// (per-wave atomics on the same six words serialised at the L2: 0.64 ms at C2's 0.6M segments)
-constexpr int kSegboxBlocks = 512;
-// the kernels around the gather run in one-wave workgroups (bre_slot.hip: they then fit the slots a
-// concurrent gather's retiring waves free, so the pipelined pass chain runs inside the other gather)
-constexpr int kPassBlock = 64;
-__global__ __launch_bounds__(kPassBlock) void k_segbox(int64_t nseg, const float *__restrict__ o, const float *__restrict__ p,
-                                                unsigned int *__restrict__ b) {
-    __shared__ unsigned int red[kPassBlock / 64][6];
-    unsigned int mn[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, mx[3] = {0u, 0u, 0u};
-    for (int64_t i = (int64_t)blockIdx.x * kPassBlock + threadIdx.x; i < nseg; i += (int64_t)gridDim.x * kPassBlock) {
-#pragma unroll
-        for (int e = 0; e < 2; ++e) {
-            const float *q = (e ? p : o) + 3 * i;
-            const float v[3] = {q[0], q[1], q[2]};
-            if (isfinite(v[0]) && isfinite(v[1]) && isfinite(v[2])) {
-#pragma unroll
-                for (int k = 0; k < 3; ++k) {
-                    mn[k] = min(mn[k], ord_u(v[k]));
-                    mx[k] = max(mx[k], ord_u(v[k]));
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            mn[k] = min(mn[k], (unsigned int)__shfl_xor((int)mn[k], off));
-            mx[k] = max(mx[k], (unsigned int)__shfl_xor((int)mx[k], off));
-        }
-    }
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            red[w][k] = mn[k];
-            red[w][3 + k] = mx[k];
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x < 6) {
-        const int k = threadIdx.x;
-        unsigned int v = red[0][k];
-        for (int j = 1; j < kPassBlock / 64; ++j) v = k < 3 ? min(v, red[j][k]) : max(v, red[j][k]);
-        if (k < 3)
-            atomicMin(&b[k], v);
-        else
-            atomicMax(&b[k], v);
-    }
-}
-
-// One wave per leaf tile: axis = mean start -> mean end of its usable beams, rho = the largest
-// distance of a clipped beam line's end points from the axis (with rounding margins), stored as the
-// pseudo-beam record the per-lane tile line reject tests (TileAxis).
-__global__ __launch_bounds__(64) void k_tile_axis(const BeamRec *__restrict__ recs, BeamSet bset, int64_t nvalid,
-                                                  int leaf_size,
-                                                  const unsigned int *__restrict__ segb, float R,
-                                                  TileAxis *__restrict__ out) {
-    const int64_t tile = blockIdx.x;
-    const int lane = threadIdx.x;
-    const int64_t j = tile * leaf_size + lane;
-    bool ok = lane < leaf_size && j < nvalid;
-    f3 b0 = mk(0.f, 0.f, 0.f), bu = mk(0.f, 0.f, 0.f);
-    float mb = 0.f, rad = 0.f;
-    if (ok) {
-        const BeamV r = load_beam(recs, j, bset);
-        b0 = r.b0;
-        bu = r.bu;
-        mb = r.mag_b;
-        rad = r.radius;
-        // a zero-length or non-finite beam has a NaN / infinite reference box: never a candidate
-        ok = mb > 0.f && isfinite(mb) && isfinite(b0.x) && isfinite(b0.y) && isfinite(b0.z) && isfinite(bu.x) &&
-             isfinite(bu.y) && isfinite(bu.z) && isfinite(rad);
-    }
-    const float rmax = wave_max(ok ? rad : 0.f);
-    const float n = wave_sum(ok ? 1.f : 0.f);
-    TileAxis A;
-    if (n == 0.f || !(segb[0] <= segb[3] && segb[1] <= segb[4] && segb[2] <= segb[5])) {
-        // no usable beam (or no finite segment): nothing of this tile can contribute
-        A.d[0] = 1.f;
-        A.d[1] = A.d[2] = 0.f;
-        A.thr = 0.f;
-        A.m[0] = A.m[1] = A.m[2] = 0.f;
-        A.grow = -1.f;
-        if (lane == 0) out[tile] = A;
-        return;
-    }
-    const f3 e = add3(b0, scale3(bu, mb));
-    // the axis through the centres of the starts' and the ends' boxes (round 5: C2 +1.2% over the
-    // mean start -> mean end, profiles/r5/run3)
-    const auto ctr = [&](float v) {
-        const float hi = wave_max(ok ? v : -FLT_MAX), lo = -wave_max(ok ? -v : -FLT_MAX);
-        return 0.5f * lo + 0.5f * hi;
-    };
-    const f3 ps = mk(ctr(b0.x), ctr(b0.y), ctr(b0.z));
-    const f3 pe = mk(ctr(e.x), ctr(e.y), ctr(e.z));
-    f3 d = sub3(pe, ps);
-    const float dl = sqrtf(lensq3(d));
-    d = (dl > 1e-6f * (1.f + fabsf(ps.x) + fabsf(ps.y) + fabsf(ps.z)) && isfinite(dl)) ? scale3(d, 1.f / dl)
-                                                                                      : mk(1.f, 0.f, 0.f);
-    // the region: segment box grown by maxd_max = R + rmax, plus margins
-    const float lo[3] = {ord_f(segb[0]), ord_f(segb[1]), ord_f(segb[2])};
-    const float hi[3] = {ord_f(segb[3]), ord_f(segb[4]), ord_f(segb[5])};
-    const float cm = fmaxf(fmaxf(fmaxf(fabsf(lo[0]), fabsf(lo[1])), fmaxf(fabsf(lo[2]), fabsf(hi[0]))),
-                           fmaxf(fabsf(hi[1]), fabsf(hi[2])));
-    const float grow = (R + rmax) * 1.001f + 1e-5f * cm + 1e-6f;
-    float dist = 0.f;
-    if (ok) {
-        const float o3[3] = {b0.x, b0.y, b0.z}, u3[3] = {bu.x, bu.y, bu.z};
-        float t0 = -FLT_MAX, t1 = FLT_MAX;
-        bool in = true;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const float l = lo[k] - grow, h = hi[k] + grow;
-            if (u3[k] == 0.f) {
-                in = in && o3[k] >= l && o3[k] <= h;
-            } else {
-                float a = (l - o3[k]) / u3[k], c = (h - o3[k]) / u3[k];
-                if (a > c) {
-                    const float x = a;
-                    a = c;
-                    c = x;
-                }
-                t0 = fmaxf(t0, a);
-                t1 = fminf(t1, c);
-            }
-        }
-        if (in && t0 <= t1) {
-            // widen the piece by a little (the slab parameters carry rounding)
-            const float tw = 1e-5f * (fabsf(t0) + fabsf(t1)) + 1e-6f;
-            t0 -= tw;
-            t1 += tw;
-            const auto dax = [&](float t) {
-                const f3 q = sub3(add3(b0, scale3(bu, t)), ps);
-                const f3 c = mk(q.y * d.z - q.z * d.y, q.z * d.x - q.x * d.z, q.x * d.y - q.y * d.x);
-                return sqrtf(lensq3(c));
-            };
-            dist = fmaxf(dax(t0), dax(t1));
-            // a NaN distance must not shrink rho: treat it as unbounded
-            if (!(dist == dist)) dist = FLT_MAX;
-        }
-    }
-    const float rho_raw = wave_max(dist);
-    const float pm = fmaxf(fmaxf(fabsf(ps.x), fabsf(ps.y)), fabsf(ps.z));
-    const float rho = rho_raw * 1.0001f + 1e-5f * (cm + pm + grow) + 1e-6f;
-    // the scan's beam-side margin Ab' (make_scan_beam) with maxd_max and the tile's largest |b0|_1 and
-    // |B| (the separable form evaluates t.n at the axis point: its |p|_1 joins the max)
-    const float b1 = wave_max(ok ? fabsf(b0.x) + fabsf(b0.y) + fabsf(b0.z) : 0.f);
-    const float p1 = fabsf(ps.x) + fabsf(ps.y) + fabsf(ps.z);
-    const float bmag = wave_max(ok ? mb : 0.f);
-    const float ab = (R + rmax) * 1.000001f + 1.93e-5f * fmaxf(b1, p1) + 2.4e-7f * bmag + 1e-6f;
-    const float thr = (rho + ab) * 1.0001f + 1e-6f;
-    A.d[0] = d.x;
-    A.d[1] = d.y;
-    A.d[2] = d.z;
-    A.thr = (rho_raw < FLT_MAX && isfinite(thr)) ? thr : FLT_MAX;  // FLT_MAX: never a reject
-    A.m[0] = d.y * ps.z - d.z * ps.y;  // m = d x p (the scan's m0 = bu x b0)
-    A.m[1] = d.z * ps.x - d.x * ps.z;
-    A.m[2] = d.x * ps.y - d.y * ps.x;
-    A.grow = grow;
-    if (lane == 0) out[tile] = A;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1314,241 +1031,6 @@ __global__ __launch_bounds__(kPassBlock) void k_reduce(int64_t nseg, const float
     }
 }
 
-// Work roots: the BVH frontier at depth log2(S) (leaves above it stay in the frontier), ordered by the
-// number of leaf tiles below each root, largest first (stable): with block map 3 every packet's
-// waves on the largest subtrees are dispatched first and the kernel's tail is made of small ones.
-// The leaves below a Karras node are a contiguous range (bre_build.hip), found by its leftmost and
-// rightmost descents.  The partial sums are added in this root order (k_reduce): deterministic.
-//
-// Starting from the root, the frontier's LARGEST internal node (leaf tiles below it, Node::nleaf; ties:
-// the lowest frontier position) is replaced by its children (the first in its place, the second
-// appended) while the frontier stays within S entries, so the S work roots are as equal in size as
-// the tree allows: the longest (packet, subtree) waves, which end the launch, are as short as they can
-// be (a breadth-first frontier left subtrees of very unequal size, and an emulated 1/8 rank's
-// iteration-0 gather 37% above 1/8 of N = 1's).  Then the roots are ordered largest first (ties in
-// frontier order) for the LPT block map.
-//
-// The greedy loop is serial (up to S - 1 expansions: 0.39 ms at C2 as a block-wide reduction per
-// expansion), but its result is not: every expanded node has more leaf tiles than its children, so
-// the expansions come in decreasing order of size and the expanded set E is the S - 1 largest
-// interior nodes (fewer when the tree has fewer), a subtree from the root; the roots are E's children
-// outside E.  So, with all threads:
-//   1. cache, breadth first, every interior node with at least total / S leaf tiles (the frontier
-//      partitions the total over <= S entries, so its largest entry, the only one ever expanded, has
-//      at least total / S): its leaf tiles, children, their leaf tiles and cache slots;
-//   2. E = the S - 1 cached nodes of largest (leaf tiles, -index), each ranked against all others;
-//   3. the roots: E's children outside E (the whole tree's root when S = 1);
-//   4. ranks: leaf tiles descending, ties by child index.
-// Ties of equal size are broken by node index instead of the frontier position the serial form used
-// (any frontier is a valid split; this one is deterministic).  A cache overflow (never seen: C2 caches
-// ~600 of 4096 slots at S = 256) still yields a valid split: the cached nodes form a subtree from the
-// root, so E's top-(S - 1) choice among them is one too.
-constexpr int kRootSlots = 4096;
-// the cache, in global scratch (one wave computes the roots: a one-wave workgroup with no LDS fits a
-// concurrent gather's slots, bre_slot.hip; round 5's version kept it in 140 KB of LDS, a whole CU)
-struct RootsScratch {
-    int32_t id[kRootSlots];     // cached node
-    int32_t nl[kRootSlots];     // its leaf tiles (Node::nleaf)
-    int32_t ch[kRootSlots][2];  // its children
-    int32_t cw[kRootSlots][2];  // their leaf tiles (1: a leaf tile, 0: empty)
-    int32_t cs[kRootSlots][2];  // their cache slots (-1: not cached)
-    int32_t in_e[kRootSlots];
-    int32_t fc[kMaxSplit + 1], fw[kMaxSplit + 1];  // the roots, unordered
-};
-
-// children, parent and leaf tiles of node x: the record's last 16 bytes
-__device__ __forceinline__ int4 node_tail(const Node *__restrict__ nodes, int32_t x) {
-    return *reinterpret_cast<const int4 *>(&nodes[x].child[0]);
-}
-
-// the wave's own global writes visible to its later reads (device-scope release + acquire)
-__device__ __forceinline__ void wave_sync_global() {
-    __threadfence();
-    __builtin_amdgcn_wave_barrier();
-}
-
-// key of a node or root of w leaf tiles and index x: larger first, ties by ascending (signed) index
-__device__ __forceinline__ unsigned long long root_key(int32_t w, int32_t x) {
-    return ((unsigned long long)(unsigned int)w << 32) | (0xffffffffu - ((unsigned int)x ^ 0x80000000u));
-}
-
-// rank of key kk among the n keys key(w[j], x[j]) (the number of larger ones): 64 keys per step, read by
-// one lane each and broadcast by readlane
-__device__ __forceinline__ int rank_among(const int32_t *w, const int32_t *x, int n, unsigned long long kk) {
-    int rank = 0;
-    for (int j0 = 0; j0 < n; j0 += 64) {
-        const int j = j0 + (int)threadIdx.x;
-        const unsigned long long kv = j < n ? root_key(w[j], x[j]) : 0ull;
-        const int m = min(64, n - j0);
-        for (int q = 0; q < m; ++q) {
-            const unsigned long long kj =
-                ((unsigned long long)(unsigned int)__builtin_amdgcn_readlane((int)(kv >> 32), q) << 32) |
-                (unsigned int)__builtin_amdgcn_readlane((int)(unsigned int)kv, q);
-            rank += kj > kk;
-        }
-    }
-    return rank;
-}
-
-__global__ __launch_bounds__(64) void k_roots(const Node *__restrict__ nodes, int S, int32_t *__restrict__ roots,
-                                              RootsScratch *__restrict__ g) {
-    const int t = threadIdx.x;
-    const unsigned long long below = (1ull << t) - 1ull;
-    const int32_t total = nodes[0].nleaf;
-    const int32_t heavy = total / S;
-    if (t == 0) g->id[0] = 0;
-    wave_sync_global();
-    // 1. breadth-first cache of the heavy interior nodes (slots handed out in lane order per child)
-    int cnt = 1, lo = 0, hi = 1;
-    while (lo < hi) {
-        for (int k0 = lo; k0 < hi; k0 += 64) {
-            const int k = k0 + t;
-            const bool act = k < hi;
-            const int4 q = act ? node_tail(nodes, g->id[k]) : make_int4(kEmptyChild, kEmptyChild, 0, 0);
-            const int32_t c[2] = {q.x, q.y};
-            int32_t w[2];
-            bool h[2];
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                w[j] = c[j] == kEmptyChild ? 0 : (c[j] < 0 ? 1 : node_tail(nodes, c[j]).w);
-                h[j] = act && c[j] >= 0 && w[j] >= heavy;
-            }
-            int32_t sl[2];
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const unsigned long long m = __ballot(h[j]);
-                const int s = cnt + __popcll(m & below);
-                sl[j] = (h[j] && s < kRootSlots) ? s : -1;
-                if (sl[j] >= 0) g->id[s] = c[j];
-                cnt += __popcll(m);
-            }
-            if (act) {
-                g->nl[k] = q.w;
-#pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    g->ch[k][j] = c[j];
-                    g->cw[k][j] = w[j];
-                    g->cs[k][j] = sl[j];
-                }
-            }
-        }
-        wave_sync_global();
-        lo = hi;
-        hi = min(cnt, kRootSlots);
-    }
-    const int nc = min(cnt, kRootSlots);
-    // 2. E: the S - 1 largest cached nodes
-    for (int k0 = 0; k0 < nc; k0 += 64) {
-        const int k = k0 + t;
-        const unsigned long long kk = k < nc ? root_key(g->nl[k], g->id[k]) : ~0ull;
-        const int rank = rank_among(g->nl, g->id, nc, kk);
-        if (k < nc) g->in_e[k] = rank < S - 1;
-    }
-    wave_sync_global();
-    // 3. the roots: E's children outside E (the whole tree's root when S = 1)
-    int nf = 0;
-    for (int k0 = 0; k0 < nc; k0 += 64) {
-        const int k = k0 + t;
-        const bool e = k < nc && g->in_e[k];
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            int32_t c = kEmptyChild, s = -1;
-            if (e) {
-                c = g->ch[k][j];
-                s = g->cs[k][j];
-            }
-            const bool root = e && c != kEmptyChild && !(s >= 0 && g->in_e[s]);
-            const unsigned long long m = __ballot(root);
-            if (root) {
-                const int f = nf + __popcll(m & below);
-                g->fc[f] = c;
-                g->fw[f] = g->cw[k][j];
-            }
-            nf += __popcll(m);
-        }
-    }
-    if (!g->in_e[0]) {
-        if (t == 0) {
-            g->fc[0] = 0;
-            g->fw[0] = total;
-        }
-        nf = 1;
-    }
-    wave_sync_global();
-    // 4. ranks: leaf tiles descending, ties by child index
-    for (int k0 = 0; k0 < nf; k0 += 64) {
-        const int k = k0 + t;
-        const unsigned long long kk = k < nf ? root_key(g->fw[k], g->fc[k]) : ~0ull;
-        const int rank = rank_among(g->fw, g->fc, nf, kk);
-        if (k < nf) roots[rank] = g->fc[k];
-    }
-    for (int k = nf + t; k < S; k += 64) roots[k] = kEmptyChild;
-    if (t == 0) roots[S] = nf;
-}
-
-template <bool COUNT>
-__global__ __launch_bounds__(kThreadBlock) void k_gather_thread(
-    int64_t nseg, const float *__restrict__ so, const float *__restrict__ sp_, const float *__restrict__ sd,
-    const float *__restrict__ stmax, const int32_t *__restrict__ pixel, float R, int64_t npix,
-    float *__restrict__ accum, float *__restrict__ seg_rgb, int32_t *__restrict__ seg_counts,
-    const BeamRec *__restrict__ recs, const float4 *__restrict__ pw, BeamSet bset, const Node *__restrict__ nodes,
-    int64_t nvalid, int leaf_size, DevCounters *ctr, int stack_cap) {
-    __shared__ int32_t stk[kThreadStackDepth][kThreadBlock];
-    const int tid = threadIdx.x;
-    const int64_t s = (int64_t)blockIdx.x * kThreadBlock + tid;
-    Lane L;
-    const bool valid = load_lane(s, nseg, so, sp_, sd, stmax, L);
-    float cr = 0.f, cg = 0.f, cb = 0.f;
-    int cand = 0, contrib = 0;
-    unsigned long long visits = 0;
-    if (valid && nvalid > 0) {
-        int node = 0;
-        int sp = 0;
-        const int cap = stack_cap < kThreadStackDepth ? stack_cap : kThreadStackDepth;
-        while (true) {
-            const NodeV n = load_node(nodes, node);
-            if (COUNT) ++visits;
-            const int32_t c0 = n.c0, c1 = n.c1;
-            float te0 = 0.f, te1 = 0.f;
-            bool h0 = (c0 != kEmptyChild) & node_test(n.b0, L.o, L.invs, L.tmax, te0);
-            bool h1 = (c1 != kEmptyChild) & node_test(n.b1, L.o, L.invs, L.tmax, te1);
-            if (h0 && c0 < 0) {
-                const int64_t first = (int64_t)(~c0) * leaf_size;
-                const int cnt = (int)min((int64_t)leaf_size, nvalid - first);
-                for (int j = 0; j < cnt; ++j)
-                    eval_beam<COUNT>(L, true, load_beam(recs, first + j, bset), pw, first + j, R, cr, cg, cb, cand, contrib);
-                h0 = false;
-            }
-            if (h1 && c1 < 0) {
-                const int64_t first = (int64_t)(~c1) * leaf_size;
-                const int cnt = (int)min((int64_t)leaf_size, nvalid - first);
-                for (int j = 0; j < cnt; ++j)
-                    eval_beam<COUNT>(L, true, load_beam(recs, first + j, bset), pw, first + j, R, cr, cg, cb, cand, contrib);
-                h1 = false;
-            }
-            if (h0 && h1) {
-                const bool first0 = !(te1 < te0);
-                if (sp >= cap) {
-                    atomicOr(&ctr->flags, kFlagStack);
-                    break;
-                }
-                stk[sp][tid] = first0 ? c1 : c0;
-                ++sp;
-                node = first0 ? c0 : c1;
-            } else if (h0) {
-                node = c0;
-            } else if (h1) {
-                node = c1;
-            } else {
-                if (sp == 0) break;
-                --sp;
-                node = stk[sp][tid];
-            }
-        }
-    }
-    finish_lane<COUNT>(s, valid, cr, cg, cb, cand, contrib, visits, pixel, npix, accum, seg_rgb, seg_counts, ctr);
-}
-
 __global__ void k_zero_seg(int64_t nseg, float *__restrict__ seg_rgb, int32_t *__restrict__ seg_counts,
                            const int32_t *__restrict__ seg_index) {
     const int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x;
@@ -1567,117 +1049,29 @@ __global__ void k_zero_seg(int64_t nseg, float *__restrict__ seg_rgb, int32_t *_
 
 }  // namespace
 
-// The 4-wide view (Node4): one thread per binary node.  Slot order is the binary order (child 0's
-// children, then child 1's), so a fixed-order walk of the 4-wide view visits the leaves in the same
-// left-to-right order as a fixed-order binary walk.  A grandchild box lies inside its parent's box, so
-// testing it directly prunes at least as tightly as testing both levels.
-__global__ __launch_bounds__(64) void k_collapse4(const Node *__restrict__ nodes, int64_t nnodes,
-                                                   Node4 *__restrict__ out) {
-    const int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x;
-    if (i >= nnodes) return;
-    const Node &n = nodes[i];
-    Node4 q;
-    int k = 0;
-    const auto put = [&](int32_t c, const float *lo, const float *hi) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            q.lo[a][k] = lo[a];
-            q.hi[a][k] = hi[a];
-        }
-        q.child[k] = c;
-        ++k;
-    };
-    for (int c = 0; c < 2; ++c) {
-        const int32_t ch = n.child[c];
-        if (ch == kEmptyChild) continue;
-        if (ch >= 0) {
-            const Node &m = nodes[ch];
-            for (int d = 0; d < 2; ++d)
-                if (m.child[d] != kEmptyChild) put(m.child[d], m.lo[d], m.hi[d]);
-        } else {
-            put(ch, n.lo[c], n.hi[c]);
-        }
-    }
-    for (; k < 4; ++k) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) q.lo[a][k] = q.hi[a][k] = 0.f;
-        q.child[k] = kEmptyChild;
-    }
-    q.pad[0] = q.pad[1] = q.pad[2] = q.pad[3] = 0;
-    out[i] = q;
-}
-
-hipError_t launch_collapse4(const Node *nodes, int64_t nnodes, Node4 *out, hipStream_t s) {
-    if (nnodes <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_collapse4, dim3((unsigned int)((nnodes + 63) / 64)), dim3(64), 0, s, nodes, nnodes, out);
-    return hipGetLastError();
-}
-
-// A work-root shard's list: the roots rank, rank + count, ... of the size-ordered list (so every shard
-// gets large and small subtrees), S2 entries padded with kEmptyChild, their number in out[S2].
-__global__ void k_roots_shard(const int32_t *__restrict__ roots, int S, int rank, int count, int S2,
-                              int32_t *__restrict__ out) {
-    const int n = roots[S];
-    const int n2 = n > rank ? (n - rank + count - 1) / count : 0;
-    for (int k = threadIdx.x; k < S2; k += blockDim.x) out[k] = k < n2 ? roots[rank + k * count] : kEmptyChild;
-    if (threadIdx.x == 0) out[S2] = n2;
-}
-
-hipError_t launch_roots_shard(const int32_t *roots, int S, int rank, int count, int S2, int32_t *out,
-                              hipStream_t s) {
-    hipLaunchKernelGGL(k_roots_shard, dim3(1), dim3(64), 0, s, roots, S, rank, count, S2, out);
-    return hipGetLastError();
-}
-
-size_t roots_scratch_bytes() { return sizeof(RootsScratch); }
-
-hipError_t launch_roots(const Node *nodes, int S, int32_t *roots, void *scratch, hipStream_t s) {
-    hipLaunchKernelGGL(k_roots, dim3(1), dim3(64), 0, s, nodes, S, roots, static_cast<RootsScratch *>(scratch));
-    return hipGetLastError();
-}
-
-hipError_t launch_gather(const GatherArgs &a, int kernel, bool counters, hipStream_t s) {
+// The tile gather of one launch's segments: k_seg_prep, the tile-axis pass (bre_tileaxis.hip), the tile
+// kernel between the caller's events, then k_reduce.
+hipError_t launch_gather_tile(const GatherArgs &a, bool counters, hipStream_t s) {
     if (a.nseg == 0) return hipSuccess;
     const int stack_cap = a.stack_cap > 0 ? a.stack_cap : kStackDepth;
     if (stack_cap > kStackDepth) return hipErrorInvalidValue;
-    if (kernel == 2) {
-        const dim3 grid((unsigned int)((a.nseg + kThreadBlock - 1) / kThreadBlock));
-        int32_t *cnt = a.seg_index ? nullptr : a.seg_counts;
-        float *rgb = a.seg_index ? nullptr : a.seg_rgb;
-        if (a.seg_index && (a.seg_rgb || a.seg_counts)) return hipErrorInvalidValue;  // kernel 2 writes in place
-        if (counters)
-            hipLaunchKernelGGL(k_gather_thread<true>, grid, dim3(kThreadBlock), 0, s, a.nseg, a.o, a.p, a.d, a.tmax,
-                               a.pixel, a.R, a.npix, a.accum, rgb, cnt, a.recs, a.pow, a.bset, a.nodes, a.nvalid,
-                               a.leaf_size, a.ctr, stack_cap);
-        else
-            hipLaunchKernelGGL(k_gather_thread<false>, grid, dim3(kThreadBlock), 0, s, a.nseg, a.o, a.p, a.d, a.tmax,
-                               a.pixel, a.R, a.npix, a.accum, rgb, cnt, a.recs, a.pow, a.bset, a.nodes, a.nvalid,
-                               a.leaf_size, a.ctr, stack_cap);
-        return hipGetLastError();
-    }
-    if (kernel != 4) return hipErrorInvalidValue;
     // per-subtree counts: candidates + contributions with counters, contributions alone otherwise
-    int32_t *pcnt = (counters || a.seg_counts) ? a.pcnt : nullptr;
-    if ((counters || a.seg_counts) && !pcnt) return hipErrorInvalidValue;
+    int32_t *pcnt = (counters || a.out.seg_counts) ? a.pcnt : nullptr;
+    if ((counters || a.out.seg_counts) && !pcnt) return hipErrorInvalidValue;
     if (!a.segrec || a.leaf_size > 64) return hipErrorInvalidValue;
     if (!a.nodes4) return hipErrorInvalidValue;  // the 4-wide walk needs the collapsed view
-    hipLaunchKernelGGL(k_seg_prep, dim3((unsigned int)((a.nseg + kPassBlock - 1) / kPassBlock)), dim3(kPassBlock), 0, s, a.nseg, a.o, a.p, a.d,
-                       a.tmax, a.segrec);
+    hipLaunchKernelGGL(k_seg_prep, dim3((unsigned int)((a.nseg + kPassBlock - 1) / kPassBlock)), dim3(kPassBlock), 0, s, a.nseg, a.seg.o, a.seg.p, a.seg.d,
+                       a.seg.t, a.segrec);
     const TileAxis *tax = nullptr;
     if (a.tileax && a.segbox && a.prefilter && a.nvalid > 0) {
-        const int64_t ntiles = (a.nvalid + a.leaf_size - 1) / a.leaf_size;
-        hipLaunchKernelGGL(k_segbox_init, dim3(1), dim3(64), 0, s, a.segbox);
-        hipLaunchKernelGGL(k_segbox, dim3((unsigned int)std::min<int64_t>(kSegboxBlocks, (a.nseg + kPassBlock - 1) / kPassBlock)), dim3(kPassBlock), 0, s, a.nseg, a.o, a.p,
-                           a.segbox);
-        hipLaunchKernelGGL(k_tile_axis, dim3((unsigned int)ntiles), dim3(64), 0, s, a.recs, a.bset, a.nvalid,
-                           a.leaf_size, a.segbox, a.R, a.tileax);
+        const hipError_t ea = launch_tile_axis(a, s);
+        if (ea != hipSuccess) return ea;
         tax = a.tileax;
     }
     const dim3 grid4((unsigned int)(((a.nseg + kTileBlock - 1) / kTileBlock) * a.split));
     // block map 0 deals S / 8 roots to each XCD: a split that is not a multiple of 8 (work-root shards:
     // ceil(S / count)) would leave roots unassigned, so such launches take the LPT map
-    GatherArgs am = a;
-    if (am.block_map == 0 && (am.split & 7) != 0) am.block_map = 3;
+    const int block_map = (a.block_map == 0 && (a.split & 7) != 0) ? 3 : a.block_map;
     if (a.wait_ev) {  // another context's tile kernel first (bre_set_gather_after)
         const hipError_t ew = hipStreamWaitEvent(s, a.wait_ev, 0);
         if (ew != hipSuccess) return ew;
@@ -1687,10 +1081,10 @@ hipError_t launch_gather(const GatherArgs &a, int kernel, bool counters, hipStre
         if (es != hipSuccess) return es;
     }
 #define BRE_LAUNCH_TILE(C, W)                                                                                    \
-    hipLaunchKernelGGL((k_gather_tile<C, W>), grid4, dim3(kTileBlock), 0, s, a.nseg, a.o, a.p, a.d, a.tmax,      \
-                       a.segrec, a.R, a.partial, pcnt, a.recs, a.pow, a.bset, a.nodes, a.nodes4, a.nvalid,        \
-                       a.leaf_size,                                                                        \
-                       a.roots, a.split, a.ctr, stack_cap, (int)a.prefilter, am.block_map, a.tscan, a.margin, tax)
+    hipLaunchKernelGGL((k_gather_tile<C, W>), grid4, dim3(kTileBlock), 0, s, a.nseg, a.seg.o, a.seg.p, a.seg.d,  \
+                       a.seg.t, a.segrec, a.R, a.partial, pcnt, a.recs, a.pow, a.bset, a.nodes, a.nodes4,        \
+                       a.nvalid, a.leaf_size, a.roots, a.split, a.ctr, stack_cap, (int)a.prefilter, block_map,   \
+                       a.tscan, a.margin, tax)
     if (counters) {
         BRE_LAUNCH_TILE(true, 1);
     } else if (a.occupancy == 1) {
@@ -1718,14 +1112,14 @@ hipError_t launch_gather(const GatherArgs &a, int kernel, bool counters, hipStre
         if (e4 != hipSuccess) return e4;
     }
     hipLaunchKernelGGL(k_reduce, dim3((unsigned int)((a.nseg + kPassBlock - 1) / kPassBlock)), dim3(kPassBlock), 0, s, a.nseg, a.partial, pcnt,
-                       a.roots, a.split, a.pixel, a.npix, a.accum, a.seg_rgb, a.seg_counts, a.seg_index, a.ctr);
+                       a.roots, a.split, a.seg.pix, a.npix, a.out.accum, a.out.seg_rgb, a.out.seg_counts, a.seg_index, a.ctr);
     return hipGetLastError();
 }
 
 hipError_t launch_zero_outputs(const GatherArgs &a, hipStream_t s) {
-    if (a.nseg == 0 || (!a.seg_rgb && !a.seg_counts)) return hipSuccess;
-    hipLaunchKernelGGL(k_zero_seg, dim3((unsigned int)((a.nseg + 63) / 64)), dim3(64), 0, s, a.nseg, a.seg_rgb,
-                       a.seg_counts, a.seg_index);
+    if (a.nseg == 0 || (!a.out.seg_rgb && !a.out.seg_counts)) return hipSuccess;
+    hipLaunchKernelGGL(k_zero_seg, dim3((unsigned int)((a.nseg + 63) / 64)), dim3(64), 0, s, a.nseg, a.out.seg_rgb,
+                       a.out.seg_counts, a.seg_index);
     return hipGetLastError();
 }
 

@@ -1,6 +1,7 @@
-// bre_lane.h — per-lane segment state and the record loads / conservative tests shared by the
-// gather kernels (bre_gather.hip: reference candidate enumeration; bre_chunk.hip: capsule-chunk
-// index).  Device code only; compiled with -ffp-contract=off (csrc/Makefile).
+// bre_lane.h — per-lane segment state, the record loads / conservative tests and the small wave
+// helpers shared by the gather kernels (bre_gather.hip, bre_thread.hip, bre_tileaxis.hip: reference
+// candidate enumeration; bre_chunk.hip: capsule-chunk index).  Device code only; compiled with
+// -ffp-contract=off (csrc/Makefile).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -12,6 +13,31 @@
 
 namespace bre {
 namespace {
+
+// A float as an unsigned int of the same order (for integer atomic min / max), and back
+__device__ __forceinline__ unsigned int f2ord(float f) {
+    unsigned int u = __float_as_uint(f);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float ord2f(unsigned int u) {
+    return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
+}
+
+__device__ __forceinline__ int lanes_below(unsigned long long m) {
+    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+}
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
+    return v;
+}
+__device__ __forceinline__ float readlane_f(float v, int i) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), i)); }
+__device__ __forceinline__ float uniform_f(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
 
 // Whole-record loads (4 x 16 B).  With a wave-uniform index these become SMEM loads into SGPRs.
 struct NodeV {

@@ -423,28 +423,27 @@ inline unsigned grid_of(int64_t n) { return (unsigned)((n + kPhotonBlock - 1) / 
 }  // namespace
 
 hipError_t launch_photons(const DevScene *scene, int stack_depth, int64_t n, uint64_t seq0, int max_depth,
-                          float radius, int32_t *counts, const int64_t *offsets, float *start, float *end,
-                          float *rad, float *power, int mode, int over, hipStream_t s) {
+                          float radius, int32_t *counts, const int64_t *offsets, const BeamOut &out, int mode,
+                          int over, hipStream_t s) {
     if (n == 0) return hipSuccess;
     const size_t lds = scene_stack_bytes(stack_depth, kPhotonBlock);
     if (mode == 1)
         hipLaunchKernelGGL(k_photons<1>, dim3(grid_of(n)), dim3(kPhotonBlock), lds, s, scene, n, seq0, max_depth,
-                           radius, counts, offsets, start, end, rad, power, over);
+                           radius, counts, offsets, out.start, out.end, out.radius, out.power, over);
     else if (mode == 2)
         hipLaunchKernelGGL(k_photons<2>, dim3(grid_of(n)), dim3(kPhotonBlock), lds, s, scene, n, seq0, max_depth,
-                           radius, counts, offsets, start, end, rad, power, over);
+                           radius, counts, offsets, out.start, out.end, out.radius, out.power, over);
     else
         hipLaunchKernelGGL(k_photons<0>, dim3(grid_of(n)), dim3(kPhotonBlock), lds, s, scene, n, seq0, max_depth,
-                           radius, counts, offsets, start, end, rad, power, 0);
+                           radius, counts, offsets, out.start, out.end, out.radius, out.power, 0);
     return hipGetLastError();
 }
 
-hipError_t launch_photon_slots(int64_t n, int cap, const int32_t *counts, const int64_t *offsets, const float *ss,
-                               const float *se, const float *sr, const float *sp, float *start, float *end,
-                               float *rad, float *power, hipStream_t s) {
+hipError_t launch_photon_slots(int64_t n, int cap, const int32_t *counts, const int64_t *offsets,
+                               const BeamView &slots, const BeamOut &out, hipStream_t s) {
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(k_photon_slots, dim3((unsigned int)((n + kSlotsBlock - 1) / kSlotsBlock)), dim3(kSlotsBlock), 0, s, n, cap, counts, offsets,
-                       ss, se, sr, sp, start, end, rad, power);
+                       slots.start, slots.end, slots.radius, slots.power, out.start, out.end, out.radius, out.power);
     return hipGetLastError();
 }
 

@@ -19,6 +19,7 @@
 #include <float.h>
 
 #include "bre_device.h"
+#include "bre_lane.h"
 #include "bre_math.h"
 
 namespace bre {
@@ -29,14 +30,6 @@ namespace {
 #define BRE_PASS_BLOCK 64  // one wave (bre_slot.hip; 256 until round 5)
 #endif
 constexpr int kBlock = BRE_PASS_BLOCK;  // threads per block of the pass kernels
-
-__device__ __forceinline__ unsigned int f2ord(float f) {
-    unsigned int u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float ord2f(unsigned int u) {
-    return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
-}
 
 __global__ void k_sort_init(unsigned int *b) {
     if (threadIdx.x < 6) b[threadIdx.x] = threadIdx.x < 3 ? 0xffffffffu : 0u;
@@ -440,12 +433,10 @@ hipError_t launch_resolve_classes(int64_t m, int classes, const float *in, float
     return hipGetLastError();
 }
 
-hipError_t launch_packet_pick(int64_t n, int64_t m, int rank, int count, int chunk, const float *o, const float *p,
-                              const float *d, const float *t, const int32_t *pix, const int32_t *index, float *o2,
-                              float *p2, float *d2, float *t2, int32_t *pix2, int32_t *index2, hipStream_t st) {
-    if (m <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_packet_pick, dim3(grid_of(m)), dim3(kBlock), 0, st, n, m, rank, count, chunk, o, p, d, t, pix, index,
-                       o2, p2, d2, t2, pix2, index2);
+hipError_t launch_packet_pick(const PacketPick &k, hipStream_t st) {
+    if (k.m <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_packet_pick, dim3(grid_of(k.m)), dim3(kBlock), 0, st, k.n, k.m, k.rank, k.count, k.chunk, k.in.o,
+                       k.in.p, k.in.d, k.in.t, k.in.pix, k.index, k.out.o, k.out.p, k.out.d, k.out.t, k.out.pix, k.index2);
     return hipGetLastError();
 }
 
@@ -461,20 +452,20 @@ hipError_t launch_sort_segments(const SegSort &s, hipStream_t st) {
     hipLaunchKernelGGL(k_sort_init, dim3(1), dim3(64), 0, st, s.bounds);
     // grid-stride bounds over at most 256 blocks (one set of six same-address atomics per block)
     const unsigned bgrid = grid_of(s.n) < 256u ? grid_of(s.n) : 256u;
-    hipLaunchKernelGGL(k_origin_bounds, dim3(bgrid), dim3(kBlock), 0, st, s.n, s.o, s.bounds);
+    hipLaunchKernelGGL(k_origin_bounds, dim3(bgrid), dim3(kBlock), 0, st, s.n, s.in.o, s.bounds);
     int key_bits = 50;
     if (s.key_mode == 1 || s.key_mode == 4) {
-        hipLaunchKernelGGL(k_origin_bounds, dim3(bgrid), dim3(kBlock), 0, st, s.n, s.p, s.bounds);
-        hipLaunchKernelGGL(k_seg_keys_op, dim3(grid_of(s.n)), dim3(kBlock), 0, st, s.n, s.o, s.p, s.bounds,
+        hipLaunchKernelGGL(k_origin_bounds, dim3(bgrid), dim3(kBlock), 0, st, s.n, s.in.p, s.bounds);
+        hipLaunchKernelGGL(k_seg_keys_op, dim3(grid_of(s.n)), dim3(kBlock), 0, st, s.n, s.in.o, s.in.p, s.bounds,
                            s.key_mode == 4 ? 1 : 0, s.keys, s.vals);
         key_bits = 60;
     } else if (s.key_mode == 2 || s.key_mode == 3) {
-        hipLaunchKernelGGL(k_origin_bounds, dim3(bgrid), dim3(kBlock), 0, st, s.n, s.p, s.bounds);
-        hipLaunchKernelGGL(k_seg_keys_line, dim3(grid_of(s.n)), dim3(kBlock), 0, st, s.n, s.o, s.p, s.d, s.bounds,
+        hipLaunchKernelGGL(k_origin_bounds, dim3(bgrid), dim3(kBlock), 0, st, s.n, s.in.p, s.bounds);
+        hipLaunchKernelGGL(k_seg_keys_line, dim3(grid_of(s.n)), dim3(kBlock), 0, st, s.n, s.in.o, s.in.p, s.in.d, s.bounds,
                            s.key_mode == 3 ? 1 : 0, s.keys, s.vals);
         key_bits = s.key_mode == 3 ? 58 : 59;
     } else {
-        hipLaunchKernelGGL(k_seg_keys, dim3(grid_of(s.n)), dim3(kBlock), 0, st, s.n, s.o, s.d, s.bounds, s.keys,
+        hipLaunchKernelGGL(k_seg_keys, dim3(grid_of(s.n)), dim3(kBlock), 0, st, s.n, s.in.o, s.in.d, s.bounds, s.keys,
                            s.vals);
     }
     hipError_t e = hipGetLastError();
@@ -485,8 +476,8 @@ hipError_t launch_sort_segments(const SegSort &s, hipStream_t st) {
                : rocprim::radix_sort_pairs(s.tmp, bytes, s.keys, s.keys_alt, s.vals, s.vals_alt, (size_t)s.n,
                                            (unsigned int)lo, (unsigned int)key_bits, st);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_seg_permute, dim3(grid_of(s.n)), dim3(kBlock), 0, st, s.n, s.vals_alt, s.o, s.p, s.d, s.t,
-                       s.pix, s.o2, s.p2, s.d2, s.t2, s.pix2);
+    hipLaunchKernelGGL(k_seg_permute, dim3(grid_of(s.n)), dim3(kBlock), 0, st, s.n, s.vals_alt, s.in.o, s.in.p, s.in.d,
+                       s.in.t, s.in.pix, s.out.o, s.out.p, s.out.d, s.out.t, s.out.pix);
     return hipGetLastError();
 }
 

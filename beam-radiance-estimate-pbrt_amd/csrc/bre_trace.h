@@ -9,6 +9,7 @@
 #include "../../include/bre_fmath.h"
 #include "../../include/bre_scene.h"
 #include "bre_math.h"
+#include "bre_views.h"
 
 #include <vector>
 
@@ -614,8 +615,8 @@ struct DevCamera {
 
 // per-(depth, pixel-slot) camera segments before compaction
 struct CamSlots {
-    float *o, *p, *d, *t;
-    int32_t *pix, *valid;
+    SegOut seg;
+    int32_t *valid;
 };
 
 void prepare_camera(const bre_scene *s, int width, int height, DevCamera *c, std::vector<uint16_t> *perms);
@@ -627,8 +628,8 @@ hipError_t launch_camera(const DevScene *scene, int stack_depth, const DevCamera
 size_t camera_scan_temp_bytes(int64_t n);
 hipError_t launch_camera_scan(void *tmp, size_t tmp_bytes, const CamSlots &s, int64_t nslots, int max_depth,
                               int64_t *offs, hipStream_t stream, bool slot);
-hipError_t launch_camera_compact(const CamSlots &s, int64_t nslots, int max_depth, const int64_t *offs, float *o,
-                                 float *p, float *d, float *t, int32_t *pix, int32_t *depth, hipStream_t stream);
+hipError_t launch_camera_compact(const CamSlots &s, int64_t nslots, int max_depth, const int64_t *offs,
+                                 const SegOut &out, int32_t *depth, hipStream_t stream);
 
 // dynamic LDS of a photon / camera launch: the scene traversal stack of every thread of a block
 inline size_t scene_stack_bytes(int stack_depth, int block) {
@@ -639,12 +640,11 @@ inline size_t scene_stack_bytes(int stack_depth, int block) {
 // mode 0: count beams per photon; 1: write them at offsets (over > 0: only photons with more than `over`
 // beams); 2: write the first `over` beams to per-photon slots and count them all (single-trace form)
 hipError_t launch_photons(const DevScene *scene, int stack_depth, int64_t n, uint64_t seq0, int max_depth,
-                          float radius, int32_t *counts, const int64_t *offsets, float *start, float *end,
-                          float *rad, float *power, int mode, int over, hipStream_t s);
+                          float radius, int32_t *counts, const int64_t *offsets, const BeamOut &out, int mode,
+                          int over, hipStream_t s);
 // the single-trace form's copy of each photon's slots to its offsets
-hipError_t launch_photon_slots(int64_t n, int cap, const int32_t *counts, const int64_t *offsets, const float *ss,
-                               const float *se, const float *sr, const float *sp, float *start, float *end,
-                               float *rad, float *power, hipStream_t s);
+hipError_t launch_photon_slots(int64_t n, int cap, const int32_t *counts, const int64_t *offsets,
+                               const BeamView &slots, const BeamOut &out, hipStream_t s);
 size_t count_scan_temp_bytes(int64_t n);
 hipError_t launch_count_scan(void *tmp, size_t bytes, const int32_t *counts, int64_t *offsets, int64_t n, hipStream_t s,
                              bool slot);

@@ -1,7 +1,7 @@
 """Host restatement of the beam BVH's hierarchy kernels and a validator of built trees (test
 infrastructure, next to refpy.py).
 
-Written from the kernels' comments (bre_build.hip k_karras / k_refit / k_single, bre_gather.hip
+Written from the kernels' comments (bre_build.hip k_karras / k_refit / k_single, bre_roots.hip
 k_collapse4, the record layouts of bre_device.h) and Karras 2012, "Maximizing Parallelism in the
 Construction of BVHs, Octrees, and k-d Trees".  Plain numpy: every node is computed at once, every
 loop has a fixed bound, and nothing here indexes outside an array: what the kernel would write out

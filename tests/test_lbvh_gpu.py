@@ -1,4 +1,4 @@
-"""The beam BVH the GPU builds (bre_build.hip k_karras / k_refit / k_single, bre_gather.hip k_collapse4)
+"""The beam BVH the GPU builds (bre_build.hip k_karras / k_refit / k_single, bre_roots.hip k_collapse4)
 against the host restatement and validator of tests/refpy_lbvh.py, word for word.
 
 * bre_device_check kind 10 runs the hierarchy kernels on the key sets of tests/test_lbvh_host.py (every

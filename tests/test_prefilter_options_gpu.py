@@ -4,7 +4,7 @@ Option 111 (prefilter margins: 1 = the round-3 rounding analysis, default; 0 = r
 margins) and option 112 (the per-lane tile line reject: 1 = on, default since round 4; 0 = off) only
 change which NON-contributing (lane, beam) pairs reach the exact stage: a pair either margin rejects
 has every reference-computed distance >= R + r (tests/test_margin_bound.py), and a lane the tile line
-reject takes off a tile has no pair in it that can contribute (bre_gather.hip, above k_tile_axis).  Removing non-contributing pairs
+reject takes off a tile has no pair in it that can contribute (bre_tileaxis.hip, above k_tile_axis).  Removing non-contributing pairs
 from the beam-major queue leaves the contributing pairs in the same relative order, so every
 per-segment sum and contribution count must be identical in all combinations -- on real C2
 data (the production configuration: kernel 0, counters off, segment sort on) at a large and a small

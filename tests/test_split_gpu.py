@@ -1,6 +1,6 @@
 """The tile kernel's work-root count S (BRE_OPT_SPLIT, powers of two up to 1024) only partitions the
 tree: every segment's contributing pairs and counts are the same for any S, and its sum differs only
-by the order in which k_reduce adds the S subtree partials (bre_gather.hip k_roots: size-balanced
+by the order in which k_reduce adds the S subtree partials (bre_roots.hip k_roots: size-balanced
 roots, largest first).  Real C2 data at a large and a small radius."""
 import numpy as np
 import pytest

@@ -1,4 +1,4 @@
-"""The work-root selection (bre_gather.hip k_roots), restated on the host.
+"""The work-root selection (bre_roots.hip k_roots), restated on the host.
 
 Round 4 chose the S work roots by a serial greedy expansion: starting from the root, replace the
 frontier's largest interior node (leaf tiles below it; ties: the lowest frontier position) by its

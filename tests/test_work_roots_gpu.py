@@ -1,4 +1,4 @@
-"""The work roots the GPU computes (k_roots, bre_gather.hip; read through bre_device_check kind 5)
+"""The work roots the GPU computes (k_roots, bre_roots.hip; read through bre_device_check kind 5)
 against the host restatements of tests/test_work_roots.py: random trees, deep and
 unbalanced ones (a caterpillar of 20,000 interior nodes puts far more heavy nodes than the kernel's
 4096 cache slots in reach: its overflow path), S from 1 to kMaxSplit.  The roots must be exactly the
