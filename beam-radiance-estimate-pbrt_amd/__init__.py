@@ -44,7 +44,7 @@ EXPORTS = [
     "bre_render_iteration", "bre_render",
     "bre_render_progressive", "bre_shard_segments", "bre_set_beams_sharded", "bre_gather_sharded",
     "bre_device_check", "bre_resolve_classes", "bre_film_add", "bre_set_gather_after", "bre_set_gather_events",
-    "bre_render_sharded", "bre_render_progressive_sharded", "bre_set_lights",
+    "bre_render_sharded", "bre_render_progressive_sharded", "bre_set_lights", "bre_set_materials",
 ]
 # bre_image_fn: int on_image(int32 iteration, const float *image_rgb, void *user)
 IMAGE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_int32, ctypes.POINTER(ctypes.c_float), ctypes.c_void_p)
@@ -129,6 +129,9 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     if hasattr(lib, "bre_set_lights"):  # (absent from earlier libraries loaded for A/B timing)
         lib.bre_set_lights.argtypes = [P, P, I32]
         lib.bre_set_lights.restype = I32
+    if hasattr(lib, "bre_set_materials"):
+        lib.bre_set_materials.argtypes = [P, P, I32, P, I64]
+        lib.bre_set_materials.restype = I32
     lib.bre_get_beams.argtypes = [P, I64, P, P, P, P, ctypes.POINTER(I64)]
     lib.bre_get_beams.restype = I32
     lib.bre_scene_cornell.argtypes = [P, F, F, F]
@@ -338,6 +341,20 @@ class BeamGather:
         arr = (Light * max(len(lights), 1))(*lights)
         self._check(self.lib.bre_set_lights(self.h, arr if lights else None, len(lights)))
 
+    # ---- materials ----
+    def set_materials(self, materials=(), triangle_material=()):
+        """bre_set_materials: the mirror / glass table (scene.Material: scene.mirror, scene.glass, a parsed
+        scene's .materials) and each scene triangle's index into it (-1: its own matte kd), as
+        scene.scene_materials returns them; used by every later pass and render of this context.  An empty
+        table clears them."""
+        from .scene import Material
+
+        materials = list(materials)
+        tm = np.ascontiguousarray(triangle_material, np.int32).reshape(-1)
+        arr = (Material * max(len(materials), 1))(*materials)
+        self._check(self.lib.bre_set_materials(self.h, arr if materials else None, len(materials),
+                                               tm.ctypes.data if tm.size else None, tm.size))
+
     # ---- photon pass ----
     def trace_photons(self, scene, n_photons: int, iteration: int = 0, max_depth: int = 5,
                       radius: float = 0.01) -> int:
@@ -446,6 +463,15 @@ class BeamGather:
         self._check(self.lib.bre_device_check(self.h, kind, n, _ptr(x), 0 if a is None else a.shape[0],
                                               None if a is None else _ptr(a), _ptr(y)))
         return y
+
+    def specular_check(self, records):
+        """bre_device_check kind 12: the passes' specular lobe with Kr = Kt = 1 on records [n, 6] of
+        (wo xyz in the shading frame, u0, eta with 0 = mirror, mode 0 Importance / 1 Radiance).  Returns
+        (wi [n, 3], pdf [n], f [n], type int32 [n]); all zero where Sample_f returns 0."""
+        x = np.ascontiguousarray(records, dtype=np.float32).reshape(-1, 6)
+        y = np.zeros_like(x)
+        self._check(self.lib.bre_device_check(self.h, 12, x.size, _ptr(x), 0, None, _ptr(y)))
+        return y[:, :3].copy(), y[:, 3].copy(), y[:, 4].copy(), y[:, 5].copy().view(np.int32)
 
     def slot_sort(self, keys, begin_bit: int = 0, end_bit: int | None = None):
         """bre_device_check kinds 6 / 8: the pass chain's stable radix sort (bre_slot.hip) of uint64 or

@@ -120,10 +120,24 @@ extern "C" {
 bre_status bre_device_check(bre_ctx *c, int32_t kind, int64_t n, const float *x, int32_t n_aux, const float *aux,
                             float *y) {
     if (!c) return BRE_ERR_INVALID_ARG;
-    if (kind < 0 || kind > 11) return fail(c, BRE_ERR_INVALID_ARG, "bre_device_check: kind %d not in [0, 11]", kind);
+    if (kind < 0 || kind > 12) return fail(c, BRE_ERR_INVALID_ARG, "bre_device_check: kind %d not in [0, 12]", kind);
     if (kind == 10) return check_hierarchy(c, n, x, n_aux, aux, y);
     if (kind == 11) return check_read_tree(c, n, y);
     if (n < 0 || (n > 0 && (!x || !y))) return fail(c, BRE_ERR_INVALID_ARG, "bre_device_check: bad arrays");
+    if (kind == 12) {
+        // the specular lobe of the photon and camera passes on records of 6 floats (layout: include/bre.h)
+        if (n % 6) return fail(c, BRE_ERR_INVALID_ARG, "bre_device_check: kind 12 needs whole records of 6 floats");
+        if (n == 0) return BRE_OK;
+        BRE_TRY(set_device(c));
+        float *dx = nullptr, *dy = nullptr;
+        HIPCHK(c, c->chk_x.get((size_t)n, &dx));
+        HIPCHK(c, c->chk_y.get((size_t)n, &dy));
+        HIPCHK(c, hipMemcpyAsync(dx, x, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, launch_check_specular(n / 6, dx, dy, c->stream));
+        HIPCHK(c, hipMemcpyAsync(y, dy, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return BRE_OK;
+    }
     if (kind >= 6 && kind <= 8) {
         // the pass chain's one-wave primitives (bre_slot.hip) on caller data
         BRE_TRY(set_device(c));

@@ -46,7 +46,23 @@ bre_status check_scene(bre_ctx *c, const bre_scene *scene, const char *fn) {
         if (c->lights[k].order > scene->n_triangles)
             return fail(c, BRE_ERR_INVALID_ARG, "%s: light %d has order %d, the scene has %d triangles", fn, (int)k,
                         c->lights[k].order, scene->n_triangles);
+    if (!c->mats.empty() && c->tri_mat.size() != (size_t)scene->n_triangles)
+        return fail(c, BRE_ERR_INVALID_ARG, "%s: the material map (bre_set_materials) covers %lld triangles, the scene "
+                    "has %d", fn, (long long)c->tri_mat.size(), scene->n_triangles);
     return BRE_OK;
+}
+
+// The byte ranges the geometry cache is keyed by, in the order sc_bytes keeps them: the scene's triangles,
+// then the context's lights, materials and material map
+struct KeyPart {
+    const void *p;
+    size_t bytes;
+};
+void geometry_key(const bre_ctx *c, const bre_scene *s, KeyPart part[4]) {
+    part[0] = {scene_triangles(s), (size_t)s->n_triangles * sizeof(bre_triangle)};
+    part[1] = {c->lights.data(), c->lights.size() * sizeof(bre_light)};
+    part[2] = {c->mats.data(), c->mats.size() * sizeof(bre_material)};
+    part[3] = {c->tri_mat.data(), c->tri_mat.size() * sizeof(int32_t)};
 }
 
 uint64_t hash_bytes(uint64_t h, const void *data, size_t bytes) {
@@ -62,17 +78,18 @@ uint64_t hash_bytes(uint64_t h, const void *data, size_t bytes) {
     return h;
 }
 
-// 64-bit hash of the scene's triangles and the context's lights (the geometry cache key of
-// upload_scene); without lights it is the hash of the triangles alone
-uint64_t hash_geometry(const bre_scene *s, const std::vector<bre_light> &lights) {
-    uint64_t h = hash_bytes(0x9e3779b97f4a7c15ull ^ (uint64_t)s->n_triangles, scene_triangles(s),
-                            (size_t)s->n_triangles * sizeof(bre_triangle));
-    if (!lights.empty()) h = hash_bytes(h ^ (uint64_t)lights.size(), lights.data(), lights.size() * sizeof(bre_light));
+// 64-bit hash of the scene's triangles and the context's lights, materials and material map (the
+// geometry cache key of upload_scene); without lights and materials it is the hash of the triangles alone
+uint64_t hash_geometry(const bre_scene *s, const KeyPart part[4]) {
+    uint64_t h = hash_bytes(0x9e3779b97f4a7c15ull ^ (uint64_t)s->n_triangles, part[0].p, part[0].bytes);
+    for (int k = 1; k < 4; ++k)
+        if (part[k].bytes) h = hash_bytes(h ^ (uint64_t)(part[k].bytes * (size_t)k), part[k].p, part[k].bytes);
     return h | 1ull;  // never 0 (= no scene)
 }
 
 // DevScene (+ the density grid of a GridDensityMedium) into ph_scene on the context's stream.  The
-// geometry (triangles, BVHAccel, lights) is rebuilt and uploaded only when the triangles change.
+// geometry (triangles, BVHAccel, lights, materials) is rebuilt and uploaded only when the triangles, the
+// context's lights or its materials change.
 bre_status upload_scene(bre_ctx *c, const bre_scene *scene) {
     float *dd = nullptr;
     if (scene->has_medium == BRE_MEDIUM_GRID) {
@@ -89,17 +106,25 @@ bre_status upload_scene(bre_ctx *c, const bre_scene *scene) {
         }
         dd = c->grid_dens.as<float>();
     }
-    const uint64_t h = hash_geometry(scene, c->lights);
+    KeyPart part[4];
+    geometry_key(c, scene, part);
+    const uint64_t h = hash_geometry(scene, part);
     // the geometry is reused only when the hash AND the bytes match (a hash collision between two
-    // scenes must not trace against the stale BVH and lights); the lights' bytes follow the triangles'
-    const size_t tri_bytes = (size_t)scene->n_triangles * sizeof(bre_triangle);
-    const size_t light_bytes = c->lights.size() * sizeof(bre_light);
-    const bool same = h == c->sc_hash && c->sc_bytes.size() == tri_bytes + light_bytes &&
-                      (tri_bytes == 0 || memcmp(c->sc_bytes.data(), scene_triangles(scene), tri_bytes) == 0) &&
-                      (light_bytes == 0 || memcmp(c->sc_bytes.data() + tri_bytes, c->lights.data(), light_bytes) == 0);
+    // scenes must not trace against the stale BVH, lights and materials)
+    bool same = h == c->sc_hash;
+    for (int k = 0; k < 4; ++k) same = same && c->sc_part[k] == part[k].bytes;
+    size_t off = 0;
+    for (int k = 0; same && k < 4; ++k) {
+        same = part[k].bytes == 0 || memcmp(c->sc_bytes.data() + off, part[k].p, part[k].bytes) == 0;
+        off += part[k].bytes;
+    }
     if (!same) {
         HostScene hs;
-        prepare_geometry(scene, &hs, c->lights.data(), (int)c->lights.size());
+        MaterialMap mm;
+        mm.mats = c->mats.data();
+        mm.n_mats = (int)c->mats.size();
+        mm.tri_mat = c->tri_mat.data();
+        prepare_geometry(scene, &hs, c->lights.data(), (int)c->lights.size(), mm);
         if (hs.depth > kSceneStack)
             return fail(c, BRE_ERR_INVALID_ARG, "scene BVH depth %d exceeds the %d-entry traversal stack (as in "
                         "BVHAccel::Intersect)", hs.depth, kSceneStack);
@@ -115,6 +140,7 @@ bre_status upload_scene(bre_ctx *c, const bre_scene *scene) {
         HIPCHK(c, up(c->sc_light_func, hs.light_func.data(), hs.light_func.size() * sizeof(float)));
         HIPCHK(c, up(c->sc_light_cdf, hs.light_cdf.data(), hs.light_cdf.size() * sizeof(float)));
         HIPCHK(c, up(c->sc_dlights, hs.dlights.data(), hs.dlights.size() * sizeof(DLight)));
+        HIPCHK(c, up(c->sc_mats, hs.mats.data(), hs.mats.size() * sizeof(bre_material)));
         HIPCHK(c, hipStreamSynchronize(c->stream));  // the host vectors go out of scope
         c->sc_head = hs.head;
         c->sc_head.t = c->sc_tris.as<PTri>();
@@ -124,11 +150,14 @@ bre_status upload_scene(bre_ctx *c, const bre_scene *scene) {
         c->sc_head.light_func = c->sc_light_func.as<float>();
         c->sc_head.light_cdf = c->sc_light_cdf.as<float>();
         c->sc_head.dlights = c->sc_dlights.as<DLight>();
+        c->sc_head.mats = c->sc_mats.as<bre_material>();
         c->sc_hash = h;
-        const unsigned char *tb = reinterpret_cast<const unsigned char *>(scene_triangles(scene));
-        c->sc_bytes.assign(tb, tb + tri_bytes);
-        const unsigned char *lb = reinterpret_cast<const unsigned char *>(c->lights.data());
-        c->sc_bytes.insert(c->sc_bytes.end(), lb, lb + light_bytes);
+        c->sc_bytes.clear();
+        for (int k = 0; k < 4; ++k) {
+            const unsigned char *b = static_cast<const unsigned char *>(part[k].p);
+            if (part[k].bytes) c->sc_bytes.insert(c->sc_bytes.end(), b, b + part[k].bytes);
+            c->sc_part[k] = part[k].bytes;
+        }
     }
     DevScene ds;
     memcpy(&ds, &c->sc_head, sizeof(DevScene));  // padding bytes included: the record compares bytewise
@@ -197,6 +226,47 @@ bre_status bre_set_lights(bre_ctx *c, const bre_light *lights, int32_t n) {
         if (!finite) return fail(c, BRE_ERR_INVALID_ARG, "bre_set_lights: light %d has a non-finite field", k);
     }
     c->lights.assign(lights, lights + n);
+    return BRE_OK;
+}
+
+bre_status bre_set_materials(bre_ctx *c, const bre_material *materials, int32_t n_materials,
+                             const int32_t *triangle_material, int64_t n_triangles) {
+    if (!c) return BRE_ERR_INVALID_ARG;
+    const char *fn = "bre_set_materials";
+    if (n_materials < 0 || n_materials > BRE_MAX_MATERIALS)
+        return fail(c, BRE_ERR_INVALID_ARG, "%s: material count must be in 0..%d", fn, BRE_MAX_MATERIALS);
+    if (n_materials == 0) {
+        c->mats.clear();
+        c->tri_mat.clear();
+        return BRE_OK;
+    }
+    if (n_triangles < 0 || n_triangles > BRE_MAX_SCENE_TRIANGLES)
+        return fail(c, BRE_ERR_INVALID_ARG, "%s: the material map's triangle count must be in 0..%d", fn,
+                    BRE_MAX_SCENE_TRIANGLES);
+    if (!materials || (n_triangles > 0 && !triangle_material))
+        return fail(c, BRE_ERR_INVALID_ARG, "%s: null material table or triangle_material map", fn);
+    std::vector<bre_material> mats(materials, materials + n_materials);
+    for (int k = 0; k < n_materials; ++k) {
+        bre_material &m = mats[(size_t)k];
+        if (m.type != BRE_MATERIAL_MIRROR && m.type != BRE_MATERIAL_GLASS)
+            return fail(c, BRE_ERR_INVALID_ARG, "%s: material %d has unknown type %d", fn, k, m.type);
+        if (!std::isfinite(m.eta) || !(m.eta > 0))
+            return fail(c, BRE_ERR_INVALID_ARG, "%s: material %d has eta %g (must be finite and > 0)", fn, k, m.eta);
+        for (int j = 0; j < 3; ++j) {
+            if (!std::isfinite(m.kr[j]) || !std::isfinite(m.kt[j]))
+                return fail(c, BRE_ERR_INVALID_ARG, "%s: material %d has a non-finite Kr or Kt", fn, k);
+            // Kr->Evaluate(*si).Clamp() (mirror.cpp:52, glass.cpp:54-55) bounds the value below by 0; the ABI
+            // also bounds it above by 1 (a reflectance), which a physical scene file never exceeds
+            m.kr[j] = m.kr[j] < 0.f ? 0.f : (m.kr[j] > 1.f ? 1.f : m.kr[j]);
+            m.kt[j] = m.kt[j] < 0.f ? 0.f : (m.kt[j] > 1.f ? 1.f : m.kt[j]);
+        }
+    }
+    for (int64_t i = 0; i < n_triangles; ++i)
+        if (triangle_material[i] < -1 || triangle_material[i] >= n_materials)
+            return fail(c, BRE_ERR_INVALID_ARG, "%s: triangle %lld has material index %d outside [-1, %d)", fn,
+                        (long long)i, triangle_material[i], n_materials);
+    c->mats.swap(mats);
+    c->tri_mat.assign(triangle_material, triangle_material + n_triangles);
     return BRE_OK;
 }
 

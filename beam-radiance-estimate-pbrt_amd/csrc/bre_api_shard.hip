@@ -205,6 +205,12 @@ bre_status check_render_sharded(bre_ctx *const *ctxs, int n_ctx, const bre_scene
         const std::vector<bre_light> &a = ctxs[0]->lights, &b = ctxs[i]->lights;
         if (a.size() != b.size() || (!a.empty() && memcmp(a.data(), b.data(), a.size() * sizeof(bre_light)) != 0))
             return fail(ctxs[0], BRE_ERR_INVALID_ARG, "context %d: %s: its lights (bre_set_lights) differ from context 0's", i, fn);
+        // ... and shade it alike (bre_set_materials): the stored table is the clamped one on both sides
+        const std::vector<bre_material> &ma = ctxs[0]->mats, &mb = ctxs[i]->mats;
+        const std::vector<int32_t> &ta = ctxs[0]->tri_mat, &tb = ctxs[i]->tri_mat;
+        if (ma.size() != mb.size() || ta != tb ||
+            (!ma.empty() && memcmp(ma.data(), mb.data(), ma.size() * sizeof(bre_material)) != 0))
+            return fail(ctxs[0], BRE_ERR_INVALID_ARG, "context %d: %s: its materials (bre_set_materials) differ from context 0's", i, fn);
     }
     if (!class_films(n_ctx) || !rp->render_media) return BRE_OK;
     for (int i = 0; i < n_ctx; ++i) {

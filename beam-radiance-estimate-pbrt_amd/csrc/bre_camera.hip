@@ -260,22 +260,18 @@ __device__ __forceinline__ int64_t halton_index(const DevCamera &C, int px, int 
     return off + sample_num * C.stride;
 }
 
-// ---- matte triangle BSDF (reflection.cpp:650-768) ----
-__device__ __forceinline__ f3 to_local(const PTri &q, f3 v) { return mk(dot3(v, q.ss), dot3(v, q.ts), dot3(v, q.n)); }
-__device__ __forceinline__ f3 to_world(const PTri &q, f3 v) {
-    return mk(q.ss.x * v.x + q.ts.x * v.y + q.n.x * v.z, q.ss.y * v.x + q.ts.y * v.y + q.n.y * v.z,
-              q.ss.z * v.x + q.ts.z * v.y + q.n.z * v.z);
-}
+// ---- matte triangle BSDF (reflection.cpp:650-768); q.mat != kMatMatte: no BxDF matches (none at all, or only
+// a specular one, which f() and Pdf() never match and which the bounce samples through specular_sample) ----
 __device__ __forceinline__ void bsdf_f(const PTri &q, f3 wo_w, f3 wi_w, float f[3]) {
     f[0] = f[1] = f[2] = 0.f;
-    if (q.absorb) return;
+    if (q.mat) return;
     if (to_local(q, wo_w).z == 0) return;
     const bool reflect = dot3(wi_w, q.n) * dot3(wo_w, q.n) > 0;
     if (reflect)
         for (int c = 0; c < 3; ++c) f[c] = 0.f + q.kd[c] * kInvPi;
 }
 __device__ __forceinline__ float bsdf_pdf(const PTri &q, f3 wo_w, f3 wi_w) {
-    if (q.absorb) return 0.f;
+    if (q.mat) return 0.f;
     const f3 wo = to_local(q, wo_w), wi = to_local(q, wi_w);
     if (wo.z == 0) return 0.f;
     float pdf = 0.f;
@@ -286,7 +282,7 @@ __device__ __forceinline__ float bsdf_pdf(const PTri &q, f3 wo_w, f3 wi_w) {
 __device__ __forceinline__ bool bsdf_sample(const PTri &q, f3 wo_w, float ux, float uy, f3 &wi_w, float &pdf,
                                             float f[3]) {
     f[0] = f[1] = f[2] = 0.f;
-    if (q.absorb) {
+    if (q.mat) {
         pdf = 0.f;
         return false;
     }
@@ -317,6 +313,10 @@ __device__ void estimate_direct(const DevScene &S, HaltonDev &hs, f3 p, f3 perr,
     const bool delta = li < 0;
     const PTri &L = S.t[delta ? 0 : li];
     Ld[0] = Ld[1] = Ld[2] = 0.f;
+    // A specular vertex (bsdfFlags = BSDF_ALL & ~BSDF_SPECULAR matches no BxDF of a mirror or glass): bsdf.f
+    // is 0, so there is no shadow ray and no Tr draw (:132-152), and the BSDF-sampling half's Sample_f has
+    // matchingComps == 0 (f = 0, pdf = 0).  Ld = 0 without a draw.
+    if (q.mat >= kMatTable) return;
     float scat_pdf = 0.f;
     f3 wi = mk(0, 0, 0);
     float Li[3] = {0.f, 0.f, 0.f};
@@ -464,6 +464,7 @@ __global__ __launch_bounds__(kCamBlock, 6) void k_camera(const DevScene *__restr
     }
     float beta[3] = {1.f, 1.f, 1.f};
     float Ld[3] = {0.f, 0.f, 0.f};
+    bool specular_bounce = false;  // :478
     for (int depth = 0; depth < max_depth; ++depth) {
         float tmax = __builtin_huge_valf();
         Hit hit;
@@ -489,8 +490,9 @@ __global__ __launch_bounds__(kCamBlock, 6) void k_camera(const DevScene *__restr
         if (!render_surfaces) break;
         const PTri &q = S.t[hit.tri];
         const f3 wo = neg3(d);
-        // isect.Le(wo): the triangle's own area light, one-sided (diffuse.h:56-58)
-        if (depth == 0 && q.emit && dot3(q.n, wo) > 0)
+        // isect.Le(wo): the triangle's own area light, one-sided (diffuse.h:56-58), at the first vertex and
+        // after a mirror or glass bounce (:528-529)
+        if ((depth == 0 || specular_bounce) && q.emit && dot3(q.n, wo) > 0)
             for (int c = 0; c < 3; ++c) Ld[c] = Ld[c] + beta[c] * q.Le[c];
         // UniformSampleOneLight (integrator.cpp:54-82): light uniformly, uLight, uScattering
         const int ln = min((int)(hs.get1d() * S.n_lights), S.n_lights - 1);
@@ -506,7 +508,18 @@ __global__ __launch_bounds__(kCamBlock, 6) void k_camera(const DevScene *__restr
             float ux, uy, pdf = 0.f, f[3];
             hs.get2d(ux, uy);
             f3 wi;
-            if (!bsdf_sample(q, wo, ux, uy, wi, pdf, f) || pdf == 0 || black3(f)) break;
+            int type = 0;  // the sampled BxDFType's specular bit; a Lambertian lobe has none
+            bool ok;
+            if (q.mat >= kMatTable) {
+                // mirror / glass: the one specular lobe, TransportMode::Radiance (:514)
+                f3 wil;
+                ok = specular_sample(S.mats[q.mat - kMatTable], to_local(q, wo), ux, kModeRadiance, wil, pdf, f, type);
+                if (ok) wi = to_world(q, wil);
+            } else {
+                ok = bsdf_sample(q, wo, ux, uy, wi, pdf, f);
+            }
+            if (!ok || pdf == 0 || black3(f)) break;
+            specular_bounce = (type & kBsdfSpecular) != 0;  // :543
             const float ad = fabsf(dot3(wi, q.n));
             for (int c = 0; c < 3; ++c) beta[c] = beta[c] * (f[c] * ad / pdf);
             o = offset_origin(hit.p, hit.perr, q.n, wi);

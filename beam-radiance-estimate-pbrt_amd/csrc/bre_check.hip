@@ -50,7 +50,37 @@ __global__ __launch_bounds__(256) void k_check(int kind, int64_t n, const float 
     }
 }
 
+// kind 12: specular_sample (bre_trace.h) on n records of 6 floats (wo xyz, u0, eta with 0 = mirror, mode),
+// Kr = Kt = 1; 6 words out per record: wi xyz, pdf, f, the sampled type (int32)
+__global__ __launch_bounds__(256) void k_check_specular(int64_t n, const float *__restrict__ x, float *__restrict__ y) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float *r = x + 6 * i;
+    bre_material m;
+    m.type = r[4] == 0.f ? BRE_MATERIAL_MIRROR : BRE_MATERIAL_GLASS;
+    m.kr[0] = m.kr[1] = m.kr[2] = m.kt[0] = m.kt[1] = m.kt[2] = 1.f;
+    m.eta = r[4];
+    f3 wi = mk(0.f, 0.f, 0.f);
+    float pdf, f[3];
+    int type;
+    if (!specular_sample(m, mk(r[0], r[1], r[2]), r[3], r[5] != 0.f ? kModeRadiance : kModeImportance, wi, pdf, f, type))
+        wi = mk(0.f, 0.f, 0.f);
+    float *o = y + 6 * i;
+    o[0] = wi.x;
+    o[1] = wi.y;
+    o[2] = wi.z;
+    o[3] = pdf;
+    o[4] = f[0];
+    o[5] = __int_as_float(type);
+}
+
 }  // namespace
+
+hipError_t launch_check_specular(int64_t n, const float *x, float *y, hipStream_t s) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_check_specular, dim3((unsigned int)((n + 255) / 256)), dim3(256), 0, s, n, x, y);
+    return hipGetLastError();
+}
 
 // outputs per input: 1 for kinds 0, 1, 3; 2 for kinds 2 and 4; 4 for kind 9
 hipError_t launch_device_check(int kind, int64_t n, const float *x, int n_aux, const float *aux, float *y,

@@ -221,11 +221,14 @@ struct bre_ctx {
     bre::DevMem ph_scene, ph_counts, ph_offsets, ph_tmp, grid_dens;
     bre::BeamArrays ph_s;  // single-trace photon pass: per-photon beam slots
     // scene geometry on the device (upload_scene): triangles, BVHAccel nodes + primitive order, lights
-    bre::DevMem sc_tris, sc_nodes, sc_prims, sc_light_tri, sc_light_func, sc_light_cdf, sc_dlights;
+    bre::DevMem sc_tris, sc_nodes, sc_prims, sc_light_tri, sc_light_func, sc_light_cdf, sc_dlights, sc_mats;
     std::vector<bre_light> lights;          // bre_set_lights: the delta lights every pass adds to its scene
-    uint64_t sc_hash = 0;                   // hash of the uploaded triangles and lights (0: none)
-    std::vector<unsigned char> sc_bytes;    // the uploaded triangles' bytes, then the lights': a hash match is
-                                            // confirmed by memcmp
+    std::vector<bre_material> mats;         // bre_set_materials: the mirror / glass table (Kr, Kt clamped) ...
+    std::vector<int32_t> tri_mat;           // ... and each triangle's index into it (-1: its own matte kd)
+    uint64_t sc_hash = 0;                   // hash of the uploaded triangles, lights and materials (0: none)
+    std::vector<unsigned char> sc_bytes;    // the uploaded triangles' bytes, then the lights', the materials' and
+                                            // the map's: a hash match is confirmed by memcmp
+    size_t sc_part[4] = {0, 0, 0, 0};       // the byte counts of those four ranges
     bre::DevScene sc_head;                  // geometry fields of the uploaded scene
     bre::DevScene ph_scene_host;            // the record last copied to ph_scene
     std::vector<unsigned char> grid_bytes;  // the density grid last copied to grid_dens

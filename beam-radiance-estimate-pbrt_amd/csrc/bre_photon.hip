@@ -86,9 +86,11 @@ static float light_power_y(const DLight &D) {
     return lum3(pw);
 }
 
-void prepare_geometry(const bre_scene *s, HostScene *out, const bre_light *lights, int n_lights) {
+void prepare_geometry(const bre_scene *s, HostScene *out, const bre_light *lights, int n_lights,
+                      const MaterialMap &mm) {
     DevScene &d = out->head;
     d.n_tris = s->n_triangles;
+    out->mats.assign(mm.mats, mm.mats + mm.n_mats);
     const bre_triangle *tri = scene_triangles(s);
     out->tris.resize((size_t)s->n_triangles);
     out->light_tri.clear();
@@ -132,7 +134,13 @@ void prepare_geometry(const bre_scene *s, HostScene *out, const bre_light *light
             T.kd[k] = t.kd[k];
             T.Le[k] = t.Le[k];
         }
-        T.absorb = (t.kd[0] == 0 && t.kd[1] == 0 && t.kd[2] == 0) ? 1 : 0;
+        T.mat = black3(t.kd) ? kMatNone : kMatMatte;
+        if (mm.n_mats > 0 && mm.tri_mat[i] >= 0) {
+            // mirror.cpp:50-56, glass.cpp:53-64: black Kr (and Kt) adds no BxDF
+            const bre_material &m = mm.mats[mm.tri_mat[i]];
+            const bool none = black3(m.kr) && (m.type == BRE_MATERIAL_MIRROR || black3(m.kt));
+            T.mat = none ? kMatNone : kMatTable + mm.tri_mat[i];
+        }
         T.emit = t.emit != 0;
         if (T.emit) {
             delta_up_to(i);
@@ -162,9 +170,10 @@ void prepare_geometry(const bre_scene *s, HostScene *out, const bre_light *light
     d.stack_depth = out->depth;
 }
 
-void prepare_scene(const bre_scene *s, HostScene *out, const float *d_density, const bre_light *lights, int n_lights) {
+void prepare_scene(const bre_scene *s, HostScene *out, const float *d_density, const bre_light *lights, int n_lights,
+                   const MaterialMap &mm) {
     out->head = DevScene{};
-    prepare_geometry(s, out, lights, n_lights);
+    prepare_geometry(s, out, lights, n_lights, mm);
     prepare_medium(s, &out->head, d_density);
 }
 
@@ -314,11 +323,12 @@ __global__ __launch_bounds__(kPhotonBlock, 6) void k_photons(const DevScene *__r
                 for (int c = 0; c < 3; ++c) bp[3 * k + c] = bm[c] * beta[c];
             }
             ++cnt;
-            // surface scattering (:296-323): Lambertian BSDF::Sample_f
+            // surface scattering (:296-323): BSDF::Sample_f of the Lambertian lobe, or of a mirror's or
+            // glass's specular lobe in TransportMode::Importance; the Get2D comes first either way
             float ux, uy;
             pcg_2d(rng, ux, uy);
             const PTri &q = S.t[hit.tri];
-            if (q.absorb) {
+            if (q.mat == kMatNone) {
                 stop = true;
             } else {
                 const f3 wo = neg3(d);
@@ -326,17 +336,22 @@ __global__ __launch_bounds__(kPhotonBlock, 6) void k_photons(const DevScene *__r
                 if (woz == 0) {
                     stop = true;
                 } else {
-                    f3 wil = cosine_hemisphere(ux, uy);
-                    if (woz < 0) wil.z *= -1;
-                    const float pdf = (woz * wil.z > 0) ? fabsf(wil.z) * kInvPi : 0.f;
-                    float fr[3];
-                    for (int c = 0; c < 3; ++c) fr[c] = q.kd[c] * kInvPi;
+                    f3 wil;
+                    float pdf, fr[3];
+                    if (q.mat >= kMatTable) {
+                        int type;
+                        specular_sample(S.mats[q.mat - kMatTable], mk(dot3(wo, q.ss), dot3(wo, q.ts), woz), ux,
+                                        kModeImportance, wil, pdf, fr, type);
+                    } else {
+                        wil = cosine_hemisphere(ux, uy);
+                        if (woz < 0) wil.z *= -1;
+                        pdf = (woz * wil.z > 0) ? fabsf(wil.z) * kInvPi : 0.f;
+                        for (int c = 0; c < 3; ++c) fr[c] = q.kd[c] * kInvPi;
+                    }
                     if (pdf == 0 || black3(fr)) {
                         stop = true;
                     } else {
-                        const f3 wi = mk(q.ss.x * wil.x + q.ts.x * wil.y + q.n.x * wil.z,
-                                         q.ss.y * wil.x + q.ts.y * wil.y + q.n.y * wil.z,
-                                         q.ss.z * wil.x + q.ts.z * wil.y + q.n.z * wil.z);
+                        const f3 wi = to_world(q, wil);
                         const float ad = fabsf(dot3(wi, q.n));
                         float bn[3];
                         for (int c = 0; c < 3; ++c) bn[c] = bm[c] * beta[c] * fr[c] * ad / pdf;

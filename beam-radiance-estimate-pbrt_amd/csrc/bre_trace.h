@@ -150,9 +150,18 @@ struct PTri {
     f3 ns;       // Triangle::Sample's normal: normalize(cross(p1 - p0, p2 - p0)), negated if flip
     float kd[3], Le[3];
     float area;  // 0.5 * |cross(p1 - p0, p2 - p0)|
-    int absorb;  // kd all zero: no BxDF
+    int mat;     // kMatMatte: Lambertian kd; kMatNone: no BxDF (black kd, or a black mirror / glass);
+                 // kMatTable + k: entry k of DevScene::mats
     int emit;    // a DiffuseAreaLight
 };
+constexpr int kMatMatte = 0, kMatNone = 1, kMatTable = 2;
+
+// BxDFType bits (reflection.h:126-134) of the lobes sampled here
+constexpr int kBsdfReflection = 1, kBsdfTransmission = 2, kBsdfSpecular = 16;
+constexpr int kModeImportance = 0, kModeRadiance = 1;  // TransportMode of a specular_sample call
+
+// The specular materials on the device are the context's bre_material records (Kr, Kt clamped)
+static_assert(sizeof(bre_material) == 32, "bre_material has no padding: the geometry cache compares its bytes");
 
 // One node of the scene's bounding volume hierarchy: the reference's BVHAccel LinearBVHNode
 // (src/accelerators/bvh.cpp, 32 B, depth-first order: an interior node's first child follows it).
@@ -200,6 +209,7 @@ struct DevScene {
     float grid_sigma_t, grid_inv_max;
     float w2m[16];            // WorldToMedium, row-major
     const float *density;     // device copy of the grid (nx*ny*nz)
+    const bre_material *mats; // the mirror / glass table a PTri::mat >= kMatTable refers to (device array)
 };
 
 // Host side of the scene: everything prepare_scene derives, in host memory; the context uploads
@@ -212,17 +222,27 @@ struct HostScene {
     std::vector<int32_t> light_tri;
     std::vector<DLight> dlights;
     std::vector<float> light_func, light_cdf;
+    std::vector<bre_material> mats;
     int depth = 0;  // deepest node of the BVH (root = 1)
+};
+
+// The context's specular materials (bre_set_materials): the table and the per-triangle index (-1: matte)
+struct MaterialMap {
+    const bre_material *mats = nullptr;
+    int n_mats = 0;
+    const int32_t *tri_mat = nullptr;  // one per scene triangle when n_mats > 0
 };
 
 // host: derive the per-triangle constants, the light distribution and the scene BVH exactly as
 // oracle/ora_pbrt.h make_scene does; `d_density` is the device copy of s->grid_density (grid media)
 void prepare_scene(const bre_scene *s, HostScene *out, const float *d_density = nullptr,
-                   const bre_light *lights = nullptr, int n_lights = 0);
+                   const bre_light *lights = nullptr, int n_lights = 0, const MaterialMap &mm = MaterialMap());
 // the two halves of prepare_scene: the triangles, lights and BVH (out->head's geometry fields and
 // the arrays), and the medium fields of a DevScene
-// (`lights`: the context's delta lights, each with order <= s->n_triangles)
-void prepare_geometry(const bre_scene *s, HostScene *out, const bre_light *lights = nullptr, int n_lights = 0);
+// (`lights`: the context's delta lights, each with order <= s->n_triangles; `mm`: its materials, the map
+// holding s->n_triangles entries)
+void prepare_geometry(const bre_scene *s, HostScene *out, const bre_light *lights = nullptr, int n_lights = 0,
+                      const MaterialMap &mm = MaterialMap());
 // a bre_light as the PointLight / SpotLight constructor leaves it
 DLight prepare_light(const bre_light &l);
 void prepare_medium(const bre_scene *s, DevScene *d, const float *d_density);
@@ -598,6 +618,84 @@ __device__ __forceinline__ bool medium_sample_any(const DevScene &S, Smp &smp, f
 BRE_TD bool black3(const float v[3]) { return v[0] == 0 && v[1] == 0 && v[2] == 0; }
 BRE_TD float lum3(const float v[3]) { return 0.212671f * v[0] + 0.715160f * v[1] + 0.072169f * v[2]; }
 
+// ---- the shading frame of a triangle's BSDF: WorldToLocal / LocalToWorld, reflection.h:437-446 ----
+BRE_TD f3 to_local(const PTri &q, f3 v) { return mk(dot3(v, q.ss), dot3(v, q.ts), dot3(v, q.n)); }
+BRE_TD f3 to_world(const PTri &q, f3 v) {
+    return mk(q.ss.x * v.x + q.ts.x * v.y + q.n.x * v.z, q.ss.y * v.x + q.ts.y * v.y + q.n.y * v.z,
+              q.ss.z * v.x + q.ts.z * v.y + q.n.z * v.z);
+}
+
+// ---- mirror and glass (src/materials/mirror.cpp, glass.cpp; one specular lobe each) ----
+// FrDielectric, reflection.cpp:47-68
+BRE_TD float fr_dielectric(float cos_i, float eta_i, float eta_t) {
+    cos_i = cos_i < -1.f ? -1.f : (cos_i > 1.f ? 1.f : cos_i);  // Clamp, pbrt.h:278-284
+    if (!(cos_i > 0.f)) {
+        const float x = eta_i;
+        eta_i = eta_t;
+        eta_t = x;
+        cos_i = fabsf(cos_i);
+    }
+    const float sin_i = sqrtf(smax(0.f, 1 - cos_i * cos_i));
+    const float sin_t = eta_i / eta_t * sin_i;
+    if (sin_t >= 1) return 1.f;
+    const float cos_t = sqrtf(smax(0.f, 1 - sin_t * sin_t));
+    const float r_parl = ((eta_t * cos_i) - (eta_i * cos_t)) / ((eta_t * cos_i) + (eta_i * cos_t));
+    const float r_perp = ((eta_i * cos_i) - (eta_t * cos_t)) / ((eta_i * cos_i) + (eta_t * cos_t));
+    return (r_parl * r_parl + r_perp * r_perp) / 2;
+}
+
+// BSDF::Sample_f (reflection.cpp:703-768) of a BSDF whose one BxDF is SpecularReflection(Kr, FresnelNoOp)
+// (mirror; Sample_f :136-143) or FresnelSpecular(Kr, Kt, 1, eta, mode) (glass; :477-511, with Refract of
+// reflection.h:96-108), called with BSDF_ALL.  wo and wi are in the shading frame, wi is not normalised;
+// u0 is u[0] (one matching component leaves it as it is: min(u[0] * 1 - 0, OneMinusEpsilon)).  Returns
+// false where Sample_f returns 0 (wo.z == 0, a failed Refract): pdf, f and type are then 0.
+BRE_TD bool specular_sample(const bre_material &m, f3 wo, float u0, int mode, f3 &wi, float &pdf, float f[3],
+                            int &type) {
+    f[0] = f[1] = f[2] = 0.f;
+    pdf = 0.f;
+    type = 0;
+    if (wo.z == 0) return false;
+    if (m.type == BRE_MATERIAL_MIRROR) {
+        wi = mk(-wo.x, -wo.y, wo.z);
+        pdf = 1.f;
+        type = kBsdfSpecular | kBsdfReflection;
+        const float ac = fabsf(wi.z);
+        for (int c = 0; c < 3; ++c) f[c] = (1.f * m.kr[c]) / ac;  // fresnel->Evaluate() * R / AbsCosTheta(wi)
+        return true;
+    }
+    const float F = fr_dielectric(wo.z, 1.f, m.eta);
+    if (u0 < F) {
+        wi = mk(-wo.x, -wo.y, wo.z);
+        pdf = F;
+        type = kBsdfSpecular | kBsdfReflection;
+        const float ac = fabsf(wi.z);
+        for (int c = 0; c < 3; ++c) f[c] = (m.kr[c] * F) / ac;
+        return true;
+    }
+    const bool entering = wo.z > 0;
+    const float eta_i = entering ? 1.f : m.eta, eta_t = entering ? m.eta : 1.f;
+    // Refract(wo, Faceforward(Normal3f(0, 0, 1), wo), etaI / etaT, wi)
+    const float eta = eta_i / eta_t;
+    const f3 n = (wo.z < 0.f) ? mk(-0.f, -0.f, -1.f) : mk(0.f, 0.f, 1.f);
+    const float cos_i = dot3(n, wo);
+    const float sin2_i = smax(0.f, 1 - cos_i * cos_i);
+    const float sin2_t = eta * eta * sin2_i;
+    if (sin2_t >= 1) return false;
+    const float cos_t = sqrtf(1 - sin2_t);
+    const float k = eta * cos_i - cos_t;
+    wi = mk(eta * -wo.x + k * n.x, eta * -wo.y + k * n.y, eta * -wo.z + k * n.z);
+    pdf = 1 - F;
+    if (pdf == 0) return false;  // BSDF::Sample_f's own test (F < 1 here: unreachable, kept as the text has it)
+    type = kBsdfSpecular | kBsdfTransmission;
+    const float ac = fabsf(wi.z);
+    for (int c = 0; c < 3; ++c) {
+        float ft = m.kt[c] * (1 - F);
+        if (mode == kModeRadiance) ft *= (eta_i * eta_i) / (eta_t * eta_t);
+        f[c] = ft / ac;
+    }
+    return true;
+}
+
 // ---- camera pass (bre_camera.hip) ----
 constexpr int kHaltonDims = 1000;  // HaltonSampler's PrimeTableSize = AwesomeSampler's limit (photonbeam.cpp:460)
 
@@ -630,6 +728,9 @@ hipError_t launch_camera_scan(void *tmp, size_t tmp_bytes, const CamSlots &s, in
                               int64_t *offs, hipStream_t stream, bool slot);
 hipError_t launch_camera_compact(const CamSlots &s, int64_t nslots, int max_depth, const int64_t *offs,
                                  const SegOut &out, int32_t *depth, hipStream_t stream);
+
+// bre_device_check kind 12 (bre_check.hip): specular_sample on n records of 6 floats, 6 words out each
+hipError_t launch_check_specular(int64_t n, const float *x, float *y, hipStream_t s);
 
 // dynamic LDS of a photon / camera launch: the scene traversal stack of every thread of a block
 inline size_t scene_stack_bytes(int stack_depth, int block) {

@@ -59,6 +59,22 @@ bre_status bre_pbrt_get_lights(const bre_pbrt *p, int32_t capacity, bre_light *o
     return BRE_OK;
 }
 
+bre_status bre_pbrt_get_materials(const bre_pbrt *p, int32_t mat_capacity, bre_material *materials,
+                                  int32_t *n_materials, int64_t tri_capacity, int32_t *triangle_material,
+                                  int64_t *n_triangles) {
+    if (!p || !p->ok || mat_capacity < 0 || tri_capacity < 0) return BRE_ERR_INVALID_ARG;
+    const int32_t nm = (int32_t)p->scene.materials.size();
+    const int64_t nt = (int64_t)p->scene.triangleMaterial.size();
+    if (n_materials) *n_materials = nm;
+    if (n_triangles) *n_triangles = nt;
+    const int32_t km = mat_capacity < nm ? mat_capacity : nm;
+    const int64_t kt = tri_capacity < nt ? tri_capacity : nt;
+    if ((km > 0 && !materials) || (kt > 0 && !triangle_material)) return BRE_ERR_INVALID_ARG;
+    for (int32_t i = 0; i < km; ++i) materials[i] = p->scene.materials[(size_t)i];
+    for (int64_t i = 0; i < kt; ++i) triangle_material[i] = p->scene.triangleMaterial[(size_t)i];
+    return BRE_OK;
+}
+
 bre_status bre_pbrt_make_spot_light(const float from[3], const float to[3], const float I[3], float coneangle,
                                     float conedeltaangle, const float *ctm, const float *ctm_inv, int32_t order,
                                     bre_light *out) {
@@ -131,7 +147,8 @@ bre_status bre_pbrt_render_devices(const bre_pbrt *p, const int32_t *devices, in
     PhotonBeamIntegrator integ(params_of(p, quick), film, std::vector<int>(devices, devices + n_devices));
     if (!integ.Context()) return BRE_ERR_NO_DEVICE;
     integ.writeFiles = write_files != 0;
-    if (!integ.Render(p->scene.scene, p->scene.lights)) return BRE_ERR_STATE;
+    if (!integ.Render(p->scene.scene, p->scene.lights, p->scene.materials, p->scene.triangleMaterial))
+        return BRE_ERR_STATE;
     if (image_rgb && !integ.Image().empty())
         memcpy(image_rgb, integ.Image().data(), integ.Image().size() * sizeof(float));
     return BRE_OK;

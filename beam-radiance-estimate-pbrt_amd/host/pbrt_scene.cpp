@@ -478,6 +478,10 @@ struct Material {
     float kd[3] = {0.5f, 0.5f, 0.5f};  // MatteMaterial "Kd" default 0.5 (materials/matte.cpp)
     float sigma = 0.f;
     bool none = false;
+    // "mirror" (MirrorMaterial, "Kr" default 0.9) and "glass" (GlassMaterial, "Kr" and "Kt" default 1, "eta" /
+    // "index" default 1.5, roughness 0): the bre_material of the shapes declared under it
+    float kr[3] = {1.f, 1.f, 1.f}, kt[3] = {1.f, 1.f, 1.f};
+    float eta = 1.5f;
 };
 
 struct GraphicsState {
@@ -500,6 +504,7 @@ struct MediumDef {
 struct ShapeRec {
     bre_triangle tri;
     std::string inside, outside;
+    int material = -1;  // index into PbrtScene::materials, -1: the triangle's matte kd
 };
 
 class Parser {
@@ -518,7 +523,9 @@ class Parser {
     void ReportUnused(const Lexer &lx, int line, const ParamSet &ps);
     void Shape(Lexer &lx, int line, const std::string &name, const ParamSet &ps);
     void MakeMedium(Lexer &lx, int line, const std::string &name, const ParamSet &ps);
-    void MakeMaterial(Lexer &lx, int line, const std::string &type, const ParamSet &ps, Material *m);
+    // `named`: from MakeNamedMaterial (the direct statement Material "glass" stays unsupported)
+    void MakeMaterial(Lexer &lx, int line, const std::string &type, const ParamSet &ps, Material *m, bool named);
+    int SpecularIndex(Lexer &lx, int line, const Material &m);
     void Camera(Lexer &lx, int line, const std::string &name, const ParamSet &ps);
     void Concat(const Xform &t) {
         ctm_ = ctm_ * t;
@@ -719,15 +726,62 @@ void Parser::Camera(Lexer &lx, int line, const std::string &name, const ParamSet
     out_->haveCamera = true;
 }
 
-void Parser::MakeMaterial(Lexer &lx, int line, const std::string &type, const ParamSet &ps, Material *m) {
+void Parser::MakeMaterial(Lexer &lx, int line, const std::string &type, const ParamSet &ps, Material *m, bool named) {
     *m = Material();
     m->type = type;
     if (type == "" || type == "none") {
         m->none = true;
         return;
     }
+    if (type == "mirror" || (type == "glass" && named)) {
+        // CreateMirrorMaterial (mirror.cpp:58-64), CreateGlassMaterial (glass.cpp:94-109)
+        const bool glass = type == "glass";
+        bool ok = true;
+        const auto spectrum = [&](const char *name, float *v, float d) {
+            v[0] = v[1] = v[2] = d;
+            if (ps.Has(name) && !ps.FindOneSpectrum(name, v)) {
+                Error(lx, line, "%s \"%s\" must be an rgb or xyz value (textures are not supported)", type.c_str(), name);
+                ok = false;
+            }
+        };
+        spectrum("Kr", m->kr, glass ? 1.f : 0.9f);
+        if (glass) {
+            spectrum("Kt", m->kt, 1.f);
+            for (const char *name : {"eta", "index", "uroughness", "vroughness"})
+                if (ps.Has(name) && !ps.FindFloats(name)) {
+                    Error(lx, line, "glass \"%s\" must be a float (textures are not supported)", name);
+                    ok = false;
+                }
+            m->eta = ps.Has("eta") ? ps.FindOneFloat("eta", 1.5f) : ps.FindOneFloat("index", 1.5f);
+            if (ps.FindOneFloat("uroughness", 0.f) != 0.f || ps.FindOneFloat("vroughness", 0.f) != 0.f) {
+                Error(lx, line, "glass \"uroughness\" / \"vroughness\" must be 0 (rough glass is not supported)");
+                ok = false;
+            }
+            ps.FindOneBool("remaproughness", true);
+            if (!(m->eta > 0.f) || !std::isfinite(m->eta)) {
+                Error(lx, line, "glass \"eta\" must be finite and > 0");
+                ok = false;
+            }
+        }
+        if (ps.Has("bumpmap")) {
+            Error(lx, line, "%s \"bumpmap\" is not supported by the GPU scene model", type.c_str());
+            ok = false;
+        }
+        ps.FindOneString("type", "");
+        if (ok) {
+            ReportUnused(lx, line, ps);
+            return;
+        }
+        Error(lx, line, "using \"matte\" in place of this \"%s\"", type.c_str());
+        *m = Material();
+        return;
+    }
     if (type != "matte") {
-        Error(lx, line, "Material \"%s\" is not supported (matte only); using \"matte\"", type.c_str());
+        if (type == "glass")
+            Error(lx, line, "Material \"glass\" is not supported as a direct statement; declare it with "
+                  "MakeNamedMaterial \"name\" \"string type\" \"glass\" and NamedMaterial \"name\"; using \"matte\"");
+        else
+            Error(lx, line, "Material \"%s\" is not supported (matte, mirror, named glass); using \"matte\"", type.c_str());
         m->type = "matte";
     }
     if (ps.Has("Kd") && !ps.FindOneSpectrum("Kd", m->kd))
@@ -736,6 +790,26 @@ void Parser::MakeMaterial(Lexer &lx, int line, const std::string &type, const Pa
     if (m->sigma != 0.f) Error(lx, line, "matte \"sigma\" must be 0 (Oren-Nayar is not supported)");
     ps.FindOneString("type", "");
     ReportUnused(lx, line, ps);
+}
+
+// The table entry of a mirror or glass material (-1 for matte): entries are shared by equal materials
+int Parser::SpecularIndex(Lexer &lx, int line, const Material &m) {
+    if (m.type != "mirror" && m.type != "glass") return -1;
+    bre_material b;
+    memset(&b, 0, sizeof(b));
+    b.type = m.type == "mirror" ? BRE_MATERIAL_MIRROR : BRE_MATERIAL_GLASS;
+    memcpy(b.kr, m.kr, sizeof(b.kr));
+    if (b.type == BRE_MATERIAL_GLASS) memcpy(b.kt, m.kt, sizeof(b.kt));
+    b.eta = b.type == BRE_MATERIAL_GLASS ? m.eta : 1.f;
+    std::vector<bre_material> &table = out_->materials;
+    for (size_t k = 0; k < table.size(); ++k)
+        if (memcmp(&table[k], &b, sizeof(b)) == 0) return (int)k;
+    if ((int)table.size() >= BRE_MAX_MATERIALS) {
+        Error(lx, line, "more than BRE_MAX_MATERIALS (%d) mirror / glass materials; using \"matte\"", BRE_MAX_MATERIALS);
+        return -1;
+    }
+    table.push_back(b);
+    return (int)table.size() - 1;
 }
 
 void Parser::MakeMedium(Lexer &lx, int line, const std::string &name, const ParamSet &ps) {
@@ -840,8 +914,10 @@ void Parser::Shape(Lexer &lx, int line, const std::string &name, const ParamSet 
               m[0][2] * (m[1][0] * m[2][1] - m[1][1] * m[2][0]);
     }
     const bool flip = gs_.reverseOrientation != (det < 0);
+    const int material = SpecularIndex(lx, line, mat);
     for (size_t t = 0; t < idx->size() / 3; ++t) {
         ShapeRec sr;
+        sr.material = material;
         memset(&sr.tri, 0, sizeof(sr.tri));
         for (int v = 0; v < 3; ++v) memcpy(sr.tri.p[v], &W[3 * (*idx)[3 * t + v]], 3 * sizeof(float));
         memcpy(sr.tri.kd, mat.kd, sizeof(sr.tri.kd));
@@ -1060,7 +1136,7 @@ bool Parser::Run(Lexer &lx, int depth) {
                 if (!inWorld_) Error(lx, line, "Shape not allowed outside WorldBegin/WorldEnd");
                 else Shape(lx, line, n, ps);
             } else if (w == "Material") {
-                MakeMaterial(lx, line, n, ps, &gs_.material);
+                MakeMaterial(lx, line, n, ps, &gs_.material, false);
                 gs_.namedMaterial.clear();
             } else if (w == "MakeNamedMaterial") {
                 const std::string type = ps.FindOneString("type", "");
@@ -1068,7 +1144,7 @@ bool Parser::Run(Lexer &lx, int depth) {
                     Error(lx, line, "No parameter string \"type\" found in MakeNamedMaterial");
                 } else {
                     Material m;
-                    MakeMaterial(lx, line, type, ps, &m);
+                    MakeMaterial(lx, line, type, ps, &m, true);
                     namedMaterials_[n] = m;
                 }
             } else if (w == "LightSource" && n == "spot") {
@@ -1170,6 +1246,9 @@ bool Parser::Finish() {
         o.triangles.resize(shapes_.size());
         for (size_t i = 0; i < shapes_.size(); ++i) o.triangles[i] = shapes_[i].tri;
     }
+    o.triangleMaterial.clear();
+    if (!o.materials.empty())
+        for (size_t i = 0; i < shapes_.size(); ++i) o.triangleMaterial.push_back(shapes_[i].material);
     if (med) {
         sc.has_medium = med->kind;
         memcpy(sc.sigma_a, med->sigma_a, sizeof(sc.sigma_a));

@@ -19,6 +19,11 @@
 //     ReverseOrientation ^ TransformSwapsHandedness); any number up to BRE_MAX_SCENE_TRIANGLES (more
 //     than BRE_MAX_TRIANGLES go through bre_scene.triangles_ext).
 //   * Material "matte" with "Kd" (rgb, default 0.5) and sigma 0; MakeNamedMaterial/NamedMaterial.
+//   * Material "mirror" ("Kr", default 0.9), and MakeNamedMaterial with "string type" "mirror" or "glass"
+//     ("Kr", "Kt" default 1; "eta", else "index", default 1.5; "uroughness" / "vroughness" must be 0): a
+//     bre_material in PbrtScene::materials, referred to by the triangles declared under it
+//     (PbrtScene::triangleMaterial).  "bumpmap" and texture-valued parameters are reported and the statement
+//     falls back to matte.  The direct statement Material "glass" is reported as unsupported.
 //   * AreaLightSource "diffuse" ("L" x "scale", one-sided): every triangle of an emitting mesh is
 //     its own light, as pbrtShape makes one DiffuseAreaLight per shape (api.cpp).
 //   * media: "homogeneous" or "heterogeneous" (GridDensityMedium); the scene model has ONE medium
@@ -114,6 +119,10 @@ struct PbrtScene {
     // Re-point scene.grid_density / scene.triangles_ext at this object's vectors (after a copy).
     void Bind();
     std::vector<bre_light> lights;    // LightSource "spot" statements, in declaration order (bre_set_lights)
+    // Material "mirror" and named "mirror" / "glass" materials in use (bre_set_materials): the table, and per
+    // scene triangle its index into it (-1: matte); both empty for a matte-only scene
+    std::vector<bre_material> materials;
+    std::vector<int32_t> triangleMaterial;
     FilmDesc film;
     std::string integratorName;       // "photonbeam" expected
     ParamSet integratorParams;        // CreatePhotonBeamIntegrator's ParamSet

@@ -197,10 +197,14 @@ int PhotonBeamIntegrator::OnImage(int32_t, const float *L, void *user) {
     return 0;
 }
 
-bool PhotonBeamIntegrator::Render(const bre_scene &scene, const std::vector<bre_light> &lights) {
+bool PhotonBeamIntegrator::Render(const bre_scene &scene, const std::vector<bre_light> &lights,
+                                  const std::vector<bre_material> &materials,
+                                  const std::vector<int32_t> &triangleMaterial) {
     if (!ctx_) return false;
     for (bre_ctx *c : ctxs_)
-        if (bre_set_lights(c, lights.data(), (int32_t)lights.size()) != BRE_OK) {
+        if (bre_set_lights(c, lights.data(), (int32_t)lights.size()) != BRE_OK ||
+            bre_set_materials(c, materials.data(), (int32_t)materials.size(), triangleMaterial.data(),
+                              (int64_t)triangleMaterial.size()) != BRE_OK) {
             err_ = bre_last_error(c);
             return false;
         }

@@ -16,14 +16,14 @@ import os
 import numpy as np
 
 from . import load_library
-from .scene import Light, RenderParams, Scene
+from .scene import Light, Material, RenderParams, Scene
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 HOST_LIB_PATH = os.path.join(HERE, "libbre_host.so")
 CLI_PATH = os.path.join(HERE, "host", "bre_pbrt")
 
 EXPORTS = ["bre_pbrt_parse_file", "bre_pbrt_parse_string", "bre_pbrt_free", "bre_pbrt_messages",
-           "bre_pbrt_get_scene", "bre_pbrt_get_lights", "bre_pbrt_make_spot_light", "bre_pbrt_get_render_params", "bre_pbrt_get_film", "bre_pbrt_render",
+           "bre_pbrt_get_scene", "bre_pbrt_get_lights", "bre_pbrt_get_materials", "bre_pbrt_make_spot_light", "bre_pbrt_get_render_params", "bre_pbrt_get_film", "bre_pbrt_render",
            "bre_pbrt_render_devices", "bre_film_finalize", "bre_write_pfm", "bre_read_pfm"]
 
 _HOST = None
@@ -46,6 +46,7 @@ def load_host_library(path: str = HOST_LIB_PATH) -> ctypes.CDLL:
     lib.bre_pbrt_messages.restype = ctypes.c_char_p
     lib.bre_pbrt_get_scene.argtypes = [P, P]
     lib.bre_pbrt_get_lights.argtypes = [P, I32, P, ctypes.POINTER(I32)]
+    lib.bre_pbrt_get_materials.argtypes = [P, I32, P, ctypes.POINTER(I32), I64, P, ctypes.POINTER(I64)]
     lib.bre_pbrt_make_spot_light.argtypes = [P, P, P, F, F, P, P, I32, P]
     lib.bre_pbrt_get_render_params.argtypes = [P, I32, P, ctypes.POINTER(I32)]
     lib.bre_pbrt_get_film.argtypes = [P, ctypes.POINTER(I32), ctypes.POINTER(I32), ctypes.POINTER(F),
@@ -87,6 +88,16 @@ class PbrtScene:
         assert self._lib.bre_pbrt_get_lights(self._h, n.value, arr, ctypes.byref(n)) == 0
         self.lights = [arr[i] for i in range(n.value)]  # LightSource "spot", for BeamGather.set_lights
         self._lights_ref = arr
+        # mirror / glass materials and the per-triangle index into them, for BeamGather.set_materials
+        nm, nt = ctypes.c_int32(), ctypes.c_int64()
+        assert self._lib.bre_pbrt_get_materials(self._h, 0, None, ctypes.byref(nm), 0, None, ctypes.byref(nt)) == 0
+        marr = (Material * max(nm.value, 1))()
+        tm = np.full(nt.value, -1, np.int32)
+        assert self._lib.bre_pbrt_get_materials(self._h, nm.value, marr, None, nt.value,
+                                                tm.ctypes.data if nt.value else None, None) == 0
+        self.materials = [marr[i] for i in range(nm.value)]
+        self.triangle_material = tm
+        self._materials_ref = marr
         self.params = RenderParams()
         wf = ctypes.c_int32()
         assert self._lib.bre_pbrt_get_render_params(self._h, int(quick), ctypes.byref(self.params), ctypes.byref(wf)) == 0

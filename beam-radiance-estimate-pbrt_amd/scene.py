@@ -70,6 +70,49 @@ def spot_light(frm, to, I, coneangle: float = 30.0, conedelta: float = 5.0, orde
     return make_spot_light(frm, to, I, coneangle, conedelta, order, ctm, ctm_inv)
 
 
+MATERIAL_MIRROR, MATERIAL_GLASS = 1, 2
+MAX_MATERIALS = 1024
+
+
+class Material(ctypes.Structure):
+    """bre_material: a MirrorMaterial or a GlassMaterial with zero roughness (32 bytes)."""
+    _fields_ = [("type", ctypes.c_int32), ("kr", F3), ("kt", F3), ("eta", ctypes.c_float)]
+
+    def to_bytes(self) -> bytes:
+        return ctypes.string_at(ctypes.addressof(self), ctypes.sizeof(self))
+
+
+def _rgb(v):
+    return F3(*([float(v)] * 3 if isinstance(v, (int, float)) else [float(x) for x in v]))
+
+
+def mirror(kr=0.9) -> Material:
+    """Material "mirror" (mirror.cpp:58-64): "Kr" (rgb or scalar, default 0.9)."""
+    return Material(MATERIAL_MIRROR, _rgb(kr), _rgb(0.0), 1.0)
+
+
+def glass(kr=1.0, kt=1.0, eta: float = 1.5) -> Material:
+    """Material "glass" with zero roughness (glass.cpp:94-109): "Kr", "Kt" (default 1), "eta" (1.5)."""
+    return Material(MATERIAL_GLASS, _rgb(kr), _rgb(kt), float(eta))
+
+
+def scene_materials(meshes):
+    """(materials, triangle_material) of `meshes` for BeamGather.set_materials: one table entry per
+    distinct Material object, in order of first use, and per triangle its index (-1: the mesh has no fifth
+    element, or None there)."""
+    table, index, tri = [], {}, []
+    for mesh in meshes:
+        m = mesh[4] if len(mesh) > 4 else None
+        k = -1
+        if m is not None:
+            if id(m) not in index:
+                index[id(m)] = len(table)
+                table.append(m)
+            k = index[id(m)]
+        tri += [k] * (len(mesh[1]) // 3)
+    return table, tri
+
+
 class RenderParams(ctypes.Structure):
     """bre_render_params: CreatePhotonBeamIntegrator's parameters (photonbeam.cpp:589-611)."""
     _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("iterations", ctypes.c_int32),
@@ -96,15 +139,17 @@ def make_scene(meshes, sigma_a=None, sigma_s=None, g=0.0,
     """meshes: list of (P, indices, kd, Le) -- a pbrt "trianglemesh" with world-space points P
     (list of xyz), index triples, Lambertian kd, and Le (None = not emitting); medium present iff
     sigma_a is given (RGB or scalar).  More than MAX_TRIANGLES triangles go to an external array
-    (Scene.triangles_ext, kept alive on the scene object)."""
+    (Scene.triangles_ext, kept alive on the scene object).  A mesh may carry a fifth element, its
+    Material (mirror / glass) or None: the struct does not hold it (scene_materials(meshes) returns
+    what BeamGather.set_materials takes)."""
     s = Scene()
     ctypes.memset(ctypes.addressof(s), 0, ctypes.sizeof(s))
-    total = sum(len(idx) // 3 for _, idx, _, _ in meshes)
+    total = sum(len(mesh[1]) // 3 for mesh in meshes)
     assert total <= MAX_SCENE_TRIANGLES
     ext = (Triangle * total)() if total > MAX_TRIANGLES else None
     dst = ext if ext is not None else s.triangles
     n = 0
-    for P, idx, kd, Le in meshes:
+    for P, idx, kd, Le in (mesh[:4] for mesh in meshes):
         assert len(idx) % 3 == 0
         for t in range(len(idx) // 3):
             T = dst[n]

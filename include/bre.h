@@ -284,6 +284,21 @@ bre_status bre_gather_sharded(bre_ctx *const *ctxs, int n_ctx, int64_t nseg, con
    (BRE_ERR_INVALID_ARG otherwise: their films are summed).  Needs no device. */
 bre_status bre_set_lights(bre_ctx *ctx, const bre_light *lights, int32_t n);
 
+/* ---- mirror and glass (bre_material, bre_scene.h) ----
+   Copies materials[0 .. n_materials) and triangle_material[0 .. n_triangles) into the context;
+   n_materials == 0 clears both.  triangle_material[i] is an index into `materials`, or -1 for triangle
+   i's own matte kd.  Sticky like bre_set_lights: every later pass and render of this context uses them,
+   for a scene with exactly n_triangles triangles (any other count is refused by the pass with
+   BRE_ERR_INVALID_ARG, where both are known).  Kr and Kt are clamped to [0, 1] (Spectrum::Clamp); kt is
+   ignored for a mirror; a mirror with black Kr, or a glass with black Kr and Kt, has no BxDF and absorbs
+   like a black kd.  BRE_ERR_INVALID_ARG (the message names the material, and the context's materials stay
+   as they were): a null array with a non-zero count, n_materials < 0 or > BRE_MAX_MATERIALS, n_triangles
+   < 0 or > BRE_MAX_SCENE_TRIANGLES, an unknown type, an index outside [-1, n_materials), a non-finite or
+   non-positive eta, a non-finite Kr or Kt.  Contexts of one sharded render must hold equal materials.
+   Needs no device. */
+bre_status bre_set_materials(bre_ctx *ctx, const bre_material *materials, int32_t n_materials,
+                             const int32_t *triangle_material, int64_t n_triangles);
+
 /* ---- photon pass (replaces photonbeam.cpp:362-437: emission, TracePhotonBeamRecursive and the
    merge into one beam vector, then the PhotonBeamBVH build of :438) ----
    Traces photons [0, n_photons) of `iteration` on the device (photon i uses PCG32 sequence
@@ -426,6 +441,11 @@ bre_status bre_resolve_image(int64_t npix, const float *ld_rgb, int iteration, f
              (nvalid int32), each sorted record's test box (6 floats: lo xyz, hi xyz), the nnodes Node
              records, the nleaf leaf_parent words (0 for a single leaf) and, where the build made them
              (kernels 0 and 4), the nnodes Node4 records.
+     kind 12: the passes' specular lobe (specular_sample, bre_trace.h: SpecularReflection::Sample_f and
+             FresnelSpecular::Sample_f inside BSDF::Sample_f) with Kr = Kt = 1.  x holds n / 6 records of 6
+             floats: wo in the shading frame (xyz), u[0], eta (0: a mirror), the transport mode (0:
+             Importance, 1: Radiance); y receives 6 words per record: wi in the shading frame (xyz), pdf,
+             the scalar f, and the sampled BxDFType as int32 (all zero where Sample_f returns 0).
    so the tests can hold them against the reference's own primitive tests (src/tests/fp_tests.cpp,
    find_interval.cpp), against the compiler's correctly rounded sqrt and division, and (kinds 10, 11)
    against a host restatement and validator of the hierarchy (tests/refpy_lbvh.py). */

@@ -46,6 +46,14 @@ bre_status bre_pbrt_get_scene(const bre_pbrt *p, bre_scene *out);
    bre_set_lights: at most `capacity` are written to `out`, *n (may be NULL) receives their number.
    bre_pbrt_render sets them on every context it makes. */
 bre_status bre_pbrt_get_lights(const bre_pbrt *p, int32_t capacity, bre_light *out, int32_t *n);
+/* The scene's mirror and glass materials (Material "mirror"; MakeNamedMaterial with "string type" "mirror"
+   or "glass") as a bre_material table, and per scene triangle its index into it (-1: matte), for
+   bre_set_materials.  At most mat_capacity table entries and tri_capacity map entries are written;
+   *n_materials and *n_triangles (may be NULL) receive the counts (n_materials 0: a matte-only scene).
+   bre_pbrt_render sets them on every context it makes. */
+bre_status bre_pbrt_get_materials(const bre_pbrt *p, int32_t mat_capacity, bre_material *materials,
+                                  int32_t *n_materials, int64_t tri_capacity, int32_t *triangle_material,
+                                  int64_t *n_triangles);
 /* A spot light as CreateSpotLight (src/lights/spot.cpp:104-124) builds it, by the code the parser uses:
    light_to_world = CTM * Translate(from) * Inverse(dirToZ), world_to_light the tracked inverse,
    cone_falloff_start_deg = coneangle - conedeltaangle.  I is "I" times "scale"; ctm is a row-major 4x4

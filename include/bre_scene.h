@@ -28,6 +28,14 @@
  *                       them with their Sample_Le, the camera pass lights surfaces with their Sample_Li
  *                       (no MIS, a shadow ray to the light's position); a scene lit only by them needs
  *                       no emitting triangle.
+ *   - mirror and glass (bre_material below; MirrorMaterial, src/materials/mirror.cpp, and GlassMaterial
+ *                       with zero roughness, src/materials/glass.cpp), set on the context with
+ *                       bre_set_materials as a table and a per-triangle index.  Both passes sample the one
+ *                       specular lobe (SpecularReflection::Sample_f, FresnelSpecular::Sample_f;
+ *                       reflection.cpp:136-143, 477-511): the photon pass in TransportMode::Importance,
+ *                       the camera pass in Radiance (the eta^2 factor), with isect.Le added after a
+ *                       specular bounce and no direct light on a specular vertex.  The medium fills the
+ *                       glass too (shapes carry no medium transition).
  *   - an optional medium filling all of space (every ray -- camera, photon, spawned -- travels
  *                       in it) with a Henyey-Greenstein phase function (src/core/medium.cpp:194-213):
  *                       BRE_MEDIUM_HOMOGENEOUS = HomogeneousMedium (src/media/homogeneous.cpp:44-77),
@@ -113,6 +121,22 @@ typedef struct bre_light {
                                    scene.lights the light comes before the area lights of the triangles
                                    with index >= order; lights of equal order keep their array order */
 } bre_light;
+
+/* Perfectly specular materials: pbrt's MirrorMaterial (src/materials/mirror.cpp: one SpecularReflection
+   with FresnelNoOp) and GlassMaterial with zero roughness (src/materials/glass.cpp: one FresnelSpecular
+   between index 1 outside and `eta` inside).  Like the lights they are not part of bre_scene: a context
+   holds a table of them and a per-triangle index into it (bre_set_materials, bre.h); a triangle mapped to
+   -1 keeps its own matte kd.  `emit` is independent of the material, as in pbrt. */
+#define BRE_MATERIAL_MIRROR 1
+#define BRE_MATERIAL_GLASS 2
+#define BRE_MAX_MATERIALS 1024 /* table entries accepted by bre_set_materials */
+
+typedef struct bre_material {
+    int32_t type; /* BRE_MATERIAL_MIRROR / BRE_MATERIAL_GLASS */
+    float kr[3];  /* "Kr", clamped to [0, 1] (Spectrum::Clamp); black = no reflection lobe */
+    float kt[3];  /* glass: "Kt", clamped to [0, 1]; ignored for a mirror */
+    float eta;    /* glass: "eta" / "index", finite and > 0 (also checked for a mirror, which ignores it) */
+} bre_material;   /* 32 bytes, no padding */
 
 /* PhotonBeamIntegrator parameters (CreatePhotonBeamIntegrator, photonbeam.cpp:589-611). */
 typedef struct bre_render_params {

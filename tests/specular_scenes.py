@@ -1,0 +1,117 @@
+"""The scenes of the mirror / glass tests (test infrastructure): name -> (scene.Scene, [scene.Light],
+[scene.Material], triangle_material).  Every scene has at most 40 triangles.
+
+mirror  the Cornell walls in fog, the floor a mirror with Kr 0.9, a point light
+prism   scenes/prism_fog.pbrt built by hand: the walls in the C1 fog, the oblique spot of spot_fog.pbrt, a closed
+        glass box (eta 1.5, outward normals) in the spot's shaft and a mirror quad on the floor beside it
+area    the Cornell box with its area light, a glass box, and a tilted mirror quad that faces the light and the
+        camera (isect.Le after a specular bounce; both EstimateDirect halves on a specular vertex)
+grid    prism in an 8^3 GridDensityMedium with g = 0.7 (a Tr draw too many would shift the sampler dimensions)
+black   three materials without a full lobe: a mirror with Kr 0 and a glass with Kr = Kt = 0 (no BxDF), and a glass
+        with Kt 0 only (reflects with probability F, otherwise the path ends)
+eta1    prism with eta 1: F is 0 up to a rounding residue, so every hit transmits, undeviated
+"""
+import functools
+import importlib
+
+import lights_scenes as ls
+
+NAMES = ("mirror", "prism", "area", "grid", "black", "eta1")
+CAMERA_NAMES = ("mirror", "prism", "area", "grid", "black")
+N_PHOTONS, MAX_DEPTH, RADIUS = 2000, 5, 0.01
+PHOTON_ITERATIONS, CAMERA_ITERATIONS = (0, 2), (0, 3)
+CAM_W = CAM_H = 24
+CAM_DEPTH = 5
+BOX_LO, BOX_HI = (0.37, 0.3, 0.47), (0.57, 0.5, 0.67)  # around the spot's axis at y = 0.4
+UNUSED_KD = (0.5, 0.5, 0.5)  # a triangle under a material never shows its kd; this is what the .pbrt parser leaves there
+
+
+def _sm():
+    return importlib.import_module("beam-radiance-estimate-pbrt_amd.scene")
+
+
+def box_mesh(lo, hi, material, kd=UNUSED_KD):
+    """A closed axis-aligned box as one mesh of 12 triangles whose normals point outward."""
+    (x0, y0, z0), (x1, y1, z1) = lo, hi
+    faces = [
+        [(x0, y1, z0), (x0, y1, z1), (x1, y1, z1), (x1, y1, z0)],  # +y
+        [(x0, y0, z0), (x1, y0, z0), (x1, y0, z1), (x0, y0, z1)],  # -y
+        [(x0, y0, z1), (x1, y0, z1), (x1, y1, z1), (x0, y1, z1)],  # +z
+        [(x0, y0, z0), (x0, y1, z0), (x1, y1, z0), (x1, y0, z0)],  # -z
+        [(x1, y0, z0), (x1, y1, z0), (x1, y1, z1), (x1, y0, z1)],  # +x
+        [(x0, y0, z0), (x0, y0, z1), (x0, y1, z1), (x0, y1, z0)],  # -x
+    ]
+    P, idx = [], []
+    for f in faces:
+        idx += [len(P) + k for k in (0, 1, 2, 0, 2, 3)]
+        P += f
+    return (P, tuple(idx), kd, None, material)
+
+
+def floor_mirror_quad(material):
+    """A quad just above the floor, normal up, where the spot's shaft lands beside the box."""
+    return ([(0.55, 0.002, 0.55), (0.55, 0.002, 0.9), (0.9, 0.002, 0.9), (0.9, 0.002, 0.55)], (0, 1, 2, 0, 2, 3), UNUSED_KD,
+            None, material)
+
+
+def meshes_of(name):
+    """(meshes with their fifth element, medium arguments, lights, grid)."""
+    sm = _sm()
+    walls = [m + (None,) for m in sm.cornell_meshes()[:-1]]
+    spot = sm.spot_light(ls.SPOT_FROM, ls.SPOT_TO, ls.SPOT_I, 30.0, 5.0, 0)
+    point = sm.point_light(ls.POINT_P, ls.POINT_I)
+    fog = (0.05, 0.5, 0.0)
+    if name == "mirror":
+        floor = walls[0][:4] + (sm.mirror(0.9),)
+        return [floor] + walls[1:], fog, [point], False
+    if name in ("prism", "grid", "eta1"):
+        glass = sm.glass(1.0, 1.0, 1.0 if name == "eta1" else 1.5)
+        meshes = walls + [box_mesh(BOX_LO, BOX_HI, glass), floor_mirror_quad(sm.mirror(0.9))]
+        if name == "grid":
+            return meshes, (0.5, 4.5, 0.7), [spot], True
+        return meshes, fog, [spot], False
+    if name == "area":
+        light = sm.cornell_meshes()[-1] + (None,)
+        # y - z = -0.6: the normal (0, 1, -1) / sqrt(2) faces the light above and the camera in front
+        tilted = ([(0.25, 0.15, 0.75), (0.25, 0.35, 0.95), (0.75, 0.35, 0.95), (0.75, 0.15, 0.75)], (0, 1, 2, 0, 2, 3),
+                  UNUSED_KD, None, sm.mirror(0.9))
+        box = box_mesh((0.12, 0.05, 0.35), (0.38, 0.31, 0.6), sm.glass(1.0, 1.0, 1.5))
+        return walls + [box, tilted, light], fog, [], False
+    if name == "black":
+        floor = walls[0][:4] + (sm.glass(1.0, 0.0, 1.5),)       # reflects with probability F, else ends
+        left = walls[4][:4] + (sm.mirror(0.0),)                  # no BxDF
+        right = walls[5][:4] + (sm.glass(0.0, 0.0, 1.5),)        # no BxDF
+        return [floor] + walls[1:4] + [left, right], fog, [point], False
+    raise KeyError(name)
+
+
+@functools.lru_cache(maxsize=None)
+def build(name):
+    sm = _sm()
+    meshes, (sa, ss, g), lights, grid = meshes_of(name)
+    scene = sm.make_scene(meshes, sa, ss, g)
+    if grid:
+        scene = sm.grid_medium(scene, ls.grid_density8(), 8)
+    materials, tri_mat = sm.scene_materials(meshes)
+    assert scene.n_triangles <= 40
+    return scene, lights, materials, tri_mat
+
+
+# The restatement is the slow side (seconds per pass): each reference is computed once per (scene, iteration)
+# and shared by every test of the session; the returned arrays are not to be modified.
+@functools.lru_cache(maxsize=None)
+def photon_ref(name, iteration):
+    import refpy_specular as rs
+
+    stats = rs.new_stats()
+    ref = rs.trace_photons(*build(name), N_PHOTONS, iteration, MAX_DEPTH, RADIUS, stats=stats)
+    return ref, stats
+
+
+@functools.lru_cache(maxsize=None)
+def camera_ref(name, iteration):
+    import refpy_specular as rs
+
+    stats = rs.new_stats()
+    ref = rs.camera_pass(*build(name), CAM_W, CAM_H, iteration, CAM_DEPTH, stats=stats)
+    return ref, stats
