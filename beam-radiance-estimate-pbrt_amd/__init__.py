@@ -28,6 +28,7 @@ OPT_COUNTERS, OPT_TIMING, OPT_KERNEL, OPT_LEAF_SIZE, OPT_SQRT_MODE, OPT_SPLIT, O
 OPT_SHARD_RANK, OPT_SHARD_COUNT, OPT_TILE_LEAF = 8, 9, 10
 OPT_CHUNK_LEN, OPT_CHUNK_LEAF, OPT_SORT_SEGMENTS, OPT_SHARD_BLOCK, OPT_SHARD_MODE = 11, 12, 13, 14, 15
 OPT_FILM_CLASSES, FILM_CLASSES = 16, 8
+OPT_SEGMENT_BUDGET = 17
 EMPTY_CHILD = -(2 ** 31)  # kEmptyChild (bre_device.h): no child
 # Node / Node4 (bre_device.h) as bre_device_check kinds 10 and 11 return them
 NODE_DTYPE = np.dtype([("lo", "<f4", (2, 3)), ("hi", "<f4", (2, 3)), ("child", "<i4", (2,)), ("parent", "<i4"),
@@ -45,6 +46,7 @@ EXPORTS = [
     "bre_render_progressive", "bre_shard_segments", "bre_set_beams_sharded", "bre_gather_sharded",
     "bre_device_check", "bre_resolve_classes", "bre_film_add", "bre_set_gather_after", "bre_set_gather_events",
     "bre_render_sharded", "bre_render_progressive_sharded", "bre_set_lights", "bre_set_materials",
+    "bre_set_media",
 ]
 # bre_image_fn: int on_image(int32 iteration, const float *image_rgb, void *user)
 IMAGE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_int32, ctypes.POINTER(ctypes.c_float), ctypes.c_void_p)
@@ -132,6 +134,9 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     if hasattr(lib, "bre_set_materials"):
         lib.bre_set_materials.argtypes = [P, P, I32, P, I64]
         lib.bre_set_materials.restype = I32
+    if hasattr(lib, "bre_set_media"):
+        lib.bre_set_media.argtypes = [P, P, I32, P, P, I64, I32, P, I32]
+        lib.bre_set_media.restype = I32
     lib.bre_get_beams.argtypes = [P, I64, P, P, P, P, ctypes.POINTER(I64)]
     lib.bre_get_beams.restype = I32
     lib.bre_scene_cornell.argtypes = [P, F, F, F]
@@ -354,6 +359,25 @@ class BeamGather:
         arr = (Material * max(len(materials), 1))(*materials)
         self._check(self.lib.bre_set_materials(self.h, arr if materials else None, len(materials),
                                                tm.ctypes.data if tm.size else None, tm.size))
+
+    # ---- media ----
+    def set_media(self, media=(), tri_inside=(), tri_outside=(), camera_medium: int = -1, light_medium=()):
+        """bre_set_media: the media table (scene.Medium: scene.medium_homogeneous, scene.medium_grid), each scene
+        triangle's (inside, outside) indices into it, the camera's medium and each delta light's (-1: vacuum), as
+        scene.scene_media returns them; used by every later pass and render of this context, whose scenes must
+        then have no medium of their own.  An empty table clears them."""
+        from .scene import Medium
+
+        media = list(media)
+        ti = np.ascontiguousarray(tri_inside, np.int32).reshape(-1)
+        to = np.ascontiguousarray(tri_outside, np.int32).reshape(-1)
+        if ti.size != to.size:
+            raise ValueError(f"set_media: {ti.size} inside and {to.size} outside indices")
+        lm = np.ascontiguousarray(light_medium, np.int32).reshape(-1)
+        arr = (Medium * max(len(media), 1))(*media)
+        self._check(self.lib.bre_set_media(self.h, arr if media else None, len(media),
+                                           ti.ctypes.data if ti.size else None, to.ctypes.data if to.size else None,
+                                           ti.size, int(camera_medium), lm.ctypes.data if lm.size else None, lm.size))
 
     # ---- photon pass ----
     def trace_photons(self, scene, n_photons: int, iteration: int = 0, max_depth: int = 5,

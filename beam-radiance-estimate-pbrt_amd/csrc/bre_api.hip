@@ -282,6 +282,10 @@ bre_status bre_set_option(bre_ctx *c, int option, int64_t value) {
             return fail(c, BRE_ERR_INVALID_ARG, "BRE_OPT_FILM_CLASSES must be 1 or %d", BRE_FILM_CLASSES);
         c->film_classes = (int)value;
         return BRE_OK;
+    case BRE_OPT_SEGMENT_BUDGET:  // camera pass with media: segment planes beyond maxdepth
+        if (value < 0 || value > 240) return fail(c, BRE_ERR_INVALID_ARG, "segment budget must be in 0..240");
+        c->seg_budget = (int)value;
+        return BRE_OK;
     case 102:  // internal: tile kernel register budget, min waves per SIMD (sweeps); default 6 with the lane ray
                // in registers (r2 final, 77 VGPRs; explore38)
         if (value != 1 && (value < 4 || value > 8))

@@ -3,6 +3,7 @@
 // bre_render* loops over them.
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstring>
 #include <vector>
 
@@ -49,6 +50,66 @@ bre_status check_scene(bre_ctx *c, const bre_scene *scene, const char *fn) {
     if (!c->mats.empty() && c->tri_mat.size() != (size_t)scene->n_triangles)
         return fail(c, BRE_ERR_INVALID_ARG, "%s: the material map (bre_set_materials) covers %lld triangles, the scene "
                     "has %d", fn, (long long)c->tri_mat.size(), scene->n_triangles);
+    if (c->media.empty()) {
+        if (c->has_interface)
+            return fail(c, BRE_ERR_INVALID_ARG, "%s: a BRE_MATERIAL_INTERFACE triangle needs the context's media "
+                        "(bre_set_media)", fn);
+        return BRE_OK;
+    }
+    // two sources of media would be ambiguous
+    if (scene->has_medium != BRE_MEDIUM_NONE)
+        return fail(c, BRE_ERR_INVALID_ARG, "%s: the context holds media (bre_set_media): the scene's has_medium must "
+                    "be BRE_MEDIUM_NONE", fn);
+    if (c->tri_med.size() != 2 * (size_t)scene->n_triangles)
+        return fail(c, BRE_ERR_INVALID_ARG, "%s: the media pairs (bre_set_media) cover %lld triangles, the scene has %d",
+                    fn, (long long)(c->tri_med.size() / 2), scene->n_triangles);
+    if (c->light_med.size() != c->lights.size())
+        return fail(c, BRE_ERR_INVALID_ARG, "%s: the media (bre_set_media) name %lld delta lights, the context holds "
+                    "%lld", fn, (long long)c->light_med.size(), (long long)c->lights.size());
+    return BRE_OK;
+}
+
+// The context's media on the device: the table with its grids behind one another, the pairs and the lights'
+// media.  Uploaded when bre_set_media changed them.
+bre_status upload_media(bre_ctx *c) {
+    if (!c->media_dirty) return BRE_OK;
+    std::vector<DevMedium> table(c->media.size());
+    std::vector<float> dens;
+    std::vector<size_t> first(c->media.size(), 0);
+    for (size_t k = 0; k < c->media.size(); ++k) {
+        const bre_medium &m = c->media[k];
+        DevMedium &d = table[k];
+        d = DevMedium{};
+        d.medium = m.type;
+        for (int j = 0; j < 3; ++j) d.sigma_t[j] = m.sigma_a[j] + m.sigma_s[j];  // HomogeneousMedium ctor
+        d.g = m.g;
+        if (m.type != BRE_MEDIUM_GRID) continue;
+        // GridDensityMedium ctor (grid.h:58-77): sigma_t = (sigma_a + sigma_s)[0]; invMaxDensity, std::max order
+        const std::vector<float> &g = c->media_grid[k];
+        float mx = 0;
+        for (float v : g) mx = std::max(mx, v);
+        for (int j = 0; j < 3; ++j) d.gn[j] = m.grid_n[j];
+        d.grid_sigma_t = m.sigma_a[0] + m.sigma_s[0];
+        d.grid_inv_max = 1 / mx;
+        for (int j = 0; j < 16; ++j) d.w2m[j] = m.world_to_medium[j];
+        first[k] = dens.size();
+        dens.insert(dens.end(), g.begin(), g.end());
+    }
+    float *dd = nullptr;
+    HIPCHK(c, c->md_dens.get(dens.size() + 1, &dd));
+    for (size_t k = 0; k < table.size(); ++k)
+        if (table[k].medium == BRE_MEDIUM_GRID) table[k].density = dd + first[k];
+    const auto up = [&](DevMem &m, const void *src, size_t bytes) -> hipError_t {
+        hipError_t e = m.ensure(bytes > 0 ? bytes : 4);
+        if (e != hipSuccess || bytes == 0) return e;
+        return hipMemcpyAsync(m.ptr, src, bytes, hipMemcpyHostToDevice, c->stream);
+    };
+    HIPCHK(c, up(c->md_dens, dens.data(), dens.size() * sizeof(float)));
+    HIPCHK(c, up(c->md_table, table.data(), table.size() * sizeof(DevMedium)));
+    HIPCHK(c, up(c->md_pairs, c->tri_med.data(), c->tri_med.size() * sizeof(int32_t)));
+    HIPCHK(c, up(c->md_light, c->light_med.data(), c->light_med.size() * sizeof(int32_t)));
+    HIPCHK(c, hipStreamSynchronize(c->stream));  // the host vectors go out of scope
+    c->media_dirty = false;
     return BRE_OK;
 }
 
@@ -162,6 +223,19 @@ bre_status upload_scene(bre_ctx *c, const bre_scene *scene) {
     DevScene ds;
     memcpy(&ds, &c->sc_head, sizeof(DevScene));  // padding bytes included: the record compares bytewise
     prepare_medium(scene, &ds, dd);
+    if (!c->media.empty()) {
+        BRE_TRY(upload_media(c));
+        ds.media = c->md_table.as<DevMedium>();
+        ds.tri_med = c->md_pairs.as<int32_t>();
+        ds.light_med = c->md_light.as<int32_t>();
+        ds.n_media = (int)c->media.size();
+        ds.cam_med = c->cam_med;
+    } else {
+        ds.media = nullptr;
+        ds.tri_med = ds.light_med = nullptr;
+        ds.n_media = 0;
+        ds.cam_med = -1;
+    }
     // the scene record is copied only when it changes: in a render every pass uploads the same record,
     // and a copy queued behind another context's gather waits for that gather's blocks (round 5 trace:
     // a 1.6 KB upload took 110 ms in the two-context pipeline)
@@ -238,6 +312,7 @@ bre_status bre_set_materials(bre_ctx *c, const bre_material *materials, int32_t 
     if (n_materials == 0) {
         c->mats.clear();
         c->tri_mat.clear();
+        c->has_interface = false;
         return BRE_OK;
     }
     if (n_triangles < 0 || n_triangles > BRE_MAX_SCENE_TRIANGLES)
@@ -246,10 +321,20 @@ bre_status bre_set_materials(bre_ctx *c, const bre_material *materials, int32_t 
     if (!materials || (n_triangles > 0 && !triangle_material))
         return fail(c, BRE_ERR_INVALID_ARG, "%s: null material table or triangle_material map", fn);
     std::vector<bre_material> mats(materials, materials + n_materials);
+    std::vector<char> is_interface((size_t)n_materials, 0);
     for (int k = 0; k < n_materials; ++k) {
         bre_material &m = mats[(size_t)k];
+        if (m.type == BRE_MATERIAL_INTERFACE && !c->media.empty()) {
+            // no BSDF: Kr, Kt and eta are ignored (kept as zeros, so that equal tables compare equal)
+            m = bre_material{};
+            m.type = BRE_MATERIAL_INTERFACE;
+            is_interface[(size_t)k] = 1;
+            continue;
+        }
+        // (an interface on a context without media is refused like an unknown type: bre_set_media comes first)
         if (m.type != BRE_MATERIAL_MIRROR && m.type != BRE_MATERIAL_GLASS)
-            return fail(c, BRE_ERR_INVALID_ARG, "%s: material %d has unknown type %d", fn, k, m.type);
+            return fail(c, BRE_ERR_INVALID_ARG, "%s: material %d has unknown type %d%s", fn, k, m.type,
+                        m.type == BRE_MATERIAL_INTERFACE ? " (BRE_MATERIAL_INTERFACE needs bre_set_media first)" : "");
         if (!std::isfinite(m.eta) || !(m.eta > 0))
             return fail(c, BRE_ERR_INVALID_ARG, "%s: material %d has eta %g (must be finite and > 0)", fn, k, m.eta);
         for (int j = 0; j < 3; ++j) {
@@ -267,6 +352,103 @@ bre_status bre_set_materials(bre_ctx *c, const bre_material *materials, int32_t 
                         (long long)i, triangle_material[i], n_materials);
     c->mats.swap(mats);
     c->tri_mat.assign(triangle_material, triangle_material + n_triangles);
+    c->has_interface = false;
+    for (int64_t i = 0; i < n_triangles; ++i)
+        if (triangle_material[i] >= 0 && is_interface[(size_t)triangle_material[i]]) c->has_interface = true;
+    return BRE_OK;
+}
+
+bre_status bre_set_media(bre_ctx *c, const bre_medium *media, int32_t n_media, const int32_t *tri_inside,
+                         const int32_t *tri_outside, int64_t n_triangles, int32_t camera_medium,
+                         const int32_t *light_medium, int32_t n_lights) {
+    if (!c) return BRE_ERR_INVALID_ARG;
+    const char *fn = "bre_set_media";
+    if (n_media < 0 || n_media > BRE_MAX_MEDIA)
+        return fail(c, BRE_ERR_INVALID_ARG, "%s: medium count must be in 0..%d", fn, BRE_MAX_MEDIA);
+    if (n_media == 0) {
+        c->media.clear();
+        c->media_grid.clear();
+        c->tri_med.clear();
+        c->light_med.clear();
+        c->media_key.clear();
+        c->cam_med = -1;
+        c->media_dirty = true;
+        return BRE_OK;
+    }
+    if (n_triangles < 0 || n_triangles > BRE_MAX_SCENE_TRIANGLES)
+        return fail(c, BRE_ERR_INVALID_ARG, "%s: the media pairs' triangle count must be in 0..%d", fn,
+                    BRE_MAX_SCENE_TRIANGLES);
+    if (n_lights < 0 || n_lights > BRE_MAX_LIGHTS)
+        return fail(c, BRE_ERR_INVALID_ARG, "%s: the light media count must be in 0..%d", fn, BRE_MAX_LIGHTS);
+    if (!media || (n_triangles > 0 && (!tri_inside || !tri_outside)) || (n_lights > 0 && !light_medium))
+        return fail(c, BRE_ERR_INVALID_ARG, "%s: null media table, triangle pair array or light media array", fn);
+    const auto index_ok = [&](int32_t v) { return v >= -1 && v < n_media; };
+    int64_t cells = 0;
+    for (int k = 0; k < n_media; ++k) {
+        const bre_medium &m = media[k];
+        if (m.type != BRE_MEDIUM_HOMOGENEOUS && m.type != BRE_MEDIUM_GRID)
+            return fail(c, BRE_ERR_INVALID_ARG, "%s: medium %d has unknown type %d", fn, k, m.type);
+        for (int j = 0; j < 3; ++j)
+            if (!std::isfinite(m.sigma_a[j]) || !std::isfinite(m.sigma_s[j]) || m.sigma_a[j] < 0 || m.sigma_s[j] < 0)
+                return fail(c, BRE_ERR_INVALID_ARG, "%s: medium %d has a non-finite or negative sigma", fn, k);
+        if (!std::isfinite(m.g) || std::fabs(m.g) > 1)
+            return fail(c, BRE_ERR_INVALID_ARG, "%s: medium %d has g %g (|g| must be <= 1)", fn, k, m.g);
+        if (m.type != BRE_MEDIUM_GRID) continue;
+        const float st0 = m.sigma_a[0] + m.sigma_s[0];
+        if (m.sigma_a[1] + m.sigma_s[1] != st0 || m.sigma_a[2] + m.sigma_s[2] != st0)
+            return fail(c, BRE_ERR_INVALID_ARG, "%s: grid medium %d: sigma_a + sigma_s must be spectrally uniform", fn, k);
+        const int64_t nx = m.grid_n[0], ny = m.grid_n[1], nz = m.grid_n[2];
+        if (nx < 1 || ny < 1 || nz < 1 || nx * ny * nz > BRE_MAX_GRID_CELLS || (cells += nx * ny * nz) > BRE_MAX_GRID_CELLS)
+            return fail(c, BRE_ERR_INVALID_ARG, "%s: grid medium %d: dimensions must be >= 1, with at most %d cells "
+                        "over the table", fn, k, BRE_MAX_GRID_CELLS);
+        if (!m.grid_density) return fail(c, BRE_ERR_INVALID_ARG, "%s: grid medium %d has a null density", fn, k);
+        float mx = 0;
+        for (int64_t i = 0; i < nx * ny * nz; ++i) mx = std::max(mx, m.grid_density[i]);
+        if (!(mx > 0) || !std::isfinite(mx))
+            return fail(c, BRE_ERR_INVALID_ARG, "%s: grid medium %d: the density maximum must be finite and > 0", fn, k);
+    }
+    for (int64_t i = 0; i < n_triangles; ++i)
+        if (!index_ok(tri_inside[i]) || !index_ok(tri_outside[i]))
+            return fail(c, BRE_ERR_INVALID_ARG, "%s: triangle %lld has a medium index outside [-1, %d)", fn, (long long)i,
+                        n_media);
+    if (!index_ok(camera_medium))
+        return fail(c, BRE_ERR_INVALID_ARG, "%s: the camera medium index %d is outside [-1, %d)", fn, camera_medium, n_media);
+    for (int j = 0; j < n_lights; ++j)
+        if (!index_ok(light_medium[j]))
+            return fail(c, BRE_ERR_INVALID_ARG, "%s: light %d has a medium index outside [-1, %d)", fn, j, n_media);
+    // accepted: copy everything, the grids included
+    std::vector<unsigned char> key;
+    const auto put = [&](const void *p, size_t bytes) {
+        const unsigned char *b = static_cast<const unsigned char *>(p);
+        key.insert(key.end(), b, b + bytes);
+    };
+    c->media.assign(media, media + n_media);
+    c->media_grid.assign((size_t)n_media, std::vector<float>());
+    for (int k = 0; k < n_media; ++k) {
+        bre_medium &m = c->media[(size_t)k];
+        m.reserved = 0;
+        if (m.type == BRE_MEDIUM_GRID) {
+            const size_t n = (size_t)m.grid_n[0] * m.grid_n[1] * m.grid_n[2];
+            c->media_grid[(size_t)k].assign(m.grid_density, m.grid_density + n);
+            m.grid_density = c->media_grid[(size_t)k].data();
+        } else {
+            m.grid_density = nullptr;
+        }
+        put(&m, offsetof(bre_medium, grid_density));
+        put(c->media_grid[(size_t)k].data(), c->media_grid[(size_t)k].size() * sizeof(float));
+    }
+    c->tri_med.resize(2 * (size_t)n_triangles);
+    for (int64_t i = 0; i < n_triangles; ++i) {
+        c->tri_med[2 * (size_t)i] = tri_inside[i];
+        c->tri_med[2 * (size_t)i + 1] = tri_outside[i];
+    }
+    c->light_med.assign(light_medium, light_medium + n_lights);
+    c->cam_med = camera_medium;
+    put(c->tri_med.data(), c->tri_med.size() * sizeof(int32_t));
+    put(c->light_med.data(), c->light_med.size() * sizeof(int32_t));
+    put(&camera_medium, sizeof(camera_medium));
+    c->media_key.swap(key);
+    c->media_dirty = true;
     return BRE_OK;
 }
 
@@ -295,6 +477,7 @@ bre_status bre_trace_photons(bre_ctx *c, const bre_scene *scene, int64_t n_photo
     const DevScene *ds = c->ph_scene.as<DevScene>();
     if (c->timing) HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
     const int sdepth = c->sc_head.stack_depth;
+    const bool media = !c->media.empty();
     // single-trace form (bre_photon.hip): `cap` beam slots per photon, scratch at most 2.5 GB (62 slots at
     // 1M photons: the re-trace of the photons with more beams than slots is the form's tail, 1.65 ms
     // with 16 slots vs 1.41 with 64 at C2, profiles/r4/run36); below 4 slots, or with option 116 = 0,
@@ -306,10 +489,10 @@ bre_status bre_trace_photons(bre_ctx *c, const bre_scene *scene, int64_t n_photo
     if (cap > 0) {
         HIPCHK(c, slots.ensure(N * (size_t)cap));
         HIPCHK(c, launch_photons(ds, sdepth, n_photons, seq0, max_depth, beam_radius, counts, nullptr, slots.out(), 2, cap,
-                                 c->stream));
+                                 media, c->stream));
     } else {
         HIPCHK(c, launch_photons(ds, sdepth, n_photons, seq0, max_depth, beam_radius, counts, nullptr, BeamOut{}, 0, 0,
-                                 c->stream));
+                                 media, c->stream));
     }
     HIPCHK(c, launch_count_scan(c->ph_tmp.ptr, c->ph_tmp.cap, counts, offsets, n_photons, c->stream,
                                 c->slot_passes != 0));
@@ -321,7 +504,7 @@ bre_status bre_trace_photons(bre_ctx *c, const bre_scene *scene, int64_t n_photo
             HIPCHK(c, launch_photon_slots(n_photons, cap, counts, offsets, slots.view(), in.out(), c->stream));
         // every photon (two-trace form), or only those with more beams than slots
         HIPCHK(c, launch_photons(ds, sdepth, n_photons, seq0, max_depth, beam_radius, counts, offsets, in.out(), 1, cap,
-                                 c->stream));
+                                 media, c->stream));
     }
     float photon_ms = 0.f;
     if (c->timing) {
@@ -369,7 +552,13 @@ bre_status bre_camera_pass(bre_ctx *c, const bre_scene *scene, int32_t width, in
         memcpy(&c->cam_scene, scene, sizeof(bre_scene));
     }
     const int64_t nslots = camera_slots(width, height);
-    const size_t S = (size_t)(nslots * max_depth);
+    // the slot planes: a segment's plane is its ordinal along the path, which passes the depth only where the
+    // path can cross an interface triangle; then BRE_OPT_SEGMENT_BUDGET more planes
+    const bool media = !c->media.empty();
+    const int planes = max_depth + (media && c->has_interface ? c->seg_budget : 0);
+    if (nslots * planes > (int64_t)INT32_MAX)
+        return fail(c, BRE_ERR_INVALID_ARG, "bre_camera_pass: the film is too large for %d segment planes", planes);
+    const size_t S = (size_t)(nslots * planes);
     int32_t *valid = nullptr, *depth = nullptr;
     int64_t *offs = nullptr;
     unsigned int *cam_flags = nullptr;
@@ -385,9 +574,9 @@ bre_status bre_camera_pass(bre_ctx *c, const bre_scene *scene, int32_t width, in
                             c->cam_perms.as<uint16_t>(),
                             width, height, iteration, max_depth, render_surfaces, render_media, cs, d_surface,
                             cam_flags, c->shard_rank, c->shard_count,
-                            c->shard_mode != 0 ? 0 : c->shard_block, c->film_classes, c->stream));
+                            c->shard_mode != 0 ? 0 : c->shard_block, c->film_classes, planes, media, c->stream));
     // exclusive scan of the slots' valid flags into cam_offs: total = offs[S-1] + valid[S-1]
-    HIPCHK(c, launch_camera_scan(c->cam_tmp.ptr, c->cam_tmp.cap, cs, nslots, max_depth, offs, c->stream,
+    HIPCHK(c, launch_camera_scan(c->cam_tmp.ptr, c->cam_tmp.cap, cs, nslots, planes, offs, c->stream,
                                  c->slot_passes != 0));
     int64_t last_off = 0;
     int32_t last_valid = 0;
@@ -395,11 +584,16 @@ bre_status bre_camera_pass(bre_ctx *c, const bre_scene *scene, int32_t width, in
     BRE_TRY(read_small(c, {{&last_off, offs + (S - 1), sizeof(int64_t)},
                            {&last_valid, valid + (S - 1), sizeof(int32_t)},
                            {&flags, cam_flags, sizeof(flags)}}));
+    if (flags & kCamFlagBudget) {
+        c->cam_nseg = 0;
+        return fail(c, BRE_ERR_STATE, "bre_camera_pass: a camera path crossed more medium interfaces than "
+                    "BRE_OPT_SEGMENT_BUDGET (%d) allows beyond maxdepth: no segments are kept", c->seg_budget);
+    }
     const int64_t n = last_off + last_valid;
     const size_t N = (size_t)(n > 0 ? n : 1);
     HIPCHK(c, c->seg.ensure(N));
     HIPCHK(c, c->seg_depth.get(N, &depth));
-    HIPCHK(c, launch_camera_compact(cs, nslots, max_depth, offs, c->seg.out(), depth, c->stream));
+    HIPCHK(c, launch_camera_compact(cs, nslots, planes, offs, c->seg.out(), depth, c->stream));
     float ms = 0.f;
     if (c->timing) {
         HIPCHK(c, hipEventRecord(c->ev[1], c->stream));

@@ -211,6 +211,9 @@ bre_status check_render_sharded(bre_ctx *const *ctxs, int n_ctx, const bre_scene
         if (ma.size() != mb.size() || ta != tb ||
             (!ma.empty() && memcmp(ma.data(), mb.data(), ma.size() * sizeof(bre_material)) != 0))
             return fail(ctxs[0], BRE_ERR_INVALID_ARG, "context %d: %s: its materials (bre_set_materials) differ from context 0's", i, fn);
+        // ... in the same media (bre_set_media): tables, grids, pairs, camera and light media
+        if (ctxs[0]->media_key != ctxs[i]->media_key)
+            return fail(ctxs[0], BRE_ERR_INVALID_ARG, "context %d: %s: its media (bre_set_media) differ from context 0's", i, fn);
     }
     if (!class_films(n_ctx) || !rp->render_media) return BRE_OK;
     for (int i = 0; i < n_ctx; ++i) {

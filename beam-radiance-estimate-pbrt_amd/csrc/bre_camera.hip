@@ -308,8 +308,12 @@ __device__ __forceinline__ float power_heuristic(float fpdf, float gpdf) {
 // Li = I * Falloff(-wi) / DistanceSquared(pLight, p); its shadow ray is SpawnRayTo an Interaction with
 // zero normal and zero error (interaction.h:73-78), so OffsetRayOrigin leaves pLight + 0; it has no MIS
 // weight and no BSDF-sampling half (IsDeltaLight, integrator.cpp:155, 167).
+// MED (bre_set_media): the shaded vertex lies on triangle `tri`, reached by a ray in medium `med`; the shadow
+// ray is VisibilityTester::Tr as a loop (light.cpp:63-81) and the BSDF-sampled ray Scene::IntersectTr
+// (scene.cpp:62-75): both step through interface triangles and multiply each segment's Tr in order.
+template <bool MED>
 __device__ void estimate_direct(const DevScene &S, HaltonDev &hs, f3 p, f3 perr, const PTri &q, f3 wo, int li,
-                                float usx, float usy, float ulx, float uly, float Ld[3]) {
+                                float usx, float usy, float ulx, float uly, float Ld[3], int tri, int med) {
     const bool delta = li < 0;
     const PTri &L = S.t[delta ? 0 : li];
     Ld[0] = Ld[1] = Ld[2] = 0.f;
@@ -360,12 +364,36 @@ __device__ void estimate_direct(const DevScene &S, HaltonDev &hs, f3 p, f3 perr,
         scat_pdf = bsdf_pdf(q, wo, wi);
         if (!black3(f)) {
             // VisibilityTester::Tr over Interaction::SpawnRayTo(pShape)
-            const f3 ro = offset_origin(p, perr, q.n, sub3(sp, p));
-            const f3 target = offset_origin(sp, ps.perr, ps.n, sub3(ro, sp));
-            const f3 rd = sub3(target, ro);
+            f3 ro = offset_origin(p, perr, q.n, sub3(sp, p));
+            f3 target = offset_origin(sp, ps.perr, ps.n, sub3(ro, sp));
+            f3 rd = sub3(target, ro);
             float tmax = 1 - 0.0001f;
             Hit h;
-            if (intersect_scene(S, ro, rd, tmax, h)) {
+            if constexpr (MED) {
+                int m = medium_towards(S, tri, q.n, rd, med);
+                float Tr[3] = {1.f, 1.f, 1.f};
+                while (true) {
+                    tmax = 1 - 0.0001f;
+                    const bool found = intersect_scene(S, ro, rd, tmax, h);
+                    if (found && S.t[h.tri].mat != kMatInterface) {  // before this segment's Tr draw
+                        Tr[0] = Tr[1] = Tr[2] = 0.f;
+                        break;
+                    }
+                    if (m >= 0) {
+                        float tr[3];
+                        medium_tr_any(S.media[m], hs, ro, rd, tmax, tr);
+                        for (int c = 0; c < 3; ++c) Tr[c] = Tr[c] * tr[c];
+                    }
+                    if (!found) break;
+                    // isect.SpawnRayTo(p1): a new offset origin, target and direction
+                    const f3 hn = S.t[h.tri].n;
+                    ro = offset_origin(h.p, h.perr, hn, sub3(sp, h.p));
+                    target = offset_origin(sp, ps.perr, ps.n, sub3(ro, sp));
+                    rd = sub3(target, ro);
+                    m = medium_towards(S, h.tri, hn, rd, m);
+                }
+                for (int c = 0; c < 3; ++c) Li[c] = Li[c] * Tr[c];
+            } else if (intersect_scene(S, ro, rd, tmax, h)) {
                 Li[0] = Li[1] = Li[2] = 0.f;  // every triangle has a material
             } else if (S.medium) {
                 float tr[3];
@@ -387,7 +415,7 @@ __device__ void estimate_direct(const DevScene &S, HaltonDev &hs, f3 p, f3 perr,
         for (int c = 0; c < 3; ++c) f[c] = f[c] * ad;
         if (!black3(f) && scat_pdf > 0) {
             // DiffuseAreaLight::Pdf_Li -> Shape::Pdf(ref, wi) (shape.cpp:72-87): this triangle alone
-            const f3 ro = offset_origin(p, perr, q.n, wi);
+            f3 ro = offset_origin(p, perr, q.n, wi);
             float tl;
             Hit hl;
             if (!intersect_tri(L, ro, wi, __builtin_huge_valf(), tl, hl)) return;
@@ -397,12 +425,30 @@ __device__ void estimate_direct(const DevScene &S, HaltonDev &hs, f3 p, f3 perr,
             const float wgt = power_heuristic(scat_pdf, light_pdf);
             float tmax = __builtin_huge_valf();
             Hit h;
-            const bool found = intersect_scene(S, ro, wi, tmax, h);
+            bool found;
             float tr[3] = {1.f, 1.f, 1.f};
-            if (S.medium) {
-                float t2[3];
-                medium_tr_any(S, hs, ro, wi, tmax, t2);
-                for (int c = 0; c < 3; ++c) tr[c] = tr[c] * t2[c];
+            if constexpr (MED) {
+                int m = medium_towards(S, tri, q.n, wi, med);  // it.SpawnRay(wi)
+                while (true) {
+                    tmax = __builtin_huge_valf();
+                    found = intersect_scene(S, ro, wi, tmax, h);
+                    if (m >= 0) {
+                        float t2[3];
+                        medium_tr_any(S.media[m], hs, ro, wi, tmax, t2);
+                        for (int c = 0; c < 3; ++c) tr[c] = tr[c] * t2[c];
+                    }
+                    if (!found || S.t[h.tri].mat != kMatInterface) break;
+                    const f3 hn = S.t[h.tri].n;
+                    ro = offset_origin(h.p, h.perr, hn, wi);  // isect->SpawnRay(ray.d)
+                    m = medium_towards(S, h.tri, hn, wi, m);
+                }
+            } else {
+                found = intersect_scene(S, ro, wi, tmax, h);
+                if (S.medium) {
+                    float t2[3];
+                    medium_tr_any(S, hs, ro, wi, tmax, t2);
+                    for (int c = 0; c < 3; ++c) tr[c] = tr[c] * t2[c];
+                }
             }
             // lightIsect.primitive->GetAreaLight() == &light: the same triangle, one-sided
             if (found && h.tri == li && dot3(L.n, neg3(wi)) > 0 && !black3(L.Le))
@@ -411,6 +457,10 @@ __device__ void estimate_direct(const DevScene &S, HaltonDev &hs, f3 p, f3 perr,
     }
 }
 
+// MED: the context holds media: the ray carries its medium, an interface triangle is passed through with the
+// depth not counted (:515-517), and a segment's slot plane is its ordinal along the path (`planes` of them)
+// instead of its depth.  MED false is the one-medium walk, the code it was before media.
+template <bool MED>
 __global__ __launch_bounds__(kCamBlock, 6) void k_camera(const DevScene *__restrict__ Sp, const DevCamera *__restrict__ Cp,
                                                      const uint16_t *__restrict__ perms, int iteration, int max_depth,
                                                      int render_surfaces, int render_media, int64_t nslots,
@@ -418,14 +468,15 @@ __global__ __launch_bounds__(kCamBlock, 6) void k_camera(const DevScene *__restr
                                                      float *__restrict__ sd, float *__restrict__ st,
                                                      int32_t *__restrict__ spix, int32_t *__restrict__ valid,
                                                      float *__restrict__ surface, unsigned int *__restrict__ flags,
-                                                     int shard_rank, int shard_count, int shard_block, int classes) {
+                                                     int shard_rank, int shard_count, int shard_block, int classes,
+                                                     int planes) {
     const DevScene &S = *Sp;
     const DevCamera &C = *Cp;
     const int64_t slot = (int64_t)blockIdx.x * kCamBlock + threadIdx.x;
     const int tiles_x = (C.width + 7) / 8;
     const int px = (int)(blockIdx.x % tiles_x) * 8 + (int)(threadIdx.x & 7);
     const int py = (int)(blockIdx.x / tiles_x) * 8 + (int)(threadIdx.x >> 3);
-    for (int dd = 0; dd < max_depth; ++dd) valid[dd * nslots + slot] = 0;
+    for (int dd = 0; dd < planes; ++dd) valid[dd * nslots + slot] = 0;
     if (px >= C.width || py >= C.height) return;
     // image-tile sharding: this context walks only the reference's 16x16 camera-pass tiles
     // (photonbeam.cpp:345-347, 444-452) of the blocks of shard_block x shard_block tiles whose
@@ -465,14 +516,22 @@ __global__ __launch_bounds__(kCamBlock, 6) void k_camera(const DevScene *__restr
     float beta[3] = {1.f, 1.f, 1.f};
     float Ld[3] = {0.f, 0.f, 0.f};
     bool specular_bounce = false;  // :478
+    int med = -1, ord = 0;         // MED: ray.medium, and the segments recorded so far
+    if constexpr (MED) med = S.cam_med;
     for (int depth = 0; depth < max_depth; ++depth) {
         float tmax = __builtin_huge_valf();
         Hit hit;
         if (!intersect_scene(S, o, d, tmax, hit)) break;  // area and delta lights: Le(ray) = 0
-        float mb[3] = {1.f, 1.f, 1.f};
-        if (S.medium) medium_tr_any(S, hs, o, d, tmax, mb);
+        float mb[3];
+        ray_medium_tr<MED>(S, med, hs, o, d, tmax, mb);
         if (render_media) {
-            const int64_t k = depth * nslots + slot;
+            if constexpr (MED) {
+                if (ord >= planes) {  // more interface crossings than the budget: reported, never dropped silently
+                    atomicOr(flags, kCamFlagBudget);
+                    break;
+                }
+            }
+            const int64_t k = (MED ? ord++ : depth) * nslots + slot;
             so[3 * k + 0] = o.x;
             so[3 * k + 1] = o.y;
             so[3 * k + 2] = o.z;
@@ -487,43 +546,52 @@ __global__ __launch_bounds__(kCamBlock, 6) void k_camera(const DevScene *__restr
             valid[k] = 1;
         }
         for (int c = 0; c < 3; ++c) beta[c] = beta[c] * mb[c];
-        if (!render_surfaces) break;
         const PTri &q = S.t[hit.tri];
-        const f3 wo = neg3(d);
-        // isect.Le(wo): the triangle's own area light, one-sided (diffuse.h:56-58), at the first vertex and
-        // after a mirror or glass bounce (:528-529)
-        if ((depth == 0 || specular_bounce) && q.emit && dot3(q.n, wo) > 0)
-            for (int c = 0; c < 3; ++c) Ld[c] = Ld[c] + beta[c] * q.Le[c];
-        // UniformSampleOneLight (integrator.cpp:54-82): light uniformly, uLight, uScattering
-        const int ln = min((int)(hs.get1d() * S.n_lights), S.n_lights - 1);
-        const float light_pdf = 1.f / (float)S.n_lights;  // Float(1) / nLights
-        float ulx, uly, usx, usy;
-        hs.get2d(ulx, uly);
-        hs.get2d(usx, usy);
-        float ed[3];
-        const int lt = S.light_tri[ln];
-        estimate_direct(S, hs, hit.p, hit.perr, q, normalize3(wo), lt, usx, usy, ulx, uly, ed);
-        for (int c = 0; c < 3; ++c) Ld[c] = Ld[c] + beta[c] * (ed[c] / light_pdf);
-        if (depth < max_depth - 1) {
-            float ux, uy, pdf = 0.f, f[3];
-            hs.get2d(ux, uy);
-            f3 wi;
-            int type = 0;  // the sampled BxDFType's specular bit; a Lambertian lobe has none
-            bool ok;
-            if (q.mat >= kMatTable) {
-                // mirror / glass: the one specular lobe, TransportMode::Radiance (:514)
-                f3 wil;
-                ok = specular_sample(S.mats[q.mat - kMatTable], to_local(q, wo), ux, kModeRadiance, wil, pdf, f, type);
-                if (ok) wi = to_world(q, wil);
-            } else {
-                ok = bsdf_sample(q, wo, ux, uy, wi, pdf, f);
+        if (MED && q.mat == kMatInterface) {
+            // no BSDF (:515-517): ray = isect.SpawnRay(ray.d); --depth -- no Le, no direct light, no Sample_f and
+            // no draw; the roulette below still runs
+            o = offset_origin(hit.p, hit.perr, q.n, d);
+            med = medium_towards(S, hit.tri, q.n, d, med);
+            --depth;
+        } else {
+            if (!render_surfaces) break;
+            const f3 wo = neg3(d);
+            // isect.Le(wo): the triangle's own area light, one-sided (diffuse.h:56-58), at the first vertex and
+            // after a mirror or glass bounce (:528-529)
+            if ((depth == 0 || specular_bounce) && q.emit && dot3(q.n, wo) > 0)
+                for (int c = 0; c < 3; ++c) Ld[c] = Ld[c] + beta[c] * q.Le[c];
+            // UniformSampleOneLight (integrator.cpp:54-82): light uniformly, uLight, uScattering
+            const int ln = min((int)(hs.get1d() * S.n_lights), S.n_lights - 1);
+            const float light_pdf = 1.f / (float)S.n_lights;  // Float(1) / nLights
+            float ulx, uly, usx, usy;
+            hs.get2d(ulx, uly);
+            hs.get2d(usx, usy);
+            float ed[3];
+            const int lt = S.light_tri[ln];
+            estimate_direct<MED>(S, hs, hit.p, hit.perr, q, normalize3(wo), lt, usx, usy, ulx, uly, ed, hit.tri, med);
+            for (int c = 0; c < 3; ++c) Ld[c] = Ld[c] + beta[c] * (ed[c] / light_pdf);
+            if (depth < max_depth - 1) {
+                float ux, uy, pdf = 0.f, f[3];
+                hs.get2d(ux, uy);
+                f3 wi;
+                int type = 0;  // the sampled BxDFType's specular bit; a Lambertian lobe has none
+                bool ok;
+                if (q.mat >= kMatTable) {
+                    // mirror / glass: the one specular lobe, TransportMode::Radiance (:514)
+                    f3 wil;
+                    ok = specular_sample(S.mats[q.mat - kMatTable], to_local(q, wo), ux, kModeRadiance, wil, pdf, f, type);
+                    if (ok) wi = to_world(q, wil);
+                } else {
+                    ok = bsdf_sample(q, wo, ux, uy, wi, pdf, f);
+                }
+                if (!ok || pdf == 0 || black3(f)) break;
+                specular_bounce = (type & kBsdfSpecular) != 0;  // :543
+                const float ad = fabsf(dot3(wi, q.n));
+                for (int c = 0; c < 3; ++c) beta[c] = beta[c] * (f[c] * ad / pdf);
+                o = offset_origin(hit.p, hit.perr, q.n, wi);
+                d = wi;
+                if constexpr (MED) med = medium_towards(S, hit.tri, q.n, wi, med);  // isect.SpawnRay(wi)
             }
-            if (!ok || pdf == 0 || black3(f)) break;
-            specular_bounce = (type & kBsdfSpecular) != 0;  // :543
-            const float ad = fabsf(dot3(wi, q.n));
-            for (int c = 0; c < 3; ++c) beta[c] = beta[c] * (f[c] * ad / pdf);
-            o = offset_origin(hit.p, hit.perr, q.n, wi);
-            d = wi;
         }
         const float y = lum3(beta);
         if (y < 0.25f) {
@@ -566,13 +634,17 @@ int64_t camera_slots(int width, int height) {
 hipError_t launch_camera(const DevScene *scene, int stack_depth, const DevCamera *cam, const uint16_t *perms, int width,
                          int height, int iteration, int max_depth, int render_surfaces, int render_media,
                          const CamSlots &s, float *surface, unsigned int *flags, int shard_rank, int shard_count,
-                         int shard_block, int classes, hipStream_t stream) {
+                         int shard_block, int classes, int planes, bool media, hipStream_t stream) {
     const int64_t nslots = camera_slots(width, height);
     if (nslots == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_camera, dim3((unsigned)(nslots / kCamBlock)), dim3(kCamBlock),
-                       scene_stack_bytes(stack_depth, kCamBlock), stream, scene, cam, perms,
-                       iteration, max_depth, render_surfaces, render_media, nslots, s.seg.o, s.seg.p, s.seg.d, s.seg.t, s.seg.pix,
-                       s.valid, surface, flags, shard_rank, shard_count, shard_block, classes < 1 ? 1 : classes);
+    const auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)(nslots / kCamBlock)), dim3(kCamBlock),
+                           scene_stack_bytes(stack_depth, kCamBlock), stream, scene, cam, perms, iteration, max_depth,
+                           render_surfaces, render_media, nslots, s.seg.o, s.seg.p, s.seg.d, s.seg.t, s.seg.pix,
+                           s.valid, surface, flags, shard_rank, shard_count, shard_block, classes < 1 ? 1 : classes,
+                           planes);
+    };
+    media ? go(k_camera<true>) : go(k_camera<false>);
     return hipGetLastError();
 }
 

@@ -225,6 +225,18 @@ struct bre_ctx {
     std::vector<bre_light> lights;          // bre_set_lights: the delta lights every pass adds to its scene
     std::vector<bre_material> mats;         // bre_set_materials: the mirror / glass table (Kr, Kt clamped) ...
     std::vector<int32_t> tri_mat;           // ... and each triangle's index into it (-1: its own matte kd)
+    bool has_interface = false;             // ... one of which leads to a BRE_MATERIAL_INTERFACE entry
+    // bre_set_media: the table (grid_density pointing into media_grid), each triangle's (inside, outside) pair
+    // interleaved, each delta light's medium and the camera's; media_key is all of it as bytes (the pointers
+    // left out, the grids in), which is what two contexts' media are compared by
+    std::vector<bre_medium> media;
+    std::vector<std::vector<float>> media_grid;
+    std::vector<int32_t> tri_med, light_med;
+    int cam_med = -1;
+    std::vector<unsigned char> media_key;
+    bool media_dirty = false;               // the device copies below are older than the state above
+    bre::DevMem md_table, md_pairs, md_light, md_dens;
+    int seg_budget = 16;                    // BRE_OPT_SEGMENT_BUDGET
     uint64_t sc_hash = 0;                   // hash of the uploaded triangles, lights and materials (0: none)
     std::vector<unsigned char> sc_bytes;    // the uploaded triangles' bytes, then the lights', the materials' and
                                             // the map's: a hash match is confirmed by memcmp

@@ -22,6 +22,7 @@
 #include <rocprim/device/device_scan.hpp>
 
 #include <algorithm>
+#include <type_traits>
 #include <vector>
 
 #include "bre_device.h"
@@ -140,6 +141,7 @@ void prepare_geometry(const bre_scene *s, HostScene *out, const bre_light *light
             const bre_material &m = mm.mats[mm.tri_mat[i]];
             const bool none = black3(m.kr) && (m.type == BRE_MATERIAL_MIRROR || black3(m.kt));
             T.mat = none ? kMatNone : kMatTable + mm.tri_mat[i];
+            if (m.type == BRE_MATERIAL_INTERFACE) T.mat = kMatInterface;  // GetMaterial() == nullptr: no BSDF
         }
         T.emit = t.emit != 0;
         if (T.emit) {
@@ -193,11 +195,18 @@ struct Frame {
     int depth;
     float beta[3];
 };
+// ... with media (bre_set_media): the parent resumes in its own medium
+struct FrameMed : Frame {
+    int med;
+};
 
 // MODE 0: count each photon's beams; 1: write them at offsets[i] + k (with over > 0: only the photons
 // whose count exceeds `over`, the single-trace form's overflow); 2: write the first `over` beams to
 // the photon's slots i * over + k and count them all.
-template <int MODE>
+// MED: the context holds media: the ray carries its medium (an index into S.media, -1 vacuum), taken by
+// GetMedium at every spawn, and an interface triangle is passed through (photonbeam.cpp:300-304).  MED false
+// is the one-medium walk, the code it was before media.
+template <int MODE, bool MED>
 __global__ __launch_bounds__(kPhotonBlock, 6) void k_photons(const DevScene *__restrict__ Sp, int64_t n, uint64_t seq0,
                                                           int max_depth, float radius, int32_t *__restrict__ counts,
                                                           const int64_t *__restrict__ offsets, float *__restrict__ bs,
@@ -224,6 +233,7 @@ __global__ __launch_bounds__(kPhotonBlock, 6) void k_photons(const DevScene *__r
     f3 o, d;
     float beta[3];
     bool alive;
+    int med = -1;  // MED: photonRay.medium
     if (lt >= 0) {
         const PTri &L = S.t[lt];
         const ShapeSample ps = sample_tri(L, u0x, u0y);
@@ -234,6 +244,8 @@ __global__ __launch_bounds__(kPhotonBlock, 6) void k_photons(const DevScene *__r
         coord_system(ps.n, v1, v2);
         d = add3(add3(scale3(v1, wl.x), scale3(v2, wl.y)), scale3(ps.n, wl.z));
         o = offset_origin(ps.p, ps.perr, ps.n, d);
+        // DiffuseAreaLight::Sample_Le: pShape.mediumInterface = mediumInterface, the ray is pShape.SpawnRay(w)
+        if constexpr (MED) med = dot3(d, ps.n) > 0 ? S.tri_med[2 * lt + 1] : S.tri_med[2 * lt];
         const bool front = dot3(ps.n, d) > 0;  // DiffuseAreaLight::L, one-sided
         alive = !(pdf_pos == 0 || pdf_dir == 0 || !front || black3(L.Le));
         if (alive) {
@@ -249,6 +261,7 @@ __global__ __launch_bounds__(kPhotonBlock, 6) void k_photons(const DevScene *__r
         float pdf_dir, fo;
         light_sample_le(D, u0x, u0y, d, pdf_dir, fo);
         o = D.p;
+        if constexpr (MED) med = S.light_med[~lt];  // Ray(pLight, w, Infinity, time, mediumInterface.inside)
         float Le[3];
         for (int c = 0; c < 3; ++c) Le[c] = D.I[c] * fo;
         alive = !(pdf_dir == 0 || black3(Le));
@@ -261,7 +274,7 @@ __global__ __launch_bounds__(kPhotonBlock, 6) void k_photons(const DevScene *__r
     }
 
     // ---- TracePhotonBeamRecursive as a state machine ----
-    Frame stk[BRE_MAX_DEPTH];
+    typename std::conditional<MED, FrameMed, Frame>::type stk[BRE_MAX_DEPTH];
     int sp = 0;
     int depth = 0;
     float tmax = 0;
@@ -276,7 +289,7 @@ __global__ __launch_bounds__(kPhotonBlock, 6) void k_photons(const DevScene *__r
             } else {
                 bool scattered = false;
                 float ts = 0;
-                if (S.medium) scattered = medium_sample_any(S, rng, o, d, tmax, ts);
+                scattered = ray_medium_sample<MED>(S, med, rng, o, d, tmax, ts);
                 if (black3(beta)) {
                     stop = true;
                 } else if (scattered) {
@@ -284,10 +297,12 @@ __global__ __launch_bounds__(kPhotonBlock, 6) void k_photons(const DevScene *__r
                     // beta * Tr(whole segment) (photonbeam.cpp:276-285)
                     float hx, hy;
                     pcg_2d(rng, hx, hy);
-                    const f3 wi = hg_sample(S.g, neg3(d), hx, hy);
+                    float g = S.g;
+                    if constexpr (MED) g = S.media[med].g;
+                    const f3 wi = hg_sample(g, neg3(d), hx, hy);
                     float tr[3];
-                    medium_tr_any(S, rng, o, d, tmax, tr);
-                    Frame &f = stk[sp++];
+                    ray_medium_tr<MED>(S, med, rng, o, d, tmax, tr);
+                    auto &f = stk[sp++];
                     f.o = o;
                     f.d = d;
                     f.tmax = tmax;
@@ -295,6 +310,7 @@ __global__ __launch_bounds__(kPhotonBlock, 6) void k_photons(const DevScene *__r
                     f.perr = hit.perr;
                     f.tri = hit.tri;
                     f.depth = depth;
+                    if constexpr (MED) f.med = med;  // the child stays in it too (MediumInterface(this))
                     for (int c = 0; c < 3; ++c) {
                         f.beta[c] = beta[c];
                         beta[c] = beta[c] * tr[c];
@@ -309,8 +325,8 @@ __global__ __launch_bounds__(kPhotonBlock, 6) void k_photons(const DevScene *__r
         if (!stop) {
             resume = false;
             // beam for the whole surface-hit segment, powerEnd = Tr * beta (:289-294)
-            float bm[3] = {1.f, 1.f, 1.f};
-            if (S.medium) medium_tr_any(S, rng, o, d, tmax, bm);
+            float bm[3];
+            ray_medium_tr<MED>(S, med, rng, o, d, tmax, bm);
             if (MODE == 1 || (MODE == 2 && cnt < over)) {
                 const int64_t k = w + cnt;
                 bs[3 * k + 0] = o.x;
@@ -323,6 +339,16 @@ __global__ __launch_bounds__(kPhotonBlock, 6) void k_photons(const DevScene *__r
                 for (int c = 0; c < 3; ++c) bp[3 * k + c] = bm[c] * beta[c];
             }
             ++cnt;
+            if constexpr (MED) {
+                // no BSDF (:300-304): --depth; photonRay = isect.SpawnRay(photonRay.d); continue -- before the
+                // Get2D, with beta as it was (not multiplied by the segment's Tr) and without roulette
+                const PTri &qi = S.t[hit.tri];
+                if (qi.mat == kMatInterface) {
+                    o = offset_origin(hit.p, hit.perr, qi.n, d);
+                    med = medium_towards(S, hit.tri, qi.n, d, med);
+                    continue;
+                }
+            }
             // surface scattering (:296-323): BSDF::Sample_f of the Lambertian lobe, or of a mirror's or
             // glass's specular lobe in TransportMode::Importance; the Get2D comes first either way
             float ux, uy;
@@ -357,6 +383,7 @@ __global__ __launch_bounds__(kPhotonBlock, 6) void k_photons(const DevScene *__r
                         for (int c = 0; c < 3; ++c) bn[c] = bm[c] * beta[c] * fr[c] * ad / pdf;
                         o = offset_origin(hit.p, hit.perr, q.n, wi);
                         d = wi;
+                        if constexpr (MED) med = medium_towards(S, hit.tri, q.n, wi, med);  // isect.SpawnRay(wi)
                         const float qrr = smax(0.f, 1 - lum3(bn) / lum3(beta));
                         if (pcg_float(rng) < qrr) {
                             stop = true;
@@ -371,7 +398,7 @@ __global__ __launch_bounds__(kPhotonBlock, 6) void k_photons(const DevScene *__r
         }
         // this path ends: resume the innermost suspended parent after its recursive call
         if (sp == 0) break;
-        const Frame &f = stk[--sp];
+        const auto &f = stk[--sp];
         o = f.o;
         d = f.d;
         tmax = f.tmax;
@@ -380,6 +407,7 @@ __global__ __launch_bounds__(kPhotonBlock, 6) void k_photons(const DevScene *__r
         hit.tri = f.tri;
         depth = f.depth;
         for (int c = 0; c < 3; ++c) beta[c] = f.beta[c];
+        if constexpr (MED) med = f.med;
         resume = true;
     }
     if (MODE != 1) counts[i] = cnt;
@@ -439,18 +467,16 @@ inline unsigned grid_of(int64_t n) { return (unsigned)((n + kPhotonBlock - 1) / 
 
 hipError_t launch_photons(const DevScene *scene, int stack_depth, int64_t n, uint64_t seq0, int max_depth,
                           float radius, int32_t *counts, const int64_t *offsets, const BeamOut &out, int mode,
-                          int over, hipStream_t s) {
+                          int over, bool media, hipStream_t s) {
     if (n == 0) return hipSuccess;
     const size_t lds = scene_stack_bytes(stack_depth, kPhotonBlock);
-    if (mode == 1)
-        hipLaunchKernelGGL(k_photons<1>, dim3(grid_of(n)), dim3(kPhotonBlock), lds, s, scene, n, seq0, max_depth,
-                           radius, counts, offsets, out.start, out.end, out.radius, out.power, over);
-    else if (mode == 2)
-        hipLaunchKernelGGL(k_photons<2>, dim3(grid_of(n)), dim3(kPhotonBlock), lds, s, scene, n, seq0, max_depth,
-                           radius, counts, offsets, out.start, out.end, out.radius, out.power, over);
-    else
-        hipLaunchKernelGGL(k_photons<0>, dim3(grid_of(n)), dim3(kPhotonBlock), lds, s, scene, n, seq0, max_depth,
-                           radius, counts, offsets, out.start, out.end, out.radius, out.power, 0);
+    const auto go = [&](auto kernel, int ov) {
+        hipLaunchKernelGGL(kernel, dim3(grid_of(n)), dim3(kPhotonBlock), lds, s, scene, n, seq0, max_depth, radius,
+                           counts, offsets, out.start, out.end, out.radius, out.power, ov);
+    };
+    if (mode == 1) media ? go(k_photons<1, true>, over) : go(k_photons<1, false>, over);
+    else if (mode == 2) media ? go(k_photons<2, true>, over) : go(k_photons<2, false>, over);
+    else media ? go(k_photons<0, true>, 0) : go(k_photons<0, false>, 0);
     return hipGetLastError();
 }
 

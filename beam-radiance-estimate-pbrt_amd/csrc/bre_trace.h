@@ -151,10 +151,11 @@ struct PTri {
     float kd[3], Le[3];
     float area;  // 0.5 * |cross(p1 - p0, p2 - p0)|
     int mat;     // kMatMatte: Lambertian kd; kMatNone: no BxDF (black kd, or a black mirror / glass);
-                 // kMatTable + k: entry k of DevScene::mats
+                 // kMatTable + k: entry k of DevScene::mats; kMatInterface: no BSDF
     int emit;    // a DiffuseAreaLight
 };
 constexpr int kMatMatte = 0, kMatNone = 1, kMatTable = 2;
+constexpr int kMatInterface = -1;  // BRE_MATERIAL_INTERFACE: no BSDF at all, the walks pass through
 
 // BxDFType bits (reflection.h:126-134) of the lobes sampled here
 constexpr int kBsdfReflection = 1, kBsdfTransmission = 2, kBsdfSpecular = 16;
@@ -187,6 +188,20 @@ struct DLight {
     int spot;                    // 1: SpotLight, 0: PointLight
 };
 
+// One entry of the context's media table (bre_medium as the HomogeneousMedium / GridDensityMedium
+// constructors leave it).  The medium fields carry DevScene's names, so the medium functions below take
+// either: the scene's one medium, or a table entry.
+static_assert(sizeof(bre_medium) == 120, "bre_medium has no padding: the pointer is part of the layout");
+struct DevMedium {
+    int medium;  // BRE_MEDIUM_HOMOGENEOUS / _GRID
+    float sigma_t[3];
+    float g;
+    int gn[3];
+    float grid_sigma_t, grid_inv_max;
+    float w2m[16];
+    const float *density;
+};
+
 struct DevScene {
     int n_tris, n_lights, medium, n_nodes;  // medium: BRE_MEDIUM_NONE / _HOMOGENEOUS / _GRID
     int stack_depth;                        // traversal stack entries per thread (the tree depth)
@@ -210,6 +225,12 @@ struct DevScene {
     float w2m[16];            // WorldToMedium, row-major
     const float *density;     // device copy of the grid (nx*ny*nz)
     const bre_material *mats; // the mirror / glass table a PTri::mat >= kMatTable refers to (device array)
+    // bre_set_media (null / 0 without): the table, per triangle its (inside, outside) pair of table indices
+    // (-1: vacuum), per delta light its medium, and the camera's
+    const DevMedium *media;
+    const int32_t *tri_med;    // 2 * n_tris
+    const int32_t *light_med;  // one per entry of dlights
+    int n_media, cam_med;
 };
 
 // Host side of the scene: everything prepare_scene derives, in host memory; the context uploads
@@ -457,7 +478,8 @@ BRE_TD void light_sample_le(const DLight &D, float u0, float u1, f3 &d, float &p
 __device__ __forceinline__ float smp_1d(Pcg &r) { return pcg_float(r); }
 
 // HomogeneousMedium::Tr, homogeneous.cpp:44-48
-__device__ __forceinline__ void medium_tr(const DevScene &S, f3 d, float tmax, float tr[3]) {
+template <class M>
+__device__ __forceinline__ void medium_tr(const M &S, f3 d, float tmax, float tr[3]) {
     const float x = smin(tmax * len3(d), kMaxFloat);
     // one expf per distinct argument (a grey medium's three channels share theirs: the same values)
     const float a0 = -S.sigma_t[0] * x, a1 = -S.sigma_t[1] * x, a2 = -S.sigma_t[2] * x;
@@ -467,8 +489,8 @@ __device__ __forceinline__ void medium_tr(const DevScene &S, f3 d, float tmax, f
 }
 
 // HomogeneousMedium::Sample distance part, homogeneous.cpp:50-60 (two draws)
-template <class Smp>
-__device__ __forceinline__ bool medium_sample(const DevScene &S, Smp &rng, f3 d, float tmax, float &t) {
+template <class M, class Smp>
+__device__ __forceinline__ bool medium_sample(const M &S, Smp &rng, f3 d, float tmax, float &t) {
     int ch = (int)(smp_1d(rng) * 3);
     ch = (2 < ch) ? 2 : ch;  // std::min(ch, 2)
     const float st = ch == 0 ? S.sigma_t[0] : (ch == 1 ? S.sigma_t[1] : S.sigma_t[2]);
@@ -481,13 +503,15 @@ __device__ __forceinline__ bool medium_sample(const DevScene &S, Smp &rng, f3 d,
 BRE_TD float lerp_ref(float t, float v1, float v2) { return (1 - t) * v1 + t * v2; }  // pbrt.h:391
 
 // GridDensityMedium::D, grid.h:84-88 (0 outside [0, n) per axis)
-__device__ __forceinline__ float grid_D(const DevScene &S, int x, int y, int z) {
+template <class M>
+__device__ __forceinline__ float grid_D(const M &S, int x, int y, int z) {
     if (!(x >= 0 && x < S.gn[0] && y >= 0 && y < S.gn[1] && z >= 0 && z < S.gn[2])) return 0.f;
     return S.density[((int64_t)z * S.gn[1] + y) * S.gn[0] + x];
 }
 
 // GridDensityMedium::Density, grid.cpp:46-60: trilinear over the sample lattice at cell centres
-__device__ __forceinline__ float grid_density(const DevScene &S, f3 p) {
+template <class M>
+__device__ __forceinline__ float grid_density(const M &S, f3 p) {
     const float sx = p.x * (float)S.gn[0] - .5f, sy = p.y * (float)S.gn[1] - .5f, sz = p.z * (float)S.gn[2] - .5f;
     const int ix = (int)floorf(sx), iy = (int)floorf(sy), iz = (int)floorf(sz);
     const float dx = sx - (float)ix, dy = sy - (float)iy, dz = sz - (float)iz;
@@ -503,7 +527,8 @@ __device__ __forceinline__ float grid_density(const DevScene &S, f3 p) {
 // WorldToMedium(Ray(o, Normalize(d), tMax * |d|)) (grid.cpp:66-67) through
 // Transform::operator()(Ray) (transform.h:251-264, point with error bound :278-299, vector :236-242),
 // then Bounds3f(0, 1)::IntersectP(ray, &t0, &t1) (geometry.h:1386-1408).  Returns false on a miss.
-__device__ __forceinline__ bool grid_ray(const DevScene &S, f3 o, f3 d, float tmax, f3 &mo, f3 &md, float &t0,
+template <class M>
+__device__ __forceinline__ bool grid_ray(const M &S, f3 o, f3 d, float tmax, f3 &mo, f3 &md, float &t0,
                                          float &t1) {
     const f3 dn = normalize3(d);
     const float tm = tmax * len3(d);
@@ -558,8 +583,8 @@ __device__ __forceinline__ bool grid_ray(const DevScene &S, f3 o, f3 d, float tm
 
 // GridDensityMedium::Sample, grid.cpp:62-89: delta tracking.  On an interaction, t is the
 // medium-space distance and the interaction point is rWorld(t) = o + d*t (as the reference).
-template <class Smp>
-__device__ __forceinline__ bool grid_sample(const DevScene &S, Smp &smp, f3 o, f3 d, float tmax, float &t_out) {
+template <class M, class Smp>
+__device__ __forceinline__ bool grid_sample(const M &S, Smp &smp, f3 o, f3 d, float tmax, float &t_out) {
     f3 mo, md;
     float tmin, tm;
     if (!grid_ray(S, o, d, tmax, mo, md, tmin, tm)) return false;
@@ -576,8 +601,8 @@ __device__ __forceinline__ bool grid_sample(const DevScene &S, Smp &smp, f3 o, f
 }
 
 // GridDensityMedium::Tr, grid.cpp:91-118: ratio tracking with Russian roulette below 0.1
-template <class Smp>
-__device__ __forceinline__ float grid_tr(const DevScene &S, Smp &smp, f3 o, f3 d, float tmax) {
+template <class M, class Smp>
+__device__ __forceinline__ float grid_tr(const M &S, Smp &smp, f3 o, f3 d, float tmax) {
     f3 mo, md;
     float tmin, tm;
     if (!grid_ray(S, o, d, tmax, mo, md, tmin, tm)) return 1.f;
@@ -598,8 +623,8 @@ __device__ __forceinline__ float grid_tr(const DevScene &S, Smp &smp, f3 o, f3 d
 }
 
 // Medium::Tr of the world ray (o, d, tmax) for either medium type
-template <class Smp>
-__device__ __forceinline__ void medium_tr_any(const DevScene &S, Smp &smp, f3 o, f3 d, float tmax, float tr[3]) {
+template <class M, class Smp>
+__device__ __forceinline__ void medium_tr_any(const M &S, Smp &smp, f3 o, f3 d, float tmax, float tr[3]) {
     if (S.medium == BRE_MEDIUM_GRID) {
         const float t = grid_tr(S, smp, o, d, tmax);
         tr[0] = tr[1] = tr[2] = t;
@@ -609,10 +634,38 @@ __device__ __forceinline__ void medium_tr_any(const DevScene &S, Smp &smp, f3 o,
 }
 
 // Medium::Sample distance decision; on true the interaction point is o + d*t
-template <class Smp>
-__device__ __forceinline__ bool medium_sample_any(const DevScene &S, Smp &smp, f3 o, f3 d, float tmax, float &t) {
+template <class M, class Smp>
+__device__ __forceinline__ bool medium_sample_any(const M &S, Smp &smp, f3 o, f3 d, float tmax, float &t) {
     if (S.medium == BRE_MEDIUM_GRID) return grid_sample(S, smp, o, d, tmax, t);
     return medium_sample(S, smp, d, tmax, t);
+}
+
+// ---- the medium a ray travels in.  MED false: the scene's one medium (S.medium), `med` unused.  MED true
+// (bre_set_media): entry `med` of S.media, or vacuum for -1: nothing is drawn and Tr = 1. ----
+template <bool MED, class Smp>
+__device__ __forceinline__ bool ray_medium_sample(const DevScene &S, int med, Smp &smp, f3 o, f3 d, float tmax,
+                                                  float &t) {
+    if constexpr (MED) return med >= 0 && medium_sample_any(S.media[med], smp, o, d, tmax, t);
+    else return S.medium && medium_sample_any(S, smp, o, d, tmax, t);
+}
+// tr = Tr of the segment (1 in vacuum)
+template <bool MED, class Smp>
+__device__ __forceinline__ void ray_medium_tr(const DevScene &S, int med, Smp &smp, f3 o, f3 d, float tmax,
+                                              float tr[3]) {
+    tr[0] = tr[1] = tr[2] = 1.f;
+    if constexpr (MED) {
+        if (med >= 0) medium_tr_any(S.media[med], smp, o, d, tmax, tr);
+    } else {
+        if (S.medium) medium_tr_any(S, smp, o, d, tmax, tr);
+    }
+}
+// Interaction::GetMedium(w) (interaction.h:86-88) at a point of triangle `tri` reached by a ray in medium
+// `med`: the triangle's pair when it is a transition, else the ray's medium on both sides
+// (GeometricPrimitive::Intersect, primitive.cpp:97-101)
+__device__ __forceinline__ int medium_towards(const DevScene &S, int tri, f3 n, f3 w, int med) {
+    const int in = S.tri_med[2 * tri], out = S.tri_med[2 * tri + 1];
+    if (in == out) return med;
+    return dot3(w, n) > 0 ? out : in;
 }
 
 BRE_TD bool black3(const float v[3]) { return v[0] == 0 && v[1] == 0 && v[2] == 0; }
@@ -719,10 +772,13 @@ struct CamSlots {
 
 void prepare_camera(const bre_scene *s, int width, int height, DevCamera *c, std::vector<uint16_t> *perms);
 int64_t camera_slots(int width, int height);
+// `planes`: the slot planes of `s` (max_depth, plus the segment budget with media and an interface triangle);
+// `media`: the context holds media (the kernel that carries a medium per ray)
 hipError_t launch_camera(const DevScene *scene, int stack_depth, const DevCamera *cam, const uint16_t *perms, int width,
                          int height, int iteration, int max_depth, int render_surfaces, int render_media,
                          const CamSlots &s, float *surface, unsigned int *flags, int shard_rank, int shard_count,
-                         int shard_block, int classes, hipStream_t stream);
+                         int shard_block, int classes, int planes, bool media, hipStream_t stream);
+constexpr unsigned int kCamFlagBudget = 1u;  // k_camera's flag word: a path overran its segment budget
 size_t camera_scan_temp_bytes(int64_t n);
 hipError_t launch_camera_scan(void *tmp, size_t tmp_bytes, const CamSlots &s, int64_t nslots, int max_depth,
                               int64_t *offs, hipStream_t stream, bool slot);
@@ -740,9 +796,10 @@ inline size_t scene_stack_bytes(int stack_depth, int block) {
 // photon pass launchers (bre_photon.hip)
 // mode 0: count beams per photon; 1: write them at offsets (over > 0: only photons with more than `over`
 // beams); 2: write the first `over` beams to per-photon slots and count them all (single-trace form)
+// `media`: the context holds media (the kernels that carry a medium per ray)
 hipError_t launch_photons(const DevScene *scene, int stack_depth, int64_t n, uint64_t seq0, int max_depth,
                           float radius, int32_t *counts, const int64_t *offsets, const BeamOut &out, int mode,
-                          int over, hipStream_t s);
+                          int over, bool media, hipStream_t s);
 // the single-trace form's copy of each photon's slots to its offsets
 hipError_t launch_photon_slots(int64_t n, int cap, const int32_t *counts, const int64_t *offsets,
                                const BeamView &slots, const BeamOut &out, hipStream_t s);

@@ -20,19 +20,25 @@ static bre_status finish_parse(bre_pbrt *p, bool ok) {
 
 extern "C" {
 
-bre_status bre_pbrt_parse_file(const char *path, bre_pbrt **out) {
+static_assert(BRE_PBRT_MEDIA == kParseMedia, "the ABI's flag is the parser's");
+
+bre_status bre_pbrt_parse_file_ex(const char *path, int32_t flags, bre_pbrt **out) {
     if (!out) return BRE_ERR_INVALID_ARG;
     *out = new bre_pbrt();
-    if (!path) return BRE_ERR_INVALID_ARG;
-    return finish_parse(*out, ParsePbrtFile(path, &(*out)->scene));
+    if (!path || (flags & ~BRE_PBRT_MEDIA)) return BRE_ERR_INVALID_ARG;
+    return finish_parse(*out, ParsePbrtFile(path, &(*out)->scene, flags));
 }
 
-bre_status bre_pbrt_parse_string(const char *text, bre_pbrt **out) {
+bre_status bre_pbrt_parse_string_ex(const char *text, int32_t flags, bre_pbrt **out) {
     if (!out) return BRE_ERR_INVALID_ARG;
     *out = new bre_pbrt();
-    if (!text) return BRE_ERR_INVALID_ARG;
-    return finish_parse(*out, ParsePbrtString(text, &(*out)->scene));
+    if (!text || (flags & ~BRE_PBRT_MEDIA)) return BRE_ERR_INVALID_ARG;
+    return finish_parse(*out, ParsePbrtString(text, &(*out)->scene, flags));
 }
+
+bre_status bre_pbrt_parse_file(const char *path, bre_pbrt **out) { return bre_pbrt_parse_file_ex(path, 0, out); }
+
+bre_status bre_pbrt_parse_string(const char *text, bre_pbrt **out) { return bre_pbrt_parse_string_ex(text, 0, out); }
 
 void bre_pbrt_free(bre_pbrt *p) { delete p; }
 
@@ -72,6 +78,30 @@ bre_status bre_pbrt_get_materials(const bre_pbrt *p, int32_t mat_capacity, bre_m
     if ((km > 0 && !materials) || (kt > 0 && !triangle_material)) return BRE_ERR_INVALID_ARG;
     for (int32_t i = 0; i < km; ++i) materials[i] = p->scene.materials[(size_t)i];
     for (int64_t i = 0; i < kt; ++i) triangle_material[i] = p->scene.triangleMaterial[(size_t)i];
+    return BRE_OK;
+}
+
+bre_status bre_pbrt_get_media(const bre_pbrt *p, int32_t med_capacity, bre_medium *media, int32_t *n_media,
+                              int64_t tri_capacity, int32_t *tri_inside, int32_t *tri_outside, int64_t *n_triangles,
+                              int32_t *camera_medium, int32_t light_capacity, int32_t *light_medium, int32_t *n_lights) {
+    if (!p || !p->ok || med_capacity < 0 || tri_capacity < 0 || light_capacity < 0) return BRE_ERR_INVALID_ARG;
+    const SceneMedia &sm = p->scene.media;
+    const int32_t nm = (int32_t)sm.media.size(), nl = (int32_t)sm.lightMedium.size();
+    const int64_t nt = (int64_t)sm.triInside.size();
+    if (n_media) *n_media = nm;
+    if (n_triangles) *n_triangles = nt;
+    if (n_lights) *n_lights = nl;
+    if (camera_medium) *camera_medium = sm.cameraMedium;
+    const int32_t km = med_capacity < nm ? med_capacity : nm, kl = light_capacity < nl ? light_capacity : nl;
+    const int64_t kt = tri_capacity < nt ? tri_capacity : nt;
+    if ((km > 0 && !media) || (kt > 0 && (!tri_inside || !tri_outside)) || (kl > 0 && !light_medium))
+        return BRE_ERR_INVALID_ARG;
+    for (int32_t i = 0; i < km; ++i) media[i] = sm.media[(size_t)i];
+    for (int64_t i = 0; i < kt; ++i) {
+        tri_inside[i] = sm.triInside[(size_t)i];
+        tri_outside[i] = sm.triOutside[(size_t)i];
+    }
+    for (int32_t i = 0; i < kl; ++i) light_medium[i] = sm.lightMedium[(size_t)i];
     return BRE_OK;
 }
 
@@ -147,7 +177,7 @@ bre_status bre_pbrt_render_devices(const bre_pbrt *p, const int32_t *devices, in
     PhotonBeamIntegrator integ(params_of(p, quick), film, std::vector<int>(devices, devices + n_devices));
     if (!integ.Context()) return BRE_ERR_NO_DEVICE;
     integ.writeFiles = write_files != 0;
-    if (!integ.Render(p->scene.scene, p->scene.lights, p->scene.materials, p->scene.triangleMaterial))
+    if (!integ.Render(p->scene.scene, p->scene.lights, p->scene.materials, p->scene.triangleMaterial, &p->scene.media))
         return BRE_ERR_STATE;
     if (image_rgb && !integ.Image().empty())
         memcpy(image_rgb, integ.Image().data(), integ.Image().size() * sizeof(float));

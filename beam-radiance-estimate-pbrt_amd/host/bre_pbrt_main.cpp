@@ -1,6 +1,7 @@
 // bre_pbrt_main.cpp — `bre_pbrt scene.pbrt`: the pbrt command line for scenes whose Integrator
 // is "photonbeam" (src/main/pbrt.cpp: parse, WorldEnd -> Render, film written by the integrator),
-// with the render on an MI355X.  Options: --quick, --outfile FILE, --device N, --devices A,B,... (the
+// with the render on an MI355X.  Options: --quick, --outfile FILE, --media (media bounded by surfaces:
+// MediumInterface on shapes and lights, Material "none" boundaries), --device N, --devices A,B,... (the
 // render split over several GPUs, one context per entry; a repeated ordinal is allowed); pbrt's
 // --nthreads is accepted and ignored.  Without --devices, a BRE_DEVICES environment value naming more
 // than one device selects them.  Exit status 0 on success.
@@ -14,7 +15,7 @@
 #include "../../include/bre_pbrt.h"
 
 static const char *kUsage =
-    "usage: bre_pbrt [--quick] [--outfile file.pfm] [--device n | --devices a,b,...] scene.pbrt\n";
+    "usage: bre_pbrt [--quick] [--media] [--outfile file.pfm] [--device n | --devices a,b,...] scene.pbrt\n";
 
 // "0,1,2,3" -> ordinals; empty when the text is not a comma-separated list of non-negative integers
 static std::vector<int32_t> ParseDevices(const char *text) {
@@ -31,10 +32,11 @@ static std::vector<int32_t> ParseDevices(const char *text) {
 
 int main(int argc, char **argv) {
     const char *scene = nullptr, *outfile = nullptr;
-    int quick = 0, device = 0;
+    int quick = 0, device = 0, flags = 0;
     std::vector<int32_t> devices;
     for (int i = 1; i < argc; ++i) {
         if (!strcmp(argv[i], "--quick")) quick = 1;
+        else if (!strcmp(argv[i], "--media")) flags |= BRE_PBRT_MEDIA;
         else if (!strcmp(argv[i], "--outfile") && i + 1 < argc) outfile = argv[++i];
         else if (!strcmp(argv[i], "--device") && i + 1 < argc) device = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--devices") && i + 1 < argc) {
@@ -59,7 +61,7 @@ int main(int argc, char **argv) {
         if (env.size() > 1) devices = env;
     }
     bre_pbrt *p = nullptr;
-    const bre_status st = bre_pbrt_parse_file(scene, &p);
+    const bre_status st = bre_pbrt_parse_file_ex(scene, flags, &p);
     int ne = 0, nw = 0;
     fputs(bre_pbrt_messages(p, &ne, &nw), stderr);
     if (st != BRE_OK) {

@@ -509,7 +509,7 @@ struct ShapeRec {
 
 class Parser {
   public:
-    explicit Parser(PbrtScene *out) : out_(out) {}
+    Parser(PbrtScene *out, int flags) : out_(out), mediaOk_((flags & kParseMedia) != 0) {}
 
     bool Run(Lexer &lx, int depth);
     bool Finish();
@@ -532,7 +532,10 @@ class Parser {
         ctmKind_ = 2;
     }
 
+    bool FinishMedia(const std::string &cameraMedium);
+
     PbrtScene *out_;
+    bool mediaOk_;  // kParseMedia
     Xform ctm_ = Xform::Identity();
     int ctmKind_ = 0;  // 0 identity, 1 exactly one LookAt, 2 anything else
     float lookAt_[9] = {0, 0, 0, 0, 0, 1, 0, 1, 0};
@@ -794,13 +797,17 @@ void Parser::MakeMaterial(Lexer &lx, int line, const std::string &type, const Pa
 
 // The table entry of a mirror or glass material (-1 for matte): entries are shared by equal materials
 int Parser::SpecularIndex(Lexer &lx, int line, const Material &m) {
-    if (m.type != "mirror" && m.type != "glass") return -1;
+    if (m.type != "mirror" && m.type != "glass" && !m.none) return -1;
     bre_material b;
     memset(&b, 0, sizeof(b));
-    b.type = m.type == "mirror" ? BRE_MATERIAL_MIRROR : BRE_MATERIAL_GLASS;
-    memcpy(b.kr, m.kr, sizeof(b.kr));
-    if (b.type == BRE_MATERIAL_GLASS) memcpy(b.kt, m.kt, sizeof(b.kt));
-    b.eta = b.type == BRE_MATERIAL_GLASS ? m.eta : 1.f;
+    if (m.none) {
+        b.type = BRE_MATERIAL_INTERFACE;  // Material "" / "none": no BSDF (kParseMedia)
+    } else {
+        b.type = m.type == "mirror" ? BRE_MATERIAL_MIRROR : BRE_MATERIAL_GLASS;
+        memcpy(b.kr, m.kr, sizeof(b.kr));
+        if (b.type == BRE_MATERIAL_GLASS) memcpy(b.kt, m.kt, sizeof(b.kt));
+        b.eta = b.type == BRE_MATERIAL_GLASS ? m.eta : 1.f;
+    }
     std::vector<bre_material> &table = out_->materials;
     for (size_t k = 0; k < table.size(); ++k)
         if (memcmp(&table[k], &b, sizeof(b)) == 0) return (int)k;
@@ -898,7 +905,7 @@ void Parser::Shape(Lexer &lx, int line, const std::string &name, const ParamSet 
             mat = Material();
         }
     }
-    if (mat.none) {
+    if (mat.none && !mediaOk_) {
         Error(lx, line, "shapes without a material (medium boundaries) are not supported by the GPU scene model");
         return;
     }
@@ -1221,10 +1228,14 @@ bool Parser::Finish() {
         if (it == media_.end()) return fatal("Named medium \"" + M + "\" undefined.");
         med = &it->second;
     }
+    if (mediaOk_) {
+        if (!FinishMedia(M)) return false;
+        med = nullptr;  // the media are the table's: the scene itself has none
+    }
     // One medium fills all space: a non-transition interface ("" "") keeps the ray's medium
     // (GeometricPrimitive::Intersect), an (M, M) interface re-enters M; photons leave the light
     // through its own interface, so the emitter must carry (M, M) when M is not vacuum.
-    for (size_t i = 0; i < shapes_.size(); ++i) {
+    for (size_t i = 0; !mediaOk_ && i < shapes_.size(); ++i) {
         const ShapeRec &s = shapes_[i];
         const bool inherit = s.inside.empty() && s.outside.empty();
         const bool same = s.inside == M && s.outside == M;
@@ -1232,7 +1243,7 @@ bool Parser::Finish() {
             return fatal("shape " + std::to_string(i) + " has MediumInterface \"" + s.inside + "\" \"" + s.outside +
                          "\"; the GPU scene model has one medium (\"" + M + "\") filling all space");
     }
-    for (size_t i = 0; i < lightOutside_.size(); ++i)
+    for (size_t i = 0; !mediaOk_ && i < lightOutside_.size(); ++i)
         if (lightOutside_[i] != M)
             return fatal("light " + std::to_string(i) + " is declared in medium \"" + lightOutside_[i] +
                          "\"; the GPU scene model has one medium (\"" + M + "\") filling all space");
@@ -1270,21 +1281,80 @@ bool Parser::Finish() {
     return true;
 }
 
+// kParseMedia: every named medium in use becomes an entry of PbrtScene::media (equal media share one), every
+// shape keeps its MediumInterface, the camera medium is the outside medium at Camera... WorldEnd (api.cpp:651-655)
+// and a light sits in the outside medium of its graphics state (MakeLight, api.cpp).
+bool Parser::FinishMedia(const std::string &cameraMedium) {
+    PbrtScene &o = *out_;
+    SceneMedia &sm = o.media;
+    sm = SceneMedia();
+    bool ok = true;
+    const auto index = [&](const std::string &name) -> int32_t {
+        if (name.empty()) return -1;
+        auto it = media_.find(name);
+        if (it == media_.end()) {
+            o.messages += "Error: Named medium \"" + name + "\" undefined.\n";
+            ++o.errors;
+            ok = false;
+            return -1;
+        }
+        const MediumDef &d = it->second;
+        bre_medium b;
+        memset(&b, 0, sizeof(b));
+        b.type = d.kind;
+        memcpy(b.sigma_a, d.sigma_a, sizeof(b.sigma_a));
+        memcpy(b.sigma_s, d.sigma_s, sizeof(b.sigma_s));
+        b.g = d.g;
+        if (d.kind == BRE_MEDIUM_GRID) {
+            memcpy(b.grid_n, d.n, sizeof(b.grid_n));
+            memcpy(b.world_to_medium, d.worldToMedium, sizeof(b.world_to_medium));
+        }
+        for (size_t k = 0; k < sm.media.size(); ++k)
+            if (memcmp(&sm.media[k], &b, sizeof(b)) == 0 && sm.density[k] == d.density) return (int32_t)k;
+        if ((int)sm.media.size() >= BRE_MAX_MEDIA) {
+            o.messages += "Error: more than BRE_MAX_MEDIA (" + std::to_string(BRE_MAX_MEDIA) + ") media in use\n";
+            ++o.errors;
+            ok = false;
+            return -1;
+        }
+        sm.media.push_back(b);  // grid_density stays null here: Bind() points it at the copy
+        sm.density.push_back(d.kind == BRE_MEDIUM_GRID ? d.density : std::vector<float>());
+        return (int32_t)sm.media.size() - 1;
+    };
+    bool interfaces = false;
+    for (const ShapeRec &s : shapes_) {
+        sm.triInside.push_back(index(s.inside));
+        sm.triOutside.push_back(index(s.outside));
+        interfaces = interfaces || (s.material >= 0 && o.materials[(size_t)s.material].type == BRE_MATERIAL_INTERFACE);
+    }
+    for (const std::string &name : lightOutside_) sm.lightMedium.push_back(index(name));
+    sm.cameraMedium = index(cameraMedium);
+    if (ok && interfaces && sm.media.empty()) {
+        o.messages += "Error: shapes without a material bound no medium: the scene names none\n";
+        ++o.errors;
+        ok = false;
+    }
+    if (sm.media.empty()) sm = SceneMedia();  // a scene in vacuum: nothing to set
+    sm.Bind();
+    return ok;
+}
+
 }  // namespace
 
 void PbrtScene::Bind() {
+    media.Bind();
     scene.grid_density = density.empty() ? nullptr : density.data();
     scene.triangles_ext = triangles.empty() ? nullptr : triangles.data();
 }
 
-static bool ParseLexer(Lexer &lx, PbrtScene *out) {
+static bool ParseLexer(Lexer &lx, PbrtScene *out, int flags) {
     *out = PbrtScene();
-    Parser p(out);
+    Parser p(out, flags);
     if (!p.Run(lx, 0)) return false;
     return p.Finish();
 }
 
-bool ParsePbrtFile(const std::string &path, PbrtScene *out) {
+bool ParsePbrtFile(const std::string &path, PbrtScene *out, int flags) {
     std::ifstream in(path, std::ios::binary);
     if (!in) {
         *out = PbrtScene();
@@ -1295,12 +1365,12 @@ bool ParsePbrtFile(const std::string &path, PbrtScene *out) {
     std::stringstream ss;
     ss << in.rdbuf();
     Lexer lx(ss.str(), path);
-    return ParseLexer(lx, out);
+    return ParseLexer(lx, out, flags);
 }
 
-bool ParsePbrtString(const std::string &text, PbrtScene *out) {
+bool ParsePbrtString(const std::string &text, PbrtScene *out, int flags) {
     Lexer lx(text, "<string>");
-    return ParseLexer(lx, out);
+    return ParseLexer(lx, out, flags);
 }
 
 // ---------------------------------------------------------------------------------------------

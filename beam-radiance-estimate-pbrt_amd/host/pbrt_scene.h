@@ -26,9 +26,10 @@
 //     falls back to matte.  The direct statement Material "glass" is reported as unsupported.
 //   * AreaLightSource "diffuse" ("L" x "scale", one-sided): every triangle of an emitting mesh is
 //     its own light, as pbrtShape makes one DiffuseAreaLight per shape (api.cpp).
-//   * media: "homogeneous" or "heterogeneous" (GridDensityMedium); the scene model has ONE medium
+//   * media: "homogeneous" or "heterogeneous" (GridDensityMedium).  By default the scene has ONE medium
 //     filling all space, so every shape's inside/outside medium and the camera medium must be
-//     that medium (or all empty = vacuum).
+//     that medium (or all empty = vacuum); with kParseMedia every named medium in use becomes a table
+//     entry and every shape and light keeps its MediumInterface (PbrtScene::media).
 //   * LightSource "spot" ("I" x "scale", "from", "to", "coneangle", "conedeltaangle"): a bre_light with
 //     CreateSpotLight's transform, in PbrtScene::lights; its outside medium must be the scene's medium.
 //     Every other LightSource is reported as unsupported.
@@ -111,6 +112,20 @@ struct FilmDesc {
     float scale = 1.f;
 };
 
+// The media of a scene parsed with kParseMedia (bre_set_media's arguments): the table of the named media in
+// use (equal media share an entry), per scene triangle its MediumInterface as indices into it (-1: vacuum),
+// the camera's medium and each spot light's.  All empty / -1 otherwise.
+constexpr int kParseMedia = 1;  // BRE_PBRT_MEDIA (include/bre_pbrt.h)
+struct SceneMedia {
+    std::vector<bre_medium> media;             // grid_density points into `density`
+    std::vector<std::vector<float>> density;   // per table entry: a heterogeneous medium's data
+    std::vector<int32_t> triInside, triOutside, lightMedium;
+    int32_t cameraMedium = -1;
+    void Bind() {
+        for (size_t k = 0; k < media.size(); ++k) media[k].grid_density = density[k].empty() ? nullptr : density[k].data();
+    }
+};
+
 // Everything the render needs from one .pbrt file.
 struct PbrtScene {
     bre_scene scene;                  // grid_density / triangles_ext point into the vectors below
@@ -123,6 +138,7 @@ struct PbrtScene {
     // scene triangle its index into it (-1: matte); both empty for a matte-only scene
     std::vector<bre_material> materials;
     std::vector<int32_t> triangleMaterial;
+    SceneMedia media;                 // kParseMedia: the scene's media; scene.has_medium is then BRE_MEDIUM_NONE
     FilmDesc film;
     std::string integratorName;       // "photonbeam" expected
     ParamSet integratorParams;        // CreatePhotonBeamIntegrator's ParamSet
@@ -141,8 +157,11 @@ void MakeSpotLight(const Xform &l2w, const float from[3], const float to[3], con
 // Parse a .pbrt file / string (pbrtParseFile / pbrtParseString).  Returns false only on a fatal
 // problem (unreadable file, syntax error, no renderable scene); per-statement problems are
 // recorded as errors and the statement skipped, as pbrt does.
-bool ParsePbrtFile(const std::string &path, PbrtScene *out);
-bool ParsePbrtString(const std::string &text, PbrtScene *out);
+// `flags`: 0, or kParseMedia: media bounded by surfaces are accepted (MediumInterface on any shape or light,
+// Material "" / "none" shapes as interface triangles) and arrive as PbrtScene::media instead of the one
+// medium of bre_scene.
+bool ParsePbrtFile(const std::string &path, PbrtScene *out, int flags = 0);
+bool ParsePbrtString(const std::string &text, PbrtScene *out, int flags = 0);
 
 // Film::SetImage(L) + Film::WriteImage (film.cpp:132-140, 168-210) for the photon-beam
 // integrator's image: per pixel RGB -> XYZ (RGBSpectrum::ToXYZ), filterWeightSum = 1, no splats,

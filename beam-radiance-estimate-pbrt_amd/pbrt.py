@@ -16,13 +16,15 @@ import os
 import numpy as np
 
 from . import load_library
-from .scene import Light, Material, RenderParams, Scene
+from .scene import Light, Material, Medium, RenderParams, Scene
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 HOST_LIB_PATH = os.path.join(HERE, "libbre_host.so")
 CLI_PATH = os.path.join(HERE, "host", "bre_pbrt")
 
-EXPORTS = ["bre_pbrt_parse_file", "bre_pbrt_parse_string", "bre_pbrt_free", "bre_pbrt_messages",
+PBRT_MEDIA = 1  # BRE_PBRT_MEDIA
+EXPORTS = ["bre_pbrt_parse_file", "bre_pbrt_parse_string", "bre_pbrt_parse_file_ex", "bre_pbrt_parse_string_ex",
+           "bre_pbrt_get_media", "bre_pbrt_free", "bre_pbrt_messages",
            "bre_pbrt_get_scene", "bre_pbrt_get_lights", "bre_pbrt_get_materials", "bre_pbrt_make_spot_light", "bre_pbrt_get_render_params", "bre_pbrt_get_film", "bre_pbrt_render",
            "bre_pbrt_render_devices", "bre_film_finalize", "bre_write_pfm", "bre_read_pfm"]
 
@@ -40,6 +42,10 @@ def load_host_library(path: str = HOST_LIB_PATH) -> ctypes.CDLL:
     P, I64, I32, F = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_float
     lib.bre_pbrt_parse_file.argtypes = [ctypes.c_char_p, ctypes.POINTER(P)]
     lib.bre_pbrt_parse_string.argtypes = [ctypes.c_char_p, ctypes.POINTER(P)]
+    lib.bre_pbrt_parse_file_ex.argtypes = [ctypes.c_char_p, I32, ctypes.POINTER(P)]
+    lib.bre_pbrt_parse_string_ex.argtypes = [ctypes.c_char_p, I32, ctypes.POINTER(P)]
+    lib.bre_pbrt_get_media.argtypes = [P, I32, P, ctypes.POINTER(I32), I64, P, P, ctypes.POINTER(I64),
+                                       ctypes.POINTER(I32), I32, P, ctypes.POINTER(I32)]
     lib.bre_pbrt_free.argtypes = [P]
     lib.bre_pbrt_free.restype = None
     lib.bre_pbrt_messages.argtypes = [P, ctypes.POINTER(I32), ctypes.POINTER(I32)]
@@ -98,6 +104,19 @@ class PbrtScene:
         self.materials = [marr[i] for i in range(nm.value)]
         self.triangle_material = tm
         self._materials_ref = marr
+        # media bounded by surfaces (parse_*(..., media=True)), for BeamGather.set_media; the grids stay the handle's
+        nd, nt, cm, nl = ctypes.c_int32(), ctypes.c_int64(), ctypes.c_int32(), ctypes.c_int32()
+        assert self._lib.bre_pbrt_get_media(self._h, 0, None, ctypes.byref(nd), 0, None, None, ctypes.byref(nt),
+                                            ctypes.byref(cm), 0, None, ctypes.byref(nl)) == 0
+        darr = (Medium * max(nd.value, 1))()
+        ti, to = np.full(nt.value, -1, np.int32), np.full(nt.value, -1, np.int32)
+        lm = np.full(nl.value, -1, np.int32)
+        assert self._lib.bre_pbrt_get_media(self._h, nd.value, darr, None, nt.value, ti.ctypes.data if nt.value else None,
+                                            to.ctypes.data if nt.value else None, None, None, nl.value,
+                                            lm.ctypes.data if nl.value else None, None) == 0
+        self.media = [darr[i] for i in range(nd.value)]
+        self.tri_inside, self.tri_outside, self.camera_medium, self.light_medium = ti, to, cm.value, lm
+        self._media_ref = darr
         self.params = RenderParams()
         wf = ctypes.c_int32()
         assert self._lib.bre_pbrt_get_render_params(self._h, int(quick), ctypes.byref(self.params), ctypes.byref(wf)) == 0
@@ -140,19 +159,24 @@ class PbrtScene:
             pass
 
 
-def _parse(fn, arg: bytes, quick: bool) -> PbrtScene:
+def _parse(fn, arg: bytes, quick: bool, media: bool) -> PbrtScene:
     lib = load_host_library()
     h = ctypes.c_void_p()
-    st = getattr(lib, fn)(arg, ctypes.byref(h))
+    if media:
+        st = getattr(lib, fn + "_ex")(arg, PBRT_MEDIA, ctypes.byref(h))
+    else:
+        st = getattr(lib, fn)(arg, ctypes.byref(h))
     return PbrtScene(h, st == 0, quick)
 
 
-def parse_file(path: str, quick: bool = False) -> PbrtScene:
-    return _parse("bre_pbrt_parse_file", os.fsencode(path), quick)
+def parse_file(path: str, quick: bool = False, media: bool = False) -> PbrtScene:
+    """`media`: BRE_PBRT_MEDIA -- media bounded by surfaces are accepted (.media, .tri_inside, .tri_outside,
+    .camera_medium, .light_medium on the result) instead of refused."""
+    return _parse("bre_pbrt_parse_file", os.fsencode(path), quick, media)
 
 
-def parse_string(text: str, quick: bool = False) -> PbrtScene:
-    return _parse("bre_pbrt_parse_string", text.encode(), quick)
+def parse_string(text: str, quick: bool = False, media: bool = False) -> PbrtScene:
+    return _parse("bre_pbrt_parse_string", text.encode(), quick, media)
 
 
 def make_spot_light(frm, to, I, coneangle: float = 30.0, conedelta: float = 5.0, order: int = 0, ctm=None,

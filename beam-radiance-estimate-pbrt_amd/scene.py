@@ -113,6 +113,76 @@ def scene_materials(meshes):
     return table, tri
 
 
+MATERIAL_INTERFACE = 3
+MAX_MEDIA = 64
+
+
+def interface() -> Material:
+    """Material "" / "none": no BSDF, both walks pass through (a medium boundary).  A context takes it only
+    after BeamGather.set_media."""
+    return Material(MATERIAL_INTERFACE, _rgb(0.0), _rgb(0.0), 0.0)
+
+
+class Medium(ctypes.Structure):
+    """bre_medium: a HomogeneousMedium or a GridDensityMedium of the context's media table (120 bytes)."""
+    _fields_ = [("type", ctypes.c_int32), ("sigma_a", F3), ("sigma_s", F3), ("g", ctypes.c_float),
+                ("grid_n", ctypes.c_int32 * 3), ("world_to_medium", ctypes.c_float * 16),
+                ("reserved", ctypes.c_int32), ("grid_density", ctypes.c_void_p)]
+
+    def to_bytes(self) -> bytes:
+        return ctypes.string_at(ctypes.addressof(self), ctypes.sizeof(self))
+
+
+def medium_homogeneous(sigma_a, sigma_s, g: float = 0.0) -> Medium:
+    """MakeNamedMedium "homogeneous": sigma_a, sigma_s (rgb or scalar, "scale" applied), HG g."""
+    m = Medium()
+    m.type = MEDIUM_HOMOGENEOUS
+    m.sigma_a, m.sigma_s, m.g = _rgb(sigma_a), _rgb(sigma_s), float(g)
+    return m
+
+
+def medium_grid(sigma_a, sigma_s, g, density, n, world_to_medium=None) -> Medium:
+    """MakeNamedMedium "heterogeneous": a GridDensityMedium over `density` (n = (nx, ny, nz) or int, x fastest)
+    on the medium-space unit cube.  The array is kept alive on the object (the struct holds its address)."""
+    import numpy as np
+
+    nx, ny, nz = (n, n, n) if isinstance(n, int) else tuple(n)
+    dens = np.ascontiguousarray(density, np.float32).reshape(-1)
+    assert dens.shape[0] == nx * ny * nz
+    m = medium_homogeneous(sigma_a, sigma_s, g)
+    m.type = MEDIUM_GRID
+    m.grid_n = (ctypes.c_int32 * 3)(nx, ny, nz)
+    w = np.eye(4, dtype=np.float32) if world_to_medium is None else np.asarray(world_to_medium, np.float32)
+    m.world_to_medium = (ctypes.c_float * 16)(*[float(v) for v in w.reshape(-1)])
+    m.grid_density = dens.ctypes.data
+    m._density_ref = dens
+    return m
+
+
+def scene_media(meshes, camera_medium=None, light_media=()):
+    """(media, tri_inside, tri_outside, camera_medium, light_medium) of `meshes` for BeamGather.set_media.  A
+    mesh's sixth element is its MediumInterface, a pair (inside, outside) of Medium objects or None (vacuum);
+    a mesh without one is no transition (-1, -1).  `camera_medium` and `light_media` (one per delta light)
+    are Medium objects or None.  One table entry per distinct Medium object, in order of first use."""
+    table, index = [], {}
+
+    def idx(m):
+        if m is None:
+            return -1
+        if id(m) not in index:
+            index[id(m)] = len(table)
+            table.append(m)
+        return index[id(m)]
+
+    inside, outside = [], []
+    for mesh in meshes:
+        pair = mesh[5] if len(mesh) > 5 and mesh[5] is not None else (None, None)
+        k = len(mesh[1]) // 3
+        inside += [idx(pair[0])] * k
+        outside += [idx(pair[1])] * k
+    return table, inside, outside, idx(camera_medium), [idx(m) for m in light_media]
+
+
 class RenderParams(ctypes.Structure):
     """bre_render_params: CreatePhotonBeamIntegrator's parameters (photonbeam.cpp:589-611)."""
     _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("iterations", ctypes.c_int32),
@@ -141,7 +211,8 @@ def make_scene(meshes, sigma_a=None, sigma_s=None, g=0.0,
     sigma_a is given (RGB or scalar).  More than MAX_TRIANGLES triangles go to an external array
     (Scene.triangles_ext, kept alive on the scene object).  A mesh may carry a fifth element, its
     Material (mirror / glass) or None: the struct does not hold it (scene_materials(meshes) returns
-    what BeamGather.set_materials takes)."""
+    what BeamGather.set_materials takes).  A sixth element is the mesh's MediumInterface, a pair (inside,
+    outside) of Medium objects or None (scene_media(meshes, ...) returns what BeamGather.set_media takes)."""
     s = Scene()
     ctypes.memset(ctypes.addressof(s), 0, ctypes.sizeof(s))
     total = sum(len(mesh[1]) // 3 for mesh in meshes)

@@ -112,7 +112,7 @@ typedef enum bre_option {
                                 gathers every segment against the BVH work roots rank, rank + count, ...
                                 of the size-ordered list (kernels 0/4); surface radiance and films as
                                 in 1, per-segment outputs are the shard's subtrees' partial sums */
-    BRE_OPT_FILM_CLASSES = 16 /* 1 (default) or BRE_FILM_CLASSES (8): the films the camera pass and the
+    BRE_OPT_FILM_CLASSES = 16, /* 1 (default) or BRE_FILM_CLASSES (8): the films the camera pass and the
                                 kernel 0 / 4 gathers add to are 8 planes of float[3*npix] -- class c
                                 holds the surface radiance of the pixels p with p % 8 == c and the
                                 gather terms of the segments in the sorted order's packet chunks k
@@ -127,6 +127,10 @@ typedef enum bre_option {
                                 floats; the entry points with films of their own (bre_gather,
                                 bre_render, bre_render_progressive, bre_gather_sharded) refuse the
                                 option with BRE_ERR_STATE. */
+    BRE_OPT_SEGMENT_BUDGET = 17 /* camera pass with media (bre_set_media) and an interface triangle: the
+                                segments one pixel's path may record beyond maxdepth, 0..240 (default
+                                16).  A path that needs more sets a sticky device flag and the camera
+                                pass returns BRE_ERR_STATE: nothing is dropped silently. */
 } bre_option;
 
 #define BRE_FILM_CLASSES 8
@@ -295,9 +299,37 @@ bre_status bre_set_lights(bre_ctx *ctx, const bre_light *lights, int32_t n);
    as they were): a null array with a non-zero count, n_materials < 0 or > BRE_MAX_MATERIALS, n_triangles
    < 0 or > BRE_MAX_SCENE_TRIANGLES, an unknown type, an index outside [-1, n_materials), a non-finite or
    non-positive eta, a non-finite Kr or Kt.  Contexts of one sharded render must hold equal materials.
-   Needs no device. */
+   BRE_MATERIAL_INTERFACE (no BSDF: both walks pass through, Kr, Kt and eta ignored) is accepted only while
+   the context holds media (bre_set_media first; without them it is refused as an unknown type), and a pass
+   refuses an interface triangle once the media are cleared.  Needs no device. */
 bre_status bre_set_materials(bre_ctx *ctx, const bre_material *materials, int32_t n_materials,
                              const int32_t *triangle_material, int64_t n_triangles);
+
+/* ---- media bounded by surfaces (bre_medium, bre_scene.h; pbrt's MediumInterface) ----
+   Copies the table media[0 .. n_media) with its density grids, the per-triangle pairs
+   tri_inside / tri_outside[0 .. n_triangles) and light_medium[0 .. n_lights) into the context; n_media == 0
+   clears everything.  Every medium argument is an index into `media`, or -1 for vacuum (a null Medium*).
+   tri_inside[i] == tri_outside[i]: triangle i is no transition and a ray leaving it keeps its own medium
+   (GeometricPrimitive::Intersect).  Otherwise a ray spawned from it towards w takes `outside` when
+   Dot(w, n) > 0 and `inside` when not (Interaction::GetMedium), n the triangle's geometric normal.  An
+   emitting triangle's photons start in GetMedium(w) of its own pair, equal or not.  camera_medium is
+   Camera::medium; light_medium[j] is delta light j's mediumInterface.inside (its photons start there);
+   a null array with n_lights == 0 suits a context without delta lights.  A triangle whose material is
+   BRE_MATERIAL_INTERFACE has no BSDF: the photon walk pushes its beam and passes through without a draw,
+   depth and beta unchanged; the camera walk records its segment and passes through with the depth not
+   counted; shadow rays multiply the transmittance of each medium on the way (VisibilityTester::Tr,
+   Scene::IntersectTr).  Sticky like bre_set_lights.  While a context holds media the passes refuse, with
+   BRE_ERR_INVALID_ARG: a scene whose has_medium is not BRE_MEDIUM_NONE, a scene with another triangle
+   count, an n_lights that is not the context's light count.  Refused here with BRE_ERR_INVALID_ARG (the
+   context's media stay as they were): null arrays with non-zero counts, n_media < 0 or > BRE_MAX_MEDIA,
+   n_triangles < 0 or > BRE_MAX_SCENE_TRIANGLES, n_lights < 0 or > BRE_MAX_LIGHTS, grids with more than
+   BRE_MAX_GRID_CELLS cells together, an unknown type, an index outside [-1, n_media), a non-finite or
+   negative sigma, a grid medium whose sigma_a + sigma_s is not spectrally uniform, |g| > 1 or non-finite,
+   a grid size below 1, a null density or one without a positive maximum.  Contexts of one sharded render
+   must hold equal media.  Needs no device. */
+bre_status bre_set_media(bre_ctx *ctx, const bre_medium *media, int32_t n_media, const int32_t *tri_inside,
+                         const int32_t *tri_outside, int64_t n_triangles, int32_t camera_medium,
+                         const int32_t *light_medium, int32_t n_lights);
 
 /* ---- photon pass (replaces photonbeam.cpp:362-437: emission, TracePhotonBeamRecursive and the
    merge into one beam vector, then the PhotonBeamBVH build of :438) ----

@@ -35,6 +35,14 @@ typedef struct bre_pbrt bre_pbrt;
    failed parse can be read; BRE_OK iff the scene is renderable. */
 bre_status bre_pbrt_parse_file(const char *path, bre_pbrt **out);
 bre_status bre_pbrt_parse_string(const char *text, bre_pbrt **out);
+/* The same with flags.  BRE_PBRT_MEDIA: media bounded by surfaces are accepted instead of refused --
+   MediumInterface on any shape or light, Material "" / "none" shapes as BRE_MATERIAL_INTERFACE triangles --
+   and every named medium in use becomes an entry of the table bre_pbrt_get_media returns (equal media share
+   one); the bre_scene then has no medium of its own.  An undefined medium name fails the parse, as in pbrt.
+   flags 0 is bre_pbrt_parse_file / _string, which keep refusing such scenes. */
+#define BRE_PBRT_MEDIA 1
+bre_status bre_pbrt_parse_file_ex(const char *path, int32_t flags, bre_pbrt **out);
+bre_status bre_pbrt_parse_string_ex(const char *text, int32_t flags, bre_pbrt **out);
 void bre_pbrt_free(bre_pbrt *p);
 /* Error()/Warning() text, one message per line; counts may be NULL. */
 const char *bre_pbrt_messages(const bre_pbrt *p, int32_t *n_errors, int32_t *n_warnings);
@@ -54,6 +62,15 @@ bre_status bre_pbrt_get_lights(const bre_pbrt *p, int32_t capacity, bre_light *o
 bre_status bre_pbrt_get_materials(const bre_pbrt *p, int32_t mat_capacity, bre_material *materials,
                                   int32_t *n_materials, int64_t tri_capacity, int32_t *triangle_material,
                                   int64_t *n_triangles);
+/* The media of a scene parsed with BRE_PBRT_MEDIA, for bre_set_media: the table (grid_density points into the
+   parsed scene and stays valid until bre_pbrt_free), per scene triangle its MediumInterface as indices into it
+   (-1: vacuum), the camera's medium (the outside medium at WorldEnd) and each spot light's (the outside medium
+   where it was declared).  At most the given capacities are written; the counts and *camera_medium may be NULL.
+   n_media 0: a scene without media, or parsed without the flag.  bre_pbrt_render sets them on every context it
+   makes, before the materials. */
+bre_status bre_pbrt_get_media(const bre_pbrt *p, int32_t med_capacity, bre_medium *media, int32_t *n_media,
+                              int64_t tri_capacity, int32_t *tri_inside, int32_t *tri_outside, int64_t *n_triangles,
+                              int32_t *camera_medium, int32_t light_capacity, int32_t *light_medium, int32_t *n_lights);
 /* A spot light as CreateSpotLight (src/lights/spot.cpp:104-124) builds it, by the code the parser uses:
    light_to_world = CTM * Translate(from) * Inverse(dirToZ), world_to_light the tracked inverse,
    cone_falloff_start_deg = coneangle - conedeltaangle.  I is "I" times "scale"; ctm is a row-major 4x4

@@ -34,9 +34,13 @@
  *                       specular lobe (SpecularReflection::Sample_f, FresnelSpecular::Sample_f;
  *                       reflection.cpp:136-143, 477-511): the photon pass in TransportMode::Importance,
  *                       the camera pass in Radiance (the eta^2 factor), with isect.Le added after a
- *                       specular bounce and no direct light on a specular vertex.  The medium fills the
- *                       glass too (shapes carry no medium transition).
- *   - an optional medium filling all of space (every ray -- camera, photon, spawned -- travels
+ *                       specular bounce and no direct light on a specular vertex.  Without bre_set_media
+ *                       the scene's one medium fills the glass too.
+ *   - media bounded by surfaces (bre_medium below; pbrt's MediumInterface): a context holds a table of
+ *                       media, a per-triangle (inside, outside) pair, the camera's medium and each delta
+ *                       light's (bre_set_media, bre.h).  Every ray carries its medium; a triangle whose
+ *                       material is BRE_MATERIAL_INTERFACE has no BSDF and both walks pass through it.
+ *   - otherwise an optional medium filling all of space (every ray -- camera, photon, spawned -- travels
  *                       in it) with a Henyey-Greenstein phase function (src/core/medium.cpp:194-213):
  *                       BRE_MEDIUM_HOMOGENEOUS = HomogeneousMedium (src/media/homogeneous.cpp:44-77),
  *                       BRE_MEDIUM_GRID = GridDensityMedium (src/media/grid.{h:50-100,cpp:46-120}):
@@ -77,7 +81,8 @@ typedef struct bre_scene {
     int32_t n_triangles;   /* 1 .. BRE_MAX_TRIANGLES inline, or 1 .. BRE_MAX_SCENE_TRIANGLES through
                               triangles_ext; at least one with emit != 0 unless the context holds
                               lights (bre_set_lights) */
-    int32_t has_medium;    /* BRE_MEDIUM_NONE (vacuum) / _HOMOGENEOUS / _GRID, filling all space */
+    int32_t has_medium;    /* BRE_MEDIUM_NONE (vacuum) / _HOMOGENEOUS / _GRID, filling all space; must be
+                              BRE_MEDIUM_NONE while the context holds media (bre_set_media) */
     float sigma_a[3];      /* medium sigma_a (already multiplied by "scale") */
     float sigma_s[3];      /* medium sigma_s */
     float g;               /* Henyey-Greenstein asymmetry */
@@ -129,14 +134,36 @@ typedef struct bre_light {
    -1 keeps its own matte kd.  `emit` is independent of the material, as in pbrt. */
 #define BRE_MATERIAL_MIRROR 1
 #define BRE_MATERIAL_GLASS 2
+/* pbrt's Material "" / "none": GetMaterial() == nullptr, no BSDF at all.  Both walks pass through such a
+   triangle (photonbeam.cpp:300-304, 515-517) and shadow rays step over it (VisibilityTester::Tr,
+   Scene::IntersectTr); kr, kt and eta are ignored.  It is not a BSDF without a BxDF (a black mirror), which
+   ends the path.  bre_set_materials accepts it only on a context that holds media (bre_set_media first). */
+#define BRE_MATERIAL_INTERFACE 3
 #define BRE_MAX_MATERIALS 1024 /* table entries accepted by bre_set_materials */
 
 typedef struct bre_material {
-    int32_t type; /* BRE_MATERIAL_MIRROR / BRE_MATERIAL_GLASS */
+    int32_t type; /* BRE_MATERIAL_MIRROR / BRE_MATERIAL_GLASS / BRE_MATERIAL_INTERFACE */
     float kr[3];  /* "Kr", clamped to [0, 1] (Spectrum::Clamp); black = no reflection lobe */
     float kt[3];  /* glass: "Kt", clamped to [0, 1]; ignored for a mirror */
     float eta;    /* glass: "eta" / "index", finite and > 0 (also checked for a mirror, which ignores it) */
 } bre_material;   /* 32 bytes, no padding */
+
+/* Media bounded by surfaces: pbrt's MediumInterface.  Like the lights and materials they are not part of
+   bre_scene: a context holds a table of media, each triangle's (inside, outside) pair, the camera's medium
+   and each delta light's (bre_set_media, bre.h).  The fields mean what the same-named bre_scene fields mean. */
+#define BRE_MAX_MEDIA 64 /* table entries accepted by bre_set_media; their grids together hold at most
+                            BRE_MAX_GRID_CELLS cells */
+
+typedef struct bre_medium {
+    int32_t type;               /* BRE_MEDIUM_HOMOGENEOUS / BRE_MEDIUM_GRID */
+    float sigma_a[3];           /* finite, >= 0 */
+    float sigma_s[3];           /* finite, >= 0; a grid medium's sigma_a + sigma_s is spectrally uniform */
+    float g;                    /* Henyey-Greenstein asymmetry, |g| <= 1 */
+    int32_t grid_n[3];          /* grid: nx, ny, nz (each >= 1) */
+    float world_to_medium[16];  /* grid: WorldToMedium, row-major 4x4 */
+    int32_t reserved;           /* 0: keeps the pointer aligned without compiler padding */
+    const float *grid_density;  /* grid: nx*ny*nz densities with a positive maximum, copied at the call */
+} bre_medium;                   /* 120 bytes, no padding */
 
 /* PhotonBeamIntegrator parameters (CreatePhotonBeamIntegrator, photonbeam.cpp:589-611). */
 typedef struct bre_render_params {
