@@ -1,9 +1,9 @@
 // bre_api.hip — C ABI of libbre.so (include/bre.h): context lifetime, options, stream, stats, the
 // gather-after links and events, and the small device reads and fills every other unit uses
-// (bre_ctx.h).  The build is in bre_api_build.hip, the gathers in bre_api_gather.hip, the photon and
-// camera passes in bre_api_pass.hip, the multi-context calls in bre_api_shard.hip, the test hooks in
-// bre_api_check.hip and the host-only helpers in bre_api_host.hip.  No exceptions cross the ABI; every
-// failure is a status code plus a message for bre_last_error().
+// (bre_ctx.h).  The build is in bre_api_build.hip, the gathers in bre_api_gather.hip, the scene setters and
+// upload in bre_api_scene.hip, the passes in bre_api_pass.hip, the multi-context calls in bre_api_shard.hip,
+// the test hooks in bre_api_check.hip and the host-only helpers in bre_api_host.hip.  No exceptions cross
+// the ABI; every failure is a status code plus a message for bre_last_error().
 #include <algorithm>
 #include <cstdarg>
 #include <cstdio>

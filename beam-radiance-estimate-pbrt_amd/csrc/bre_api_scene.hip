@@ -1,0 +1,411 @@
+// bre_api_scene.hip — the scene model behind the C ABI: the sticky setters (bre_set_lights,
+// bre_set_materials, bre_set_media) that fill a context's SceneState, the checks of a bre_scene against it,
+// the comparison of two states, and upload_scene with its geometry cache, which keeps the SceneDevice.
+#include <algorithm>
+#include <cmath>
+#include <cstddef>
+#include <cstring>
+#include <vector>
+
+#include "bre_ctx.h"
+
+using namespace bre;
+
+namespace {
+
+// v into m on the context's stream, *at the device copy; m holds at least 4 bytes, so an empty array has a pointer
+template <typename T>
+hipError_t upload(bre_ctx *c, DevMem &m, const std::vector<T> &v, const T **at = nullptr) {
+    const hipError_t e = m.ensure(v.empty() ? 4 : v.size() * sizeof(T));
+    if (at) *at = m.as<T>();
+    if (e != hipSuccess || v.empty()) return e;
+    return hipMemcpyAsync(m.ptr, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, c->stream);
+}
+
+// `bytes` of src into m unless m holds them already (`last`: the bytes it was given last).  A copy is waited
+// for: the DMA reads the caller's memory.
+bre_status upload_changed(bre_ctx *c, DevMem &m, std::vector<unsigned char> &last, const void *src, size_t bytes) {
+    const unsigned char *b = static_cast<const unsigned char *>(src);
+    if (m.ptr && last.size() == bytes && memcmp(last.data(), b, bytes) == 0) return BRE_OK;
+    HIPCHK(c, m.ensure(bytes));
+    HIPCHK(c, hipMemcpyAsync(m.ptr, src, bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    last.assign(b, b + bytes);
+    return BRE_OK;
+}
+
+// The context's media on the device: the table with its grids behind one another, the pairs and the lights'
+// media.  Uploaded when bre_set_media changed them.
+bre_status upload_media(bre_ctx *c) {
+    const SceneState &h = c->held;
+    SceneDevice &dv = c->dev;
+    if (!dv.media_stale) return BRE_OK;
+    std::vector<DevMedium> table(h.media.size());
+    std::vector<float> dens;
+    std::vector<size_t> first(h.media.size(), 0);
+    for (size_t k = 0; k < h.media.size(); ++k) {
+        const bre_medium &m = h.media[k];
+        const std::vector<float> &g = h.media_grid[k];  // empty unless a grid
+        table[k] = make_medium(m.type, m.sigma_a, m.sigma_s, m.g, m.grid_n, m.world_to_medium, nullptr,
+                               max_density(g.data(), (int64_t)g.size()));
+        first[k] = dens.size();
+        dens.insert(dens.end(), g.begin(), g.end());
+    }
+    HIPCHK(c, upload(c, dv.md_dens, dens));
+    for (size_t k = 0; k < table.size(); ++k)
+        if (table[k].medium == BRE_MEDIUM_GRID) table[k].density = dv.md_dens.as<float>() + first[k];
+    HIPCHK(c, upload(c, dv.md_table, table));
+    HIPCHK(c, upload(c, dv.md_pairs, h.tri_med));
+    HIPCHK(c, upload(c, dv.md_light, h.light_med));
+    HIPCHK(c, hipStreamSynchronize(c->stream));  // the host vectors go out of scope
+    dv.media_stale = false;
+    return BRE_OK;
+}
+
+// A byte range of a key.  The lights, materials and material map of a SceneState are compared as such ranges:
+// between two contexts (scene_state_differs), and behind the scene's triangles by the geometry cache.
+struct KeyPart {
+    const void *p;
+    size_t bytes;
+};
+bool same_bytes(const KeyPart &a, const KeyPart &b) {
+    return a.bytes == b.bytes && (a.bytes == 0 || memcmp(a.p, b.p, a.bytes) == 0);
+}
+void state_key(const SceneState &h, KeyPart part[3]) {
+    part[0] = {h.lights.data(), h.lights.size() * sizeof(bre_light)};
+    part[1] = {h.mats.data(), h.mats.size() * sizeof(bre_material)};
+    part[2] = {h.tri_mat.data(), h.tri_mat.size() * sizeof(int32_t)};
+}
+// the ranges of SceneDevice::bytes: the scene's triangles, then the state's three
+void geometry_key(const SceneState &h, const bre_scene *s, KeyPart part[4]) {
+    part[0] = {scene_triangles(s), (size_t)s->n_triangles * sizeof(bre_triangle)};
+    state_key(h, part + 1);
+}
+
+uint64_t hash_bytes(uint64_t h, const void *data, size_t bytes) {
+    const unsigned char *p = static_cast<const unsigned char *>(data);
+    size_t i = 0;
+    for (; i + 8 <= bytes; i += 8) {
+        uint64_t w;
+        memcpy(&w, p + i, 8);
+        h = (h ^ w) * 0x100000001b3ull;
+        h ^= h >> 29;
+    }
+    for (; i < bytes; ++i) h = (h ^ p[i]) * 0x100000001b3ull;
+    return h;
+}
+
+// 64-bit hash of the scene's triangles and the context's lights, materials and material map (the
+// geometry cache key of upload_scene); without lights and materials it is the hash of the triangles alone
+uint64_t hash_geometry(const bre_scene *s, const KeyPart part[4]) {
+    uint64_t h = hash_bytes(0x9e3779b97f4a7c15ull ^ (uint64_t)s->n_triangles, part[0].p, part[0].bytes);
+    for (int k = 1; k < 4; ++k)
+        if (part[k].bytes) h = hash_bytes(h ^ (uint64_t)(part[k].bytes * (size_t)k), part[k].p, part[k].bytes);
+    return h | 1ull;  // never 0 (= no scene)
+}
+
+}  // namespace
+
+namespace bre {
+
+const char *scene_state_differs(const SceneState &a, const SceneState &b) {
+    KeyPart ka[3], kb[3];
+    state_key(a, ka);
+    state_key(b, kb);
+    if (!same_bytes(ka[0], kb[0])) return "lights (bre_set_lights)";
+    // the stored table is the clamped one on both sides
+    if (!same_bytes(ka[1], kb[1]) || !same_bytes(ka[2], kb[2])) return "materials (bre_set_materials)";
+    if (a.media_key != b.media_key) return "media (bre_set_media)";
+    return nullptr;
+}
+
+// Medium parameters: GridDensityMedium needs a density grid with a positive maximum (the ctor's
+// invMaxDensity = 1/maxDensity, grid.h:73-76); a non-uniform sigma_t is accepted as pbrt does
+// (its Error() only reports it, grid.h:66-70) and channel 0 is used.
+bre_status check_medium(bre_ctx *c, const bre_scene *scene, const char *fn) {
+    if (!scene) return fail(c, BRE_ERR_INVALID_ARG, "%s: null scene", fn);
+    if (scene->has_medium < BRE_MEDIUM_NONE || scene->has_medium > BRE_MEDIUM_GRID)
+        return fail(c, BRE_ERR_INVALID_ARG, "%s: unknown medium type %d", fn, scene->has_medium);
+    if (scene->has_medium != BRE_MEDIUM_GRID) return BRE_OK;
+    const int64_t nx = scene->grid_n[0], ny = scene->grid_n[1], nz = scene->grid_n[2];
+    if (nx < 1 || ny < 1 || nz < 1 || nx * ny * nz > BRE_MAX_GRID_CELLS)
+        return fail(c, BRE_ERR_INVALID_ARG, "%s: grid dimensions must be >= 1 with at most %d cells", fn,
+                    BRE_MAX_GRID_CELLS);
+    if (!scene->grid_density) return fail(c, BRE_ERR_INVALID_ARG, "%s: null grid_density", fn);
+    if (!(grid_max_density(scene) > 0))
+        return fail(c, BRE_ERR_INVALID_ARG, "%s: grid density maximum must be > 0", fn);
+    return BRE_OK;
+}
+
+// Triangle count in range and at least one light: an emitting triangle, or a delta light of the context
+// (the passes need scene.lights non-empty); every delta light's order within the triangle count
+bre_status check_scene(bre_ctx *c, const bre_scene *scene, const char *fn) {
+    if (!scene) return fail(c, BRE_ERR_INVALID_ARG, "%s: null scene", fn);
+    const SceneState &h = c->held;
+    const int cap = scene->triangles_ext ? BRE_MAX_SCENE_TRIANGLES : BRE_MAX_TRIANGLES;
+    if (scene->n_triangles < 1 || scene->n_triangles > cap)
+        return fail(c, BRE_ERR_INVALID_ARG, "%s: triangle count must be in 1..%d (%s)", fn, cap,
+                    scene->triangles_ext ? "triangles_ext" : "inline triangles; use triangles_ext for more");
+    const bre_triangle *tri = scene_triangles(scene);
+    int64_t lights = 0;
+    for (int i = 0; i < scene->n_triangles; ++i) lights += tri[i].emit != 0;
+    if (lights == 0 && h.lights.empty()) return fail(c, BRE_ERR_INVALID_ARG, "%s: the scene has no area light", fn);
+    for (size_t k = 0; k < h.lights.size(); ++k)
+        if (h.lights[k].order > scene->n_triangles)
+            return fail(c, BRE_ERR_INVALID_ARG, "%s: light %d has order %d, the scene has %d triangles", fn, (int)k,
+                        h.lights[k].order, scene->n_triangles);
+    if (!h.mats.empty() && h.tri_mat.size() != (size_t)scene->n_triangles)
+        return fail(c, BRE_ERR_INVALID_ARG, "%s: the material map (bre_set_materials) covers %lld triangles, the scene "
+                    "has %d", fn, (long long)h.tri_mat.size(), scene->n_triangles);
+    if (h.media.empty()) {
+        if (h.has_interface)
+            return fail(c, BRE_ERR_INVALID_ARG, "%s: a BRE_MATERIAL_INTERFACE triangle needs the context's media "
+                        "(bre_set_media)", fn);
+        return BRE_OK;
+    }
+    // two sources of media would be ambiguous
+    if (scene->has_medium != BRE_MEDIUM_NONE)
+        return fail(c, BRE_ERR_INVALID_ARG, "%s: the context holds media (bre_set_media): the scene's has_medium must "
+                    "be BRE_MEDIUM_NONE", fn);
+    if (h.tri_med.size() != 2 * (size_t)scene->n_triangles)
+        return fail(c, BRE_ERR_INVALID_ARG, "%s: the media pairs (bre_set_media) cover %lld triangles, the scene has %d",
+                    fn, (long long)(h.tri_med.size() / 2), scene->n_triangles);
+    if (h.light_med.size() != h.lights.size())
+        return fail(c, BRE_ERR_INVALID_ARG, "%s: the media (bre_set_media) name %lld delta lights, the context holds "
+                    "%lld", fn, (long long)h.light_med.size(), (long long)h.lights.size());
+    return BRE_OK;
+}
+
+// DevScene (+ the density grid of a GridDensityMedium) into dev.record on the context's stream.  The
+// geometry (triangles, BVHAccel, lights, materials) is rebuilt and uploaded only when the triangles, the
+// context's lights or its materials change.
+bre_status upload_scene(bre_ctx *c, const bre_scene *scene) {
+    const SceneState &h = c->held;
+    SceneDevice &dv = c->dev;
+    float *dd = nullptr;
+    if (scene->has_medium == BRE_MEDIUM_GRID) {
+        // copied only when the density values change (every pass of a render shares one grid)
+        const size_t n = (size_t)scene->grid_n[0] * scene->grid_n[1] * scene->grid_n[2];
+        BRE_TRY(upload_changed(c, dv.grid, dv.grid_bytes, scene->grid_density, n * sizeof(float)));
+        dd = dv.grid.as<float>();
+    }
+    KeyPart part[4];
+    geometry_key(h, scene, part);
+    const uint64_t hash = hash_geometry(scene, part);
+    // the geometry is reused only when the hash AND the bytes match (a hash collision between two
+    // scenes must not trace against the stale BVH, lights and materials)
+    bool same = hash == dv.hash;
+    for (int k = 0; k < 4; ++k) same = same && same_bytes({dv.bytes[k].data(), dv.bytes[k].size()}, part[k]);
+    if (!same) {
+        HostScene hs;
+        const MaterialMap mm{h.mats.data(), (int)h.mats.size(), h.tri_mat.data()};
+        prepare_geometry(scene, &hs, h.lights.data(), (int)h.lights.size(), mm);
+        if (hs.depth > kSceneStack)
+            return fail(c, BRE_ERR_INVALID_ARG, "scene BVH depth %d exceeds the %d-entry traversal stack (as in "
+                        "BVHAccel::Intersect)", hs.depth, kSceneStack);
+        dv.hash = 0;  // the cached geometry is overwritten from here on
+        dv.head = hs.head;
+        HIPCHK(c, upload(c, dv.tris, hs.tris, &dv.head.t));
+        HIPCHK(c, upload(c, dv.nodes, hs.nodes, &dv.head.nodes));
+        HIPCHK(c, upload(c, dv.prims, hs.prims, &dv.head.prims));
+        HIPCHK(c, upload(c, dv.light_tri, hs.light_tri, &dv.head.light_tri));
+        HIPCHK(c, upload(c, dv.light_func, hs.light_func, &dv.head.light_func));
+        HIPCHK(c, upload(c, dv.light_cdf, hs.light_cdf, &dv.head.light_cdf));
+        HIPCHK(c, upload(c, dv.dlights, hs.dlights, &dv.head.dlights));
+        HIPCHK(c, upload(c, dv.mats, hs.mats, &dv.head.mats));
+        HIPCHK(c, hipStreamSynchronize(c->stream));  // the host vectors go out of scope
+        dv.hash = hash;
+        for (int k = 0; k < 4; ++k) {
+            const unsigned char *b = static_cast<const unsigned char *>(part[k].p);
+            dv.bytes[k].assign(b, b + part[k].bytes);
+        }
+    }
+    DevScene ds;
+    memcpy(&ds, &dv.head, sizeof(DevScene));  // padding bytes included: the record compares bytewise
+    prepare_medium(scene, &ds, dd);
+    const bool media = !h.media.empty();  // (cleared media leave cam_med at -1)
+    if (media) BRE_TRY(upload_media(c));
+    ds.media = media ? dv.md_table.as<DevMedium>() : nullptr;
+    ds.tri_med = media ? dv.md_pairs.as<int32_t>() : nullptr;
+    ds.light_med = media ? dv.md_light.as<int32_t>() : nullptr;
+    ds.n_media = (int)h.media.size();
+    ds.cam_med = h.cam_med;
+    // the scene record is copied only when it changes: in a render every pass uploads the same record,
+    // and a copy queued behind another context's gather waits for that gather's blocks (round 5 trace:
+    // a 1.6 KB upload took 110 ms in the two-context pipeline)
+    return upload_changed(c, dv.record, dv.record_bytes, &ds, sizeof(DevScene));
+}
+
+}  // namespace bre
+
+extern "C" {
+
+bre_status bre_set_lights(bre_ctx *c, const bre_light *lights, int32_t n) {
+    if (!c) return BRE_ERR_INVALID_ARG;
+    if (n < 0 || n > BRE_MAX_LIGHTS)
+        return fail(c, BRE_ERR_INVALID_ARG, "bre_set_lights: light count must be in 0..%d", BRE_MAX_LIGHTS);
+    if (n > 0 && !lights) return fail(c, BRE_ERR_INVALID_ARG, "bre_set_lights: null lights");
+    for (int k = 0; k < n; ++k) {
+        const bre_light &l = lights[k];
+        if (l.type != BRE_LIGHT_POINT && l.type != BRE_LIGHT_SPOT)
+            return fail(c, BRE_ERR_INVALID_ARG, "bre_set_lights: light %d has unknown type %d", k, l.type);
+        if (l.order < 0) return fail(c, BRE_ERR_INVALID_ARG, "bre_set_lights: light %d has a negative order", k);
+        bool finite = std::isfinite(l.cone_total_deg) && std::isfinite(l.cone_falloff_start_deg);
+        for (int j = 0; j < 3; ++j) finite = finite && std::isfinite(l.I[j]);
+        for (int j = 0; j < 16; ++j)
+            finite = finite && std::isfinite(l.light_to_world[j]) && std::isfinite(l.world_to_light[j]);
+        if (!finite) return fail(c, BRE_ERR_INVALID_ARG, "bre_set_lights: light %d has a non-finite field", k);
+    }
+    c->held.lights.assign(lights, lights + n);
+    return BRE_OK;
+}
+
+bre_status bre_set_materials(bre_ctx *c, const bre_material *materials, int32_t n_materials,
+                             const int32_t *triangle_material, int64_t n_triangles) {
+    if (!c) return BRE_ERR_INVALID_ARG;
+    const char *fn = "bre_set_materials";
+    if (n_materials < 0 || n_materials > BRE_MAX_MATERIALS)
+        return fail(c, BRE_ERR_INVALID_ARG, "%s: material count must be in 0..%d", fn, BRE_MAX_MATERIALS);
+    if (n_materials == 0) {
+        c->held.mats.clear();
+        c->held.tri_mat.clear();
+        c->held.has_interface = false;
+        return BRE_OK;
+    }
+    if (n_triangles < 0 || n_triangles > BRE_MAX_SCENE_TRIANGLES)
+        return fail(c, BRE_ERR_INVALID_ARG, "%s: the material map's triangle count must be in 0..%d", fn,
+                    BRE_MAX_SCENE_TRIANGLES);
+    if (!materials || (n_triangles > 0 && !triangle_material))
+        return fail(c, BRE_ERR_INVALID_ARG, "%s: null material table or triangle_material map", fn);
+    std::vector<bre_material> mats(materials, materials + n_materials);
+    std::vector<char> is_interface((size_t)n_materials, 0);
+    for (int k = 0; k < n_materials; ++k) {
+        bre_material &m = mats[(size_t)k];
+        if (m.type == BRE_MATERIAL_INTERFACE && !c->held.media.empty()) {
+            // no BSDF: Kr, Kt and eta are ignored (kept as zeros, so that equal tables compare equal)
+            m = bre_material{};
+            m.type = BRE_MATERIAL_INTERFACE;
+            is_interface[(size_t)k] = 1;
+            continue;
+        }
+        // (an interface on a context without media is refused like an unknown type: bre_set_media comes first)
+        if (m.type != BRE_MATERIAL_MIRROR && m.type != BRE_MATERIAL_GLASS)
+            return fail(c, BRE_ERR_INVALID_ARG, "%s: material %d has unknown type %d%s", fn, k, m.type,
+                        m.type == BRE_MATERIAL_INTERFACE ? " (BRE_MATERIAL_INTERFACE needs bre_set_media first)" : "");
+        if (!std::isfinite(m.eta) || !(m.eta > 0))
+            return fail(c, BRE_ERR_INVALID_ARG, "%s: material %d has eta %g (must be finite and > 0)", fn, k, m.eta);
+        for (int j = 0; j < 3; ++j) {
+            if (!std::isfinite(m.kr[j]) || !std::isfinite(m.kt[j]))
+                return fail(c, BRE_ERR_INVALID_ARG, "%s: material %d has a non-finite Kr or Kt", fn, k);
+            // Kr->Evaluate(*si).Clamp() (mirror.cpp:52, glass.cpp:54-55) bounds the value below by 0; the ABI
+            // also bounds it above by 1 (a reflectance), which a physical scene file never exceeds
+            m.kr[j] = m.kr[j] < 0.f ? 0.f : (m.kr[j] > 1.f ? 1.f : m.kr[j]);
+            m.kt[j] = m.kt[j] < 0.f ? 0.f : (m.kt[j] > 1.f ? 1.f : m.kt[j]);
+        }
+    }
+    for (int64_t i = 0; i < n_triangles; ++i)
+        if (triangle_material[i] < -1 || triangle_material[i] >= n_materials)
+            return fail(c, BRE_ERR_INVALID_ARG, "%s: triangle %lld has material index %d outside [-1, %d)", fn,
+                        (long long)i, triangle_material[i], n_materials);
+    c->held.mats.swap(mats);
+    c->held.tri_mat.assign(triangle_material, triangle_material + n_triangles);
+    c->held.has_interface = false;
+    for (int64_t i = 0; i < n_triangles; ++i)
+        if (triangle_material[i] >= 0 && is_interface[(size_t)triangle_material[i]]) c->held.has_interface = true;
+    return BRE_OK;
+}
+
+bre_status bre_set_media(bre_ctx *c, const bre_medium *media, int32_t n_media, const int32_t *tri_inside,
+                         const int32_t *tri_outside, int64_t n_triangles, int32_t camera_medium,
+                         const int32_t *light_medium, int32_t n_lights) {
+    if (!c) return BRE_ERR_INVALID_ARG;
+    const char *fn = "bre_set_media";
+    if (n_media < 0 || n_media > BRE_MAX_MEDIA)
+        return fail(c, BRE_ERR_INVALID_ARG, "%s: medium count must be in 0..%d", fn, BRE_MAX_MEDIA);
+    if (n_media == 0) {
+        c->held.media.clear();
+        c->held.media_grid.clear();
+        c->held.tri_med.clear();
+        c->held.light_med.clear();
+        c->held.media_key.clear();
+        c->held.cam_med = -1;
+        c->dev.media_stale = true;
+        return BRE_OK;
+    }
+    if (n_triangles < 0 || n_triangles > BRE_MAX_SCENE_TRIANGLES)
+        return fail(c, BRE_ERR_INVALID_ARG, "%s: the media pairs' triangle count must be in 0..%d", fn,
+                    BRE_MAX_SCENE_TRIANGLES);
+    if (n_lights < 0 || n_lights > BRE_MAX_LIGHTS)
+        return fail(c, BRE_ERR_INVALID_ARG, "%s: the light media count must be in 0..%d", fn, BRE_MAX_LIGHTS);
+    if (!media || (n_triangles > 0 && (!tri_inside || !tri_outside)) || (n_lights > 0 && !light_medium))
+        return fail(c, BRE_ERR_INVALID_ARG, "%s: null media table, triangle pair array or light media array", fn);
+    const auto index_ok = [&](int32_t v) { return v >= -1 && v < n_media; };
+    int64_t cells = 0;
+    for (int k = 0; k < n_media; ++k) {
+        const bre_medium &m = media[k];
+        if (m.type != BRE_MEDIUM_HOMOGENEOUS && m.type != BRE_MEDIUM_GRID)
+            return fail(c, BRE_ERR_INVALID_ARG, "%s: medium %d has unknown type %d", fn, k, m.type);
+        for (int j = 0; j < 3; ++j)
+            if (!std::isfinite(m.sigma_a[j]) || !std::isfinite(m.sigma_s[j]) || m.sigma_a[j] < 0 || m.sigma_s[j] < 0)
+                return fail(c, BRE_ERR_INVALID_ARG, "%s: medium %d has a non-finite or negative sigma", fn, k);
+        if (!std::isfinite(m.g) || std::fabs(m.g) > 1)
+            return fail(c, BRE_ERR_INVALID_ARG, "%s: medium %d has g %g (|g| must be <= 1)", fn, k, m.g);
+        if (m.type != BRE_MEDIUM_GRID) continue;
+        const float st0 = m.sigma_a[0] + m.sigma_s[0];
+        if (m.sigma_a[1] + m.sigma_s[1] != st0 || m.sigma_a[2] + m.sigma_s[2] != st0)
+            return fail(c, BRE_ERR_INVALID_ARG, "%s: grid medium %d: sigma_a + sigma_s must be spectrally uniform", fn, k);
+        const int64_t nx = m.grid_n[0], ny = m.grid_n[1], nz = m.grid_n[2];
+        if (nx < 1 || ny < 1 || nz < 1 || nx * ny * nz > BRE_MAX_GRID_CELLS || (cells += nx * ny * nz) > BRE_MAX_GRID_CELLS)
+            return fail(c, BRE_ERR_INVALID_ARG, "%s: grid medium %d: dimensions must be >= 1, with at most %d cells "
+                        "over the table", fn, k, BRE_MAX_GRID_CELLS);
+        if (!m.grid_density) return fail(c, BRE_ERR_INVALID_ARG, "%s: grid medium %d has a null density", fn, k);
+        const float mx = max_density(m.grid_density, nx * ny * nz);
+        if (!(mx > 0) || !std::isfinite(mx))
+            return fail(c, BRE_ERR_INVALID_ARG, "%s: grid medium %d: the density maximum must be finite and > 0", fn, k);
+    }
+    for (int64_t i = 0; i < n_triangles; ++i)
+        if (!index_ok(tri_inside[i]) || !index_ok(tri_outside[i]))
+            return fail(c, BRE_ERR_INVALID_ARG, "%s: triangle %lld has a medium index outside [-1, %d)", fn, (long long)i,
+                        n_media);
+    if (!index_ok(camera_medium))
+        return fail(c, BRE_ERR_INVALID_ARG, "%s: the camera medium index %d is outside [-1, %d)", fn, camera_medium, n_media);
+    for (int j = 0; j < n_lights; ++j)
+        if (!index_ok(light_medium[j]))
+            return fail(c, BRE_ERR_INVALID_ARG, "%s: light %d has a medium index outside [-1, %d)", fn, j, n_media);
+    // accepted: copy everything, the grids included
+    std::vector<unsigned char> key;
+    const auto put = [&](const void *p, size_t bytes) {
+        const unsigned char *b = static_cast<const unsigned char *>(p);
+        key.insert(key.end(), b, b + bytes);
+    };
+    c->held.media.assign(media, media + n_media);
+    c->held.media_grid.assign((size_t)n_media, std::vector<float>());
+    for (int k = 0; k < n_media; ++k) {
+        bre_medium &m = c->held.media[(size_t)k];
+        m.reserved = 0;
+        if (m.type == BRE_MEDIUM_GRID) {
+            const size_t n = (size_t)m.grid_n[0] * m.grid_n[1] * m.grid_n[2];
+            c->held.media_grid[(size_t)k].assign(m.grid_density, m.grid_density + n);
+            m.grid_density = c->held.media_grid[(size_t)k].data();
+        } else {
+            m.grid_density = nullptr;
+        }
+        put(&m, offsetof(bre_medium, grid_density));
+        put(c->held.media_grid[(size_t)k].data(), c->held.media_grid[(size_t)k].size() * sizeof(float));
+    }
+    c->held.tri_med.resize(2 * (size_t)n_triangles);
+    for (int64_t i = 0; i < n_triangles; ++i) {
+        c->held.tri_med[2 * (size_t)i] = tri_inside[i];
+        c->held.tri_med[2 * (size_t)i + 1] = tri_outside[i];
+    }
+    c->held.light_med.assign(light_medium, light_medium + n_lights);
+    c->held.cam_med = camera_medium;
+    put(c->held.tri_med.data(), c->held.tri_med.size() * sizeof(int32_t));
+    put(c->held.light_med.data(), c->held.light_med.size() * sizeof(int32_t));
+    put(&camera_medium, sizeof(camera_medium));
+    c->held.media_key.swap(key);
+    c->dev.media_stale = true;
+    return BRE_OK;
+}
+
+}  // extern "C"

@@ -177,16 +177,6 @@ class Rendezvous {
     unsigned gen_ = 0;
 };
 
-struct FinalImage {
-    float *dst;
-    size_t n;
-};
-int keep_final_image(int32_t, const float *img, void *user) {
-    FinalImage *f = static_cast<FinalImage *>(user);
-    memcpy(f->dst, img, f->n * sizeof(float));
-    return 0;
-}
-
 // The class-plane films (n_ctx divides 8: the same bits for every such count) need the deterministic
 // per-pixel compose of kernels 0 / 4 wherever a gather runs
 bool class_films(int n_ctx) { return BRE_FILM_CLASSES % n_ctx == 0; }
@@ -200,21 +190,10 @@ bre_status check_render_sharded(bre_ctx *const *ctxs, int n_ctx, const bre_scene
     BRE_TRY(check_ctxs(ctxs, n_ctx));
     if (!scene) return fail(ctxs[0], BRE_ERR_INVALID_ARG, "%s: null scene", fn);
     BRE_TRY(check_params(ctxs[0], rp));
-    // the contexts' films are summed: every context must light the scene alike (bre_set_lights)
-    for (int i = 1; i < n_ctx; ++i) {
-        const std::vector<bre_light> &a = ctxs[0]->lights, &b = ctxs[i]->lights;
-        if (a.size() != b.size() || (!a.empty() && memcmp(a.data(), b.data(), a.size() * sizeof(bre_light)) != 0))
-            return fail(ctxs[0], BRE_ERR_INVALID_ARG, "context %d: %s: its lights (bre_set_lights) differ from context 0's", i, fn);
-        // ... and shade it alike (bre_set_materials): the stored table is the clamped one on both sides
-        const std::vector<bre_material> &ma = ctxs[0]->mats, &mb = ctxs[i]->mats;
-        const std::vector<int32_t> &ta = ctxs[0]->tri_mat, &tb = ctxs[i]->tri_mat;
-        if (ma.size() != mb.size() || ta != tb ||
-            (!ma.empty() && memcmp(ma.data(), mb.data(), ma.size() * sizeof(bre_material)) != 0))
-            return fail(ctxs[0], BRE_ERR_INVALID_ARG, "context %d: %s: its materials (bre_set_materials) differ from context 0's", i, fn);
-        // ... in the same media (bre_set_media): tables, grids, pairs, camera and light media
-        if (ctxs[0]->media_key != ctxs[i]->media_key)
-            return fail(ctxs[0], BRE_ERR_INVALID_ARG, "context %d: %s: its media (bre_set_media) differ from context 0's", i, fn);
-    }
+    // the contexts' films are summed: every context must light the scene alike, shade it alike, in the same media
+    for (int i = 1; i < n_ctx; ++i)
+        if (const char *part = scene_state_differs(ctxs[0]->held, ctxs[i]->held))
+            return fail(ctxs[0], BRE_ERR_INVALID_ARG, "context %d: %s: its %s differ from context 0's", i, fn, part);
     if (!class_films(n_ctx) || !rp->render_media) return BRE_OK;
     for (int i = 0; i < n_ctx; ++i) {
         const bre_ctx *c = ctxs[i];

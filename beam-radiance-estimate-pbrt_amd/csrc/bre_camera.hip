@@ -395,9 +395,9 @@ __device__ void estimate_direct(const DevScene &S, HaltonDev &hs, f3 p, f3 perr,
                 for (int c = 0; c < 3; ++c) Li[c] = Li[c] * Tr[c];
             } else if (intersect_scene(S, ro, rd, tmax, h)) {
                 Li[0] = Li[1] = Li[2] = 0.f;  // every triangle has a material
-            } else if (S.medium) {
+            } else if (S.own.medium) {
                 float tr[3];
-                medium_tr_any(S, hs, ro, rd, tmax, tr);
+                medium_tr_any(S.own, hs, ro, rd, tmax, tr);
                 for (int c = 0; c < 3; ++c) Li[c] = Li[c] * (1.f * tr[c]);
             }
             if (!black3(Li)) {
@@ -444,9 +444,9 @@ __device__ void estimate_direct(const DevScene &S, HaltonDev &hs, f3 p, f3 perr,
                 }
             } else {
                 found = intersect_scene(S, ro, wi, tmax, h);
-                if (S.medium) {
+                if (S.own.medium) {
                     float t2[3];
-                    medium_tr_any(S, hs, ro, wi, tmax, t2);
+                    medium_tr_any(S.own, hs, ro, wi, tmax, t2);
                     for (int c = 0; c < 3; ++c) tr[c] = tr[c] * t2[c];
                 }
             }

@@ -6,6 +6,7 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <cstring>
 #include <initializer_list>
 #include <string>
 #include <vector>
@@ -161,6 +162,37 @@ struct Stream : NoCopy {
     operator hipStream_t() const { return h; }
 };
 
+// The scene state the sticky setters store on a context, beside the bre_scene every pass is given
+struct SceneState {
+    std::vector<bre_light> lights;   // bre_set_lights: the delta lights every pass adds to its scene
+    std::vector<bre_material> mats;  // bre_set_materials: the mirror / glass table (Kr, Kt clamped) ...
+    std::vector<int32_t> tri_mat;    // ... and each triangle's index into it (-1: its own matte kd)
+    bool has_interface = false;      // ... one of which leads to a BRE_MATERIAL_INTERFACE entry
+    // bre_set_media: the table (grid_density pointing into media_grid), the triangles' (inside, outside) pairs
+    // interleaved, the delta lights' media, the camera's; media_key: all of it as bytes, the grids for the pointers
+    std::vector<bre_medium> media;
+    std::vector<std::vector<float>> media_grid;
+    std::vector<int32_t> tri_med, light_med;
+    int cam_med = -1;
+    std::vector<unsigned char> media_key;
+};
+
+// What upload_scene keeps on the device, and the host bytes it compares the next call's scene against
+struct SceneDevice {
+    // geometry: triangles, BVHAccel nodes + primitive order, scene.lights, the delta lights and the materials
+    DevMem tris, nodes, prims, light_tri, light_func, light_cdf, dlights, mats;
+    DevScene head;                     // its fields of the record below
+    uint64_t hash = 0;                 // hash of the uploaded triangles, lights and materials (0: none)
+    // the uploaded triangles' bytes, the lights', the materials' and the map's: a hash match is confirmed by memcmp
+    std::vector<unsigned char> bytes[4];
+    DevMem md_table, md_pairs, md_light, md_dens;  // the media: table, pairs, lights' media, grids (upload_media)
+    bool media_stale = false;                      // bre_set_media changed them since
+    DevMem grid;                                   // the scene's own density grid,
+    std::vector<unsigned char> grid_bytes;         // as last copied
+    DevMem record;                                 // the DevScene the kernels read,
+    std::vector<unsigned char> record_bytes;       // as last copied
+};
+
 }  // namespace bre
 
 // Members are destroyed last to first: the buffers, then the pinned words, the events, and last the streams
@@ -217,33 +249,13 @@ struct bre_ctx {
     // deterministic per-pixel compose; px_cls the film class per segment (BRE_OPT_FILM_CLASSES)
     bre::DevMem px_seg, px_cls;
     bre::SortScratch px_sort;
+    // the scene model: what the setters stored, and what upload_scene keeps on the device (bre_api_scene.hip)
+    bre::SceneState held;
+    bre::SceneDevice dev;
+    int seg_budget = 16;  // BRE_OPT_SEGMENT_BUDGET
     // photon pass
-    bre::DevMem ph_scene, ph_counts, ph_offsets, ph_tmp, grid_dens;
+    bre::DevMem ph_counts, ph_offsets, ph_tmp;
     bre::BeamArrays ph_s;  // single-trace photon pass: per-photon beam slots
-    // scene geometry on the device (upload_scene): triangles, BVHAccel nodes + primitive order, lights
-    bre::DevMem sc_tris, sc_nodes, sc_prims, sc_light_tri, sc_light_func, sc_light_cdf, sc_dlights, sc_mats;
-    std::vector<bre_light> lights;          // bre_set_lights: the delta lights every pass adds to its scene
-    std::vector<bre_material> mats;         // bre_set_materials: the mirror / glass table (Kr, Kt clamped) ...
-    std::vector<int32_t> tri_mat;           // ... and each triangle's index into it (-1: its own matte kd)
-    bool has_interface = false;             // ... one of which leads to a BRE_MATERIAL_INTERFACE entry
-    // bre_set_media: the table (grid_density pointing into media_grid), each triangle's (inside, outside) pair
-    // interleaved, each delta light's medium and the camera's; media_key is all of it as bytes (the pointers
-    // left out, the grids in), which is what two contexts' media are compared by
-    std::vector<bre_medium> media;
-    std::vector<std::vector<float>> media_grid;
-    std::vector<int32_t> tri_med, light_med;
-    int cam_med = -1;
-    std::vector<unsigned char> media_key;
-    bool media_dirty = false;               // the device copies below are older than the state above
-    bre::DevMem md_table, md_pairs, md_light, md_dens;
-    int seg_budget = 16;                    // BRE_OPT_SEGMENT_BUDGET
-    uint64_t sc_hash = 0;                   // hash of the uploaded triangles, lights and materials (0: none)
-    std::vector<unsigned char> sc_bytes;    // the uploaded triangles' bytes, then the lights', the materials' and
-                                            // the map's: a hash match is confirmed by memcmp
-    size_t sc_part[4] = {0, 0, 0, 0};       // the byte counts of those four ranges
-    bre::DevScene sc_head;                  // geometry fields of the uploaded scene
-    bre::DevScene ph_scene_host;            // the record last copied to ph_scene
-    std::vector<unsigned char> grid_bytes;  // the density grid last copied to grid_dens
     // camera pass
     bre::DevMem cam_dev, cam_perms, cam_offs, cam_tmp, cam_flags;
     bre::SegArrays cs;  // one slot per pixel sample and depth
@@ -284,6 +296,23 @@ bre_status gather_host(bre_ctx *c, int64_t nseg, const SegView &seg, float R, in
 bre_status check_params(bre_ctx *c, const bre_render_params *rp);
 // the write schedule of bre_render_progressive: is an image due after iteration `it`?
 bool image_due(int32_t it, int32_t end_iteration, int32_t write_frequency);
+// the bre_image_fn of bre_render and bre_render_sharded: keeps the last image it is given
+struct FinalImage {
+    float *dst;
+    size_t n;
+};
+inline int keep_final_image(int32_t, const float *img, void *user) {
+    const FinalImage *f = static_cast<const FinalImage *>(user);
+    memcpy(f->dst, img, f->n * sizeof(float));
+    return 0;
+}
+// bre_api_scene.hip: a bre_scene against the context's SceneState; the DevScene the kernels read
+// (c->dev.record), rebuilt and copied only where it changed
+bre_status check_scene(bre_ctx *c, const bre_scene *scene, const char *fn);
+bre_status check_medium(bre_ctx *c, const bre_scene *scene, const char *fn);
+bre_status upload_scene(bre_ctx *c, const bre_scene *scene);
+// the part that differs, "lights (bre_set_lights)", "materials ..." or "media ...", or null: the same state
+const char *scene_state_differs(const SceneState &a, const SceneState &b);
 // bre_api_build.hip
 bre_status build(bre_ctx *c, int64_t n, const BeamView &in);
 

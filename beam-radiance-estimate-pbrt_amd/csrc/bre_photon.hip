@@ -23,161 +23,11 @@
 
 #include <algorithm>
 #include <type_traits>
-#include <vector>
 
 #include "bre_device.h"
 #include "bre_trace.h"
 
 namespace bre {
-
-float grid_max_density(const bre_scene *s) {
-    float mx = 0;
-    const int64_t n = (int64_t)s->grid_n[0] * s->grid_n[1] * s->grid_n[2];
-    for (int64_t i = 0; i < n; ++i) mx = std::max(mx, s->grid_density[i]);
-    return mx;
-}
-
-void prepare_medium(const bre_scene *s, DevScene *dp, const float *d_density) {
-    DevScene &d = *dp;
-    d.medium = s->has_medium == BRE_MEDIUM_GRID ? BRE_MEDIUM_GRID : (s->has_medium ? BRE_MEDIUM_HOMOGENEOUS : 0);
-    if (d.medium == BRE_MEDIUM_GRID) {
-        // GridDensityMedium ctor (grid.h:58-77): sigma_t = (sigma_a + sigma_s)[0]; invMaxDensity
-        for (int k = 0; k < 3; ++k) d.gn[k] = s->grid_n[k];
-        d.grid_sigma_t = s->sigma_a[0] + s->sigma_s[0];
-        d.grid_inv_max = 1 / grid_max_density(s);
-        for (int k = 0; k < 16; ++k) d.w2m[k] = s->world_to_medium[k];
-        d.density = d_density;
-    }
-    for (int c = 0; c < 3; ++c)
-        d.sigma_t[c] = s->sigma_a[c] + s->sigma_s[c];  // HomogeneousMedium ctor: sigma_a + sigma_s
-    d.g = s->g;
-}
-
-// PointLight / SpotLight constructors (point.h, spot.cpp:44-51) and Light's (light.cpp:46-55)
-DLight prepare_light(const bre_light &l) {
-    DLight D{};
-    const float *m = l.light_to_world;
-    // pLight = LightToWorld(Point3f(0, 0, 0)), Transform::operator()(Point3f) (transform.h:223-233)
-    const float x = 0.f, y = 0.f, z = 0.f;
-    const float xp = m[0] * x + m[1] * y + m[2] * z + m[3];
-    const float yp = m[4] * x + m[5] * y + m[6] * z + m[7];
-    const float zp = m[8] * x + m[9] * y + m[10] * z + m[11];
-    const float wp = m[12] * x + m[13] * y + m[14] * z + m[15];
-    D.p = wp == 1 ? mk(xp, yp, zp) : div3(mk(xp, yp, zp), wp);
-    for (int r = 0; r < 3; ++r)
-        for (int c = 0; c < 3; ++c) {
-            D.l2w[3 * r + c] = l.light_to_world[4 * r + c];
-            D.w2l[3 * r + c] = l.world_to_light[4 * r + c];
-        }
-    for (int k = 0; k < 3; ++k) D.I[k] = l.I[k];
-    D.spot = l.type == BRE_LIGHT_SPOT;
-    if (D.spot) {  // std::cos(Radians(.)), pbrt.h:295
-        D.cos_total = bre_cosf((kPi / 180) * l.cone_total_deg);
-        D.cos_start = bre_cosf((kPi / 180) * l.cone_falloff_start_deg);
-    }
-    return D;
-}
-
-// Power().y(): 4 * Pi * I (point.cpp:55); I * 2 * Pi * (1 - .5f * (cosFalloffStart + cosTotalWidth))
-// (spot.cpp:75-77)
-static float light_power_y(const DLight &D) {
-    float pw[3];
-    for (int k = 0; k < 3; ++k)
-        pw[k] = D.spot ? D.I[k] * 2 * kPi * (1 - .5f * (D.cos_start + D.cos_total)) : D.I[k] * (4 * kPi);
-    return lum3(pw);
-}
-
-void prepare_geometry(const bre_scene *s, HostScene *out, const bre_light *lights, int n_lights,
-                      const MaterialMap &mm) {
-    DevScene &d = out->head;
-    d.n_tris = s->n_triangles;
-    out->mats.assign(mm.mats, mm.mats + mm.n_mats);
-    const bre_triangle *tri = scene_triangles(s);
-    out->tris.resize((size_t)s->n_triangles);
-    out->light_tri.clear();
-    out->light_func.clear();
-    // scene.lights in declaration order: a delta light comes before the area lights of the triangles
-    // with index >= its order; equal orders keep their array order (a stable sort by order)
-    out->dlights.resize((size_t)n_lights);
-    std::vector<int> by_order((size_t)n_lights);
-    for (int k = 0; k < n_lights; ++k) {
-        out->dlights[(size_t)k] = prepare_light(lights[k]);
-        by_order[(size_t)k] = k;
-    }
-    std::stable_sort(by_order.begin(), by_order.end(), [&](int a, int b) { return lights[a].order < lights[b].order; });
-    size_t next = 0;
-    const auto delta_up_to = [&](int i) {
-        for (; next < by_order.size() && lights[by_order[next]].order <= i; ++next) {
-            out->light_tri.push_back(~by_order[next]);
-            out->light_func.push_back(light_power_y(out->dlights[(size_t)by_order[next]]));
-        }
-    };
-    for (int i = 0; i < s->n_triangles; ++i) {
-        const bre_triangle &t = tri[i];
-        PTri &T = out->tris[(size_t)i];
-        T.p0 = mk(t.p[0][0], t.p[0][1], t.p[0][2]);
-        T.p1 = mk(t.p[1][0], t.p[1][1], t.p[1][2]);
-        T.p2 = mk(t.p[2][0], t.p[2][1], t.p[2][2]);
-        const f3 dp02 = sub3(T.p0, T.p2), dp12 = sub3(T.p1, T.p2);
-        // dpdu for pbrt's default uvs (0,0), (1,0), (1,1): (duv12[1] dp02 - duv02[1] dp12) invdet
-        // with duv12[1] = duv02[1] = -1, invdet = 1 (triangle.cpp:276-285)
-        const f3 dpdu = scale3(sub3(scale3(dp02, -1.f), scale3(dp12, -1.f)), 1.f);
-        T.n = normalize3(cross3d(dp02, dp12));
-        T.ns = normalize3(cross3d(sub3(T.p1, T.p0), sub3(T.p2, T.p0)));
-        if (t.flip) {
-            T.n = neg3(T.n);
-            T.ns = neg3(T.ns);
-        }
-        T.ss = normalize3(dpdu);
-        T.ts = cross3d(T.n, T.ss);
-        T.area = (float)(0.5 * (double)len3(cross3d(sub3(T.p1, T.p0), sub3(T.p2, T.p0))));
-        for (int k = 0; k < 3; ++k) {
-            T.kd[k] = t.kd[k];
-            T.Le[k] = t.Le[k];
-        }
-        T.mat = black3(t.kd) ? kMatNone : kMatMatte;
-        if (mm.n_mats > 0 && mm.tri_mat[i] >= 0) {
-            // mirror.cpp:50-56, glass.cpp:53-64: black Kr (and Kt) adds no BxDF
-            const bre_material &m = mm.mats[mm.tri_mat[i]];
-            const bool none = black3(m.kr) && (m.type == BRE_MATERIAL_MIRROR || black3(m.kt));
-            T.mat = none ? kMatNone : kMatTable + mm.tri_mat[i];
-            if (m.type == BRE_MATERIAL_INTERFACE) T.mat = kMatInterface;  // GetMaterial() == nullptr: no BSDF
-        }
-        T.emit = t.emit != 0;
-        if (T.emit) {
-            delta_up_to(i);
-            out->light_tri.push_back(i);
-            // DiffuseAreaLight::Power() = (twoSided ? 2 : 1) * Lemit * area * Pi (diffuse.cpp:64-66), .y()
-            float pw[3];
-            for (int k = 0; k < 3; ++k) pw[k] = ((T.Le[k] * 1.f) * T.area) * kPi;
-            out->light_func.push_back(lum3(pw));
-        }
-    }
-    delta_up_to(s->n_triangles);
-    const int nl = (int)out->light_tri.size();
-    d.n_lights = nl;
-    // Distribution1D(func, n) (sampling.h:57-69)
-    std::vector<float> &cdf = out->light_cdf;
-    const std::vector<float> &func = out->light_func;
-    cdf.assign((size_t)nl + 1, 0.f);
-    for (int i = 1; i < nl + 1; ++i) cdf[(size_t)i] = cdf[(size_t)i - 1] + func[(size_t)i - 1] / (float)nl;
-    d.light_func_int = cdf[(size_t)nl];
-    if (d.light_func_int == 0) {
-        for (int i = 1; i < nl + 1; ++i) cdf[(size_t)i] = (float)i / (float)nl;
-    } else {
-        for (int i = 1; i < nl + 1; ++i) cdf[(size_t)i] /= d.light_func_int;
-    }
-    out->depth = build_scene_bvh(out->tris, &out->nodes, &out->prims);
-    d.n_nodes = (int)out->nodes.size();
-    d.stack_depth = out->depth;
-}
-
-void prepare_scene(const bre_scene *s, HostScene *out, const float *d_density, const bre_light *lights, int n_lights,
-                   const MaterialMap &mm) {
-    out->head = DevScene{};
-    prepare_geometry(s, out, lights, n_lights, mm);
-    prepare_medium(s, &out->head, d_density);
-}
 
 namespace {
 
@@ -297,7 +147,7 @@ __global__ __launch_bounds__(kPhotonBlock, 6) void k_photons(const DevScene *__r
                     // beta * Tr(whole segment) (photonbeam.cpp:276-285)
                     float hx, hy;
                     pcg_2d(rng, hx, hy);
-                    float g = S.g;
+                    float g = S.own.g;
                     if constexpr (MED) g = S.media[med].g;
                     const f3 wi = hg_sample(g, neg3(d), hx, hy);
                     float tr[3];

@@ -188,25 +188,23 @@ struct DLight {
     int spot;                    // 1: SpotLight, 0: PointLight
 };
 
-// One entry of the context's media table (bre_medium as the HomogeneousMedium / GridDensityMedium
-// constructors leave it).  The medium fields carry DevScene's names, so the medium functions below take
-// either: the scene's one medium, or a table entry.
+// A medium as the HomogeneousMedium / GridDensityMedium constructors leave it (make_medium): the scene's own
+// (DevScene::own, from the bre_scene fields) or an entry of the context's media table (from a bre_medium).
 static_assert(sizeof(bre_medium) == 120, "bre_medium has no padding: the pointer is part of the layout");
 struct DevMedium {
-    int medium;  // BRE_MEDIUM_HOMOGENEOUS / _GRID
+    int medium;  // BRE_MEDIUM_HOMOGENEOUS / _GRID; BRE_MEDIUM_NONE only in DevScene::own
     float sigma_t[3];
     float g;
+    // GridDensityMedium (grid.h:50-80): sigma_t = (sigma_a + sigma_s)[0], invMaxDensity
     int gn[3];
     float grid_sigma_t, grid_inv_max;
-    float w2m[16];
-    const float *density;
+    float w2m[16];         // WorldToMedium, row-major
+    const float *density;  // device copy of the grid (nx*ny*nz)
 };
 
 struct DevScene {
-    int n_tris, n_lights, medium, n_nodes;  // medium: BRE_MEDIUM_NONE / _HOMOGENEOUS / _GRID
-    int stack_depth;                        // traversal stack entries per thread (the tree depth)
-    float sigma_t[3];
-    float g;
+    int n_tris, n_lights, n_nodes, stack_depth;  // stack_depth: traversal stack entries per thread (the tree depth)
+    DevMedium own;                               // the scene's one medium (bre_scene.has_medium; own.medium == 0: none)
     // the triangles in scene order, the BVHAccel over them (nodes + primitive order) and
     // scene.lights (the emitting triangles and the context's delta lights, merged by bre_light.order)
     // with the Distribution1D of their Power().y()
@@ -219,11 +217,6 @@ struct DevScene {
     const float *light_func;
     const float *light_cdf;     // n_lights + 1
     float light_func_int;
-    // GridDensityMedium (grid.h:50-80): sigma_t = (sigma_a + sigma_s)[0], invMaxDensity
-    int gn[3];
-    float grid_sigma_t, grid_inv_max;
-    float w2m[16];            // WorldToMedium, row-major
-    const float *density;     // device copy of the grid (nx*ny*nz)
     const bre_material *mats; // the mirror / glass table a PTri::mat >= kMatTable refers to (device array)
     // bre_set_media (null / 0 without): the table, per triangle its (inside, outside) pair of table indices
     // (-1: vacuum), per delta light its medium, and the camera's
@@ -233,7 +226,7 @@ struct DevScene {
     int n_media, cam_med;
 };
 
-// Host side of the scene: everything prepare_scene derives, in host memory; the context uploads
+// Host side of the scene: everything prepare_geometry derives, in host memory; the context uploads
 // the arrays and points the DevScene at them.
 struct HostScene {
     DevScene head;  // scalars; the array pointers are filled after the upload
@@ -254,25 +247,26 @@ struct MaterialMap {
     const int32_t *tri_mat = nullptr;  // one per scene triangle when n_mats > 0
 };
 
-// host: derive the per-triangle constants, the light distribution and the scene BVH exactly as
-// oracle/ora_pbrt.h make_scene does; `d_density` is the device copy of s->grid_density (grid media)
-void prepare_scene(const bre_scene *s, HostScene *out, const float *d_density = nullptr,
-                   const bre_light *lights = nullptr, int n_lights = 0, const MaterialMap &mm = MaterialMap());
-// the two halves of prepare_scene: the triangles, lights and BVH (out->head's geometry fields and
-// the arrays), and the medium fields of a DevScene
+// host (bre_scene.hip): derive the per-triangle constants, the light distribution and the scene BVH exactly
+// as oracle/ora_pbrt.h make_scene does: out->head's geometry fields and the arrays
 // (`lights`: the context's delta lights, each with order <= s->n_triangles; `mm`: its materials, the map
 // holding s->n_triangles entries)
 void prepare_geometry(const bre_scene *s, HostScene *out, const bre_light *lights = nullptr, int n_lights = 0,
                       const MaterialMap &mm = MaterialMap());
 // a bre_light as the PointLight / SpotLight constructor leaves it
 DLight prepare_light(const bre_light &l);
-void prepare_medium(const bre_scene *s, DevScene *d, const float *d_density);
+// a medium as its constructor leaves it: sigma_t = sigma_a + sigma_s per channel; for a grid, channel 0 of it,
+// 1 / max_density and `d_density`, the device copy of the grid (the grid arguments are not read otherwise)
+DevMedium make_medium(int type, const float sigma_a[3], const float sigma_s[3], float g, const int32_t grid_n[3],
+                      const float world_to_medium[16], const float *d_density, float max_density);
+void prepare_medium(const bre_scene *s, DevScene *d, const float *d_density);  // d->own, from s's medium fields
 // host: the scene's BVHAccel (bvh.cpp: SAH, 12 buckets, maxPrimsInNode 4, depth-first layout) over
 // the triangles' world bounds; returns the tree depth
 int build_scene_bvh(const std::vector<PTri> &tris, std::vector<SceneNode> *nodes, std::vector<int32_t> *prims);
 // the scene's triangle array: the inline one or triangles_ext (bre_scene.h)
 inline const bre_triangle *scene_triangles(const bre_scene *s) { return s->triangles_ext ? s->triangles_ext : s->triangles; }
-// host: GridDensityMedium ctor's maxDensity loop (grid.h:73-76), std::max order
+// host: GridDensityMedium ctor's maxDensity loop (grid.h:73-76), std::max order; of the scene's grid
+float max_density(const float *density, int64_t n);
 float grid_max_density(const bre_scene *s);
 
 struct Hit {
@@ -478,8 +472,7 @@ BRE_TD void light_sample_le(const DLight &D, float u0, float u1, f3 &d, float &p
 __device__ __forceinline__ float smp_1d(Pcg &r) { return pcg_float(r); }
 
 // HomogeneousMedium::Tr, homogeneous.cpp:44-48
-template <class M>
-__device__ __forceinline__ void medium_tr(const M &S, f3 d, float tmax, float tr[3]) {
+__device__ __forceinline__ void medium_tr(const DevMedium &S, f3 d, float tmax, float tr[3]) {
     const float x = smin(tmax * len3(d), kMaxFloat);
     // one expf per distinct argument (a grey medium's three channels share theirs: the same values)
     const float a0 = -S.sigma_t[0] * x, a1 = -S.sigma_t[1] * x, a2 = -S.sigma_t[2] * x;
@@ -489,8 +482,8 @@ __device__ __forceinline__ void medium_tr(const M &S, f3 d, float tmax, float tr
 }
 
 // HomogeneousMedium::Sample distance part, homogeneous.cpp:50-60 (two draws)
-template <class M, class Smp>
-__device__ __forceinline__ bool medium_sample(const M &S, Smp &rng, f3 d, float tmax, float &t) {
+template <class Smp>
+__device__ __forceinline__ bool medium_sample(const DevMedium &S, Smp &rng, f3 d, float tmax, float &t) {
     int ch = (int)(smp_1d(rng) * 3);
     ch = (2 < ch) ? 2 : ch;  // std::min(ch, 2)
     const float st = ch == 0 ? S.sigma_t[0] : (ch == 1 ? S.sigma_t[1] : S.sigma_t[2]);
@@ -503,15 +496,13 @@ __device__ __forceinline__ bool medium_sample(const M &S, Smp &rng, f3 d, float 
 BRE_TD float lerp_ref(float t, float v1, float v2) { return (1 - t) * v1 + t * v2; }  // pbrt.h:391
 
 // GridDensityMedium::D, grid.h:84-88 (0 outside [0, n) per axis)
-template <class M>
-__device__ __forceinline__ float grid_D(const M &S, int x, int y, int z) {
+__device__ __forceinline__ float grid_D(const DevMedium &S, int x, int y, int z) {
     if (!(x >= 0 && x < S.gn[0] && y >= 0 && y < S.gn[1] && z >= 0 && z < S.gn[2])) return 0.f;
     return S.density[((int64_t)z * S.gn[1] + y) * S.gn[0] + x];
 }
 
 // GridDensityMedium::Density, grid.cpp:46-60: trilinear over the sample lattice at cell centres
-template <class M>
-__device__ __forceinline__ float grid_density(const M &S, f3 p) {
+__device__ __forceinline__ float grid_density(const DevMedium &S, f3 p) {
     const float sx = p.x * (float)S.gn[0] - .5f, sy = p.y * (float)S.gn[1] - .5f, sz = p.z * (float)S.gn[2] - .5f;
     const int ix = (int)floorf(sx), iy = (int)floorf(sy), iz = (int)floorf(sz);
     const float dx = sx - (float)ix, dy = sy - (float)iy, dz = sz - (float)iz;
@@ -527,8 +518,7 @@ __device__ __forceinline__ float grid_density(const M &S, f3 p) {
 // WorldToMedium(Ray(o, Normalize(d), tMax * |d|)) (grid.cpp:66-67) through
 // Transform::operator()(Ray) (transform.h:251-264, point with error bound :278-299, vector :236-242),
 // then Bounds3f(0, 1)::IntersectP(ray, &t0, &t1) (geometry.h:1386-1408).  Returns false on a miss.
-template <class M>
-__device__ __forceinline__ bool grid_ray(const M &S, f3 o, f3 d, float tmax, f3 &mo, f3 &md, float &t0,
+__device__ __forceinline__ bool grid_ray(const DevMedium &S, f3 o, f3 d, float tmax, f3 &mo, f3 &md, float &t0,
                                          float &t1) {
     const f3 dn = normalize3(d);
     const float tm = tmax * len3(d);
@@ -583,8 +573,8 @@ __device__ __forceinline__ bool grid_ray(const M &S, f3 o, f3 d, float tmax, f3 
 
 // GridDensityMedium::Sample, grid.cpp:62-89: delta tracking.  On an interaction, t is the
 // medium-space distance and the interaction point is rWorld(t) = o + d*t (as the reference).
-template <class M, class Smp>
-__device__ __forceinline__ bool grid_sample(const M &S, Smp &smp, f3 o, f3 d, float tmax, float &t_out) {
+template <class Smp>
+__device__ __forceinline__ bool grid_sample(const DevMedium &S, Smp &smp, f3 o, f3 d, float tmax, float &t_out) {
     f3 mo, md;
     float tmin, tm;
     if (!grid_ray(S, o, d, tmax, mo, md, tmin, tm)) return false;
@@ -601,8 +591,8 @@ __device__ __forceinline__ bool grid_sample(const M &S, Smp &smp, f3 o, f3 d, fl
 }
 
 // GridDensityMedium::Tr, grid.cpp:91-118: ratio tracking with Russian roulette below 0.1
-template <class M, class Smp>
-__device__ __forceinline__ float grid_tr(const M &S, Smp &smp, f3 o, f3 d, float tmax) {
+template <class Smp>
+__device__ __forceinline__ float grid_tr(const DevMedium &S, Smp &smp, f3 o, f3 d, float tmax) {
     f3 mo, md;
     float tmin, tm;
     if (!grid_ray(S, o, d, tmax, mo, md, tmin, tm)) return 1.f;
@@ -623,8 +613,8 @@ __device__ __forceinline__ float grid_tr(const M &S, Smp &smp, f3 o, f3 d, float
 }
 
 // Medium::Tr of the world ray (o, d, tmax) for either medium type
-template <class M, class Smp>
-__device__ __forceinline__ void medium_tr_any(const M &S, Smp &smp, f3 o, f3 d, float tmax, float tr[3]) {
+template <class Smp>
+__device__ __forceinline__ void medium_tr_any(const DevMedium &S, Smp &smp, f3 o, f3 d, float tmax, float tr[3]) {
     if (S.medium == BRE_MEDIUM_GRID) {
         const float t = grid_tr(S, smp, o, d, tmax);
         tr[0] = tr[1] = tr[2] = t;
@@ -634,19 +624,19 @@ __device__ __forceinline__ void medium_tr_any(const M &S, Smp &smp, f3 o, f3 d, 
 }
 
 // Medium::Sample distance decision; on true the interaction point is o + d*t
-template <class M, class Smp>
-__device__ __forceinline__ bool medium_sample_any(const M &S, Smp &smp, f3 o, f3 d, float tmax, float &t) {
+template <class Smp>
+__device__ __forceinline__ bool medium_sample_any(const DevMedium &S, Smp &smp, f3 o, f3 d, float tmax, float &t) {
     if (S.medium == BRE_MEDIUM_GRID) return grid_sample(S, smp, o, d, tmax, t);
     return medium_sample(S, smp, d, tmax, t);
 }
 
-// ---- the medium a ray travels in.  MED false: the scene's one medium (S.medium), `med` unused.  MED true
+// ---- the medium a ray travels in.  MED false: the scene's one medium (S.own), `med` unused.  MED true
 // (bre_set_media): entry `med` of S.media, or vacuum for -1: nothing is drawn and Tr = 1. ----
 template <bool MED, class Smp>
 __device__ __forceinline__ bool ray_medium_sample(const DevScene &S, int med, Smp &smp, f3 o, f3 d, float tmax,
                                                   float &t) {
     if constexpr (MED) return med >= 0 && medium_sample_any(S.media[med], smp, o, d, tmax, t);
-    else return S.medium && medium_sample_any(S, smp, o, d, tmax, t);
+    else return S.own.medium && medium_sample_any(S.own, smp, o, d, tmax, t);
 }
 // tr = Tr of the segment (1 in vacuum)
 template <bool MED, class Smp>
@@ -656,7 +646,7 @@ __device__ __forceinline__ void ray_medium_tr(const DevScene &S, int med, Smp &s
     if constexpr (MED) {
         if (med >= 0) medium_tr_any(S.media[med], smp, o, d, tmax, tr);
     } else {
-        if (S.medium) medium_tr_any(S, smp, o, d, tmax, tr);
+        if (S.own.medium) medium_tr_any(S.own, smp, o, d, tmax, tr);
     }
 }
 // Interaction::GetMedium(w) (interaction.h:86-88) at a point of triangle `tri` reached by a ray in medium
