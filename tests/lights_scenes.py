@@ -15,6 +15,13 @@ import numpy as np
 SPOT_FROM, SPOT_TO, SPOT_I = (0.3, 0.95, 0.4), (0.6, 0.0, 0.7), (12.0, 12.0, 12.0)
 POINT_P, POINT_I = (0.5, 0.9, 0.5), (3.0, 2.5, 2.0)
 NAMES = ("point", "spot", "floor", "mixed", "grid", "blocker")
+# the bit-exact pass tests of tests/test_lights_gpu.py: their scenes, iterations and sizes
+PHOTON_NAMES = ("point", "spot", "floor", "mixed", "grid")
+CAMERA_NAMES = ("point", "mixed", "grid", "blocker", "floor")
+PHOTON_ITERATIONS, CAMERA_ITERATIONS = (0, 2), (0, 3)
+N_PHOTONS, MAX_DEPTH, RADIUS = 256, 5, 0.01
+CAM_W = CAM_H = 16
+CAM_DEPTH = 4
 
 
 def grid_density8():

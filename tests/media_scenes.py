@@ -114,23 +114,3 @@ def apply(g, case):
     g.set_lights(case.lights)
     g.set_media(case.media, case.tri_inside, case.tri_outside, case.camera_medium, case.light_medium)
     g.set_materials(case.materials, case.tri_mat)
-
-
-# The restatement is the slow side (seconds per pass): each reference is computed once per (scene, iteration)
-# and shared by every test of the session; the returned arrays are not to be modified.
-@functools.lru_cache(maxsize=None)
-def photon_ref(name, iteration):
-    import refpy_media as rm
-
-    stats = rm.new_stats()
-    ref = rm.trace_photons(*build(name), N_PHOTONS, iteration, MAX_DEPTH, RADIUS, stats=stats)
-    return ref, stats
-
-
-@functools.lru_cache(maxsize=None)
-def camera_ref(name, iteration):
-    import refpy_media as rm
-
-    stats = rm.new_stats()
-    ref = rm.camera_pass(*build(name), CAM_W, CAM_H, iteration, CAM_DEPTH, stats=stats)
-    return ref, stats

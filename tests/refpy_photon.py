@@ -1,11 +1,12 @@
-"""Independent pure-Python restatement of the photon pass (test infrastructure).
+"""The float32 arithmetic, generators and shape / medium primitives of the pure-Python restatement (test
+infrastructure); the two passes built on them are tests/refpy_passes.py.
 
-Written from the reference text (src/integrators/photonbeam.cpp:258-325, 383-421 and the pbrt
-functions they call), NOT from oracle/bre_oracle_photon.cpp, with every float operation done on
-numpy float32 scalars (IEEE single, like the reference's `Float`) and `Cross` in Python floats
-(double, geometry.h:957-963).  The transcendentals are the host libm's expf / logf / sinf / cosf,
-called through ctypes, as the reference calls them.  Slow (pure Python): used on a few hundred
-photons to pin the C++ oracle.
+Written from the reference text (src/integrators/photonbeam.cpp and the pbrt functions it calls), NOT from
+oracle/bre_oracle_photon.cpp, with every float operation done on numpy float32 scalars (IEEE single, like
+the reference's `Float`) and `Cross` in Python floats (double, geometry.h:957-963).  The transcendentals
+are the host libm's expf / logf / sinf / cosf, called through ctypes, as the reference calls them.  Here:
+PCG32, the vectors, Triangle::Intersect and Triangle::Sample, Henyey-Greenstein, GridDensityMedium, and
+the HaltonSampler.
 """
 from __future__ import annotations
 
@@ -95,6 +96,10 @@ def sub(a, b):
 
 def mul(a, s):
     return tuple(f32(s * x) for x in a)
+
+
+def mul3(a, b):
+    return tuple(f32(x * y) for x, y in zip(a, b))
 
 
 def div(a, s):
@@ -199,163 +204,75 @@ def hg_sample(g, wo, u0, u1):
     return add(add(mul(v1, f32(sin_t * cp)), mul(v2, f32(sin_t * sp))), mul(tuple(-x for x in wo), cos_t))
 
 
-def _gam(n):
-    return gamma(n)
+# ---- Triangle (shapes/triangle.cpp); T is one of refpy_passes.Scene's triangle dicts ----
+def hit_tri(T, o, d, tmax):
+    """Triangle::Intersect (triangle.cpp:177-300): watertight test; (t, p, pError) or None."""
+    p0, p1, p2 = T["p"]
+    ad = vabs(d)
+    kz = (0 if ad[0] > ad[2] else 2) if ad[0] > ad[1] else (1 if ad[1] > ad[2] else 2)
+    kx = 0 if kz + 1 == 3 else kz + 1
+    ky = 0 if kx + 1 == 3 else kx + 1
+
+    def perm(v):
+        return [v[kx], v[ky], v[kz]]
+
+    dd = perm(d)
+    a, b, c = perm(sub(p0, o)), perm(sub(p1, o)), perm(sub(p2, o))
+    sx = f32(-dd[0] / dd[2])
+    sy = f32(-dd[1] / dd[2])
+    sz = f32(f32(1) / dd[2])
+    for v in (a, b, c):
+        v[0] = f32(v[0] + f32(sx * v[2]))
+        v[1] = f32(v[1] + f32(sy * v[2]))
+    e0 = f32(f32(b[0] * c[1]) - f32(b[1] * c[0]))
+    e1 = f32(f32(c[0] * a[1]) - f32(c[1] * a[0]))
+    e2 = f32(f32(a[0] * b[1]) - f32(a[1] * b[0]))
+    if e0 == 0 or e1 == 0 or e2 == 0:
+        e0 = f32(float(c[1]) * float(b[0]) - float(c[0]) * float(b[1]))
+        e1 = f32(float(a[1]) * float(c[0]) - float(a[0]) * float(c[1]))
+        e2 = f32(float(b[1]) * float(a[0]) - float(b[0]) * float(a[1]))
+    if (e0 < 0 or e1 < 0 or e2 < 0) and (e0 > 0 or e1 > 0 or e2 > 0):
+        return None
+    det = f32(f32(e0 + e1) + e2)
+    if det == 0:
+        return None
+    for v in (a, b, c):
+        v[2] = f32(v[2] * sz)
+    ts = f32(f32(f32(e0 * a[2]) + f32(e1 * b[2])) + f32(e2 * c[2]))
+    if det < 0 and (ts >= 0 or ts < f32(tmax * det)):
+        return None
+    if det > 0 and (ts <= 0 or ts > f32(tmax * det)):
+        return None
+    inv = f32(f32(1) / det)
+    b0, b1, b2 = f32(e0 * inv), f32(e1 * inv), f32(e2 * inv)
+    t = f32(ts * inv)
+    mz = max(abs(a[2]), max(abs(b[2]), abs(c[2])))
+    mx = max(abs(a[0]), max(abs(b[0]), abs(c[0])))
+    my = max(abs(a[1]), max(abs(b[1]), abs(c[1])))
+    dz = f32(gamma(3) * mz)
+    dx = f32(gamma(5) * f32(mx + mz))
+    dy = f32(gamma(5) * f32(my + mz))
+    de = f32(f32(2) * f32(f32(f32(f32(gamma(2) * mx) * my) + f32(dy * mx)) + f32(dx * my)))
+    me = max(abs(e0), max(abs(e1), abs(e2)))
+    dt = f32(f32(f32(3) * f32(f32(f32(f32(gamma(3) * me) * mz) + f32(de * mz)) + f32(dz * me))) * abs(inv))
+    if t <= dt:
+        return None
+    sums = [f32(f32(abs(f32(b0 * p0[k])) + abs(f32(b1 * p1[k]))) + abs(f32(b2 * p2[k]))) for k in range(3)]
+    perr = mul(tuple(sums), gamma(7))
+    p = add(add(mul(p0, b0), mul(p1, b1)), mul(p2, b2))
+    return t, p, perr
 
 
-class Scene:
-    def __init__(self, s):
-        # one dict per pbrt Triangle (shapes/triangle.cpp)
-        self.tris = []
-        self.lights = []
-        for i in range(s.n_triangles):
-            t = s.triangles[i]
-            p0, p1, p2 = (tuple(f32(x) for x in t.p[k]) for k in range(3))
-            dp02, dp12 = sub(p0, p2), sub(p1, p2)
-            # dpdu = (duv12[1] * dp02 - duv02[1] * dp12) * invdet with -1, -1, 1 (triangle.cpp:276-285)
-            dpdu = mul(sub(mul(dp02, f32(-1)), mul(dp12, f32(-1))), f32(1))
-            n = normalize(cross(dp02, dp12))
-            ns = normalize(cross(sub(p1, p0), sub(p2, p0)))
-            if t.flip:
-                n = tuple(-x for x in n)
-                ns = tuple(-x for x in ns)
-            ss = normalize(dpdu)
-            area = f32(0.5 * float(length(cross(sub(p1, p0), sub(p2, p0)))))
-            self.tris.append(dict(p=(p0, p1, p2), n=n, ns=ns, ss=ss, ts=cross(n, ss), area=area,
-                                  kd=tuple(f32(x) for x in t.kd), Le=tuple(f32(x) for x in t.Le)))
-            if t.emit:
-                self.lights.append(i)
-        # ComputeLightPowerDistribution: Power() = 1 * Lemit * area * Pi, its y() (diffuse.cpp:64-66)
-        func = []
-        for li in self.lights:
-            T = self.tris[li]
-            pw = tuple(f32(f32(f32(c * f32(1)) * T["area"]) * PI) for c in T["Le"])
-            func.append(f32(f32(f32(f32(0.212671) * pw[0]) + f32(f32(0.715160) * pw[1])) + f32(f32(0.072169) * pw[2])))
-        nl = len(func)
-        cdf = [f32(0)] * (nl + 1)
-        for i in range(1, nl + 1):
-            cdf[i] = f32(cdf[i - 1] + f32(func[i - 1] / f32(nl)))
-        fint = cdf[nl]
-        if fint == 0:
-            cdf = [f32(f32(i) / f32(nl)) for i in range(nl + 1)]
-        else:
-            cdf = [cdf[0]] + [f32(c / fint) for c in cdf[1:]]
-        self.lfunc, self.lcdf, self.lint = func, cdf, fint
-        self.medium = bool(s.has_medium)
-        self.sigma_t = tuple(f32(f32(a) + f32(b)) for a, b in zip(s.sigma_a, s.sigma_s))
-        self.g = f32(s.g)
-        self.grid = s.has_medium == 2
-        if self.grid:  # GridDensityMedium ctor, grid.h:58-77
-            self.n = tuple(int(v) for v in s.grid_n)
-            self.m = [[f32(s.world_to_medium[4 * i + j]) for j in range(4)] for i in range(4)]
-            cnt = self.n[0] * self.n[1] * self.n[2]
-            self.density = np.ctypeslib.as_array((ctypes.c_float * cnt).from_address(s.grid_density)).copy()
-            self.gsig = f32(f32(s.sigma_a[0]) + f32(s.sigma_s[0]))
-            mx = f32(0)
-            for v in self.density:
-                mx = v if mx < v else mx
-            self.inv_max = f32(f32(1) / mx)
-
-    def sample_light(self, u):
-        """Distribution1D::SampleDiscrete (sampling.h:90-100) with FindInterval (pbrt.h:377-389)."""
-        size = len(self.lcdf)
-        first, ln = 0, size
-        while ln > 0:
-            half = ln >> 1
-            mid = first + half
-            if self.lcdf[mid] <= u:
-                first = mid + 1
-                ln -= half + 1
-            else:
-                ln = half
-        off = min(max(first - 1, 0), size - 2)
-        pdf = f32(self.lfunc[off] / f32(self.lint * f32(len(self.lfunc)))) if self.lint > 0 else f32(0)
-        return off, pdf
-
-    @staticmethod
-    def hit_tri(T, o, d, tmax):
-        """Triangle::Intersect (triangle.cpp:177-300): watertight test; (t, p, pError) or None."""
-        p0, p1, p2 = T["p"]
-        ad = vabs(d)
-        kz = (0 if ad[0] > ad[2] else 2) if ad[0] > ad[1] else (1 if ad[1] > ad[2] else 2)
-        kx = 0 if kz + 1 == 3 else kz + 1
-        ky = 0 if kx + 1 == 3 else kx + 1
-
-        def perm(v):
-            return [v[kx], v[ky], v[kz]]
-
-        dd = perm(d)
-        a, b, c = perm(sub(p0, o)), perm(sub(p1, o)), perm(sub(p2, o))
-        sx = f32(-dd[0] / dd[2])
-        sy = f32(-dd[1] / dd[2])
-        sz = f32(f32(1) / dd[2])
-        for v in (a, b, c):
-            v[0] = f32(v[0] + f32(sx * v[2]))
-            v[1] = f32(v[1] + f32(sy * v[2]))
-        e0 = f32(f32(b[0] * c[1]) - f32(b[1] * c[0]))
-        e1 = f32(f32(c[0] * a[1]) - f32(c[1] * a[0]))
-        e2 = f32(f32(a[0] * b[1]) - f32(a[1] * b[0]))
-        if e0 == 0 or e1 == 0 or e2 == 0:
-            e0 = f32(float(c[1]) * float(b[0]) - float(c[0]) * float(b[1]))
-            e1 = f32(float(a[1]) * float(c[0]) - float(a[0]) * float(c[1]))
-            e2 = f32(float(b[1]) * float(a[0]) - float(b[0]) * float(a[1]))
-        if (e0 < 0 or e1 < 0 or e2 < 0) and (e0 > 0 or e1 > 0 or e2 > 0):
-            return None
-        det = f32(f32(e0 + e1) + e2)
-        if det == 0:
-            return None
-        for v in (a, b, c):
-            v[2] = f32(v[2] * sz)
-        ts = f32(f32(f32(e0 * a[2]) + f32(e1 * b[2])) + f32(e2 * c[2]))
-        if det < 0 and (ts >= 0 or ts < f32(tmax * det)):
-            return None
-        if det > 0 and (ts <= 0 or ts > f32(tmax * det)):
-            return None
-        inv = f32(f32(1) / det)
-        b0, b1, b2 = f32(e0 * inv), f32(e1 * inv), f32(e2 * inv)
-        t = f32(ts * inv)
-        mz = max(abs(a[2]), max(abs(b[2]), abs(c[2])))
-        mx = max(abs(a[0]), max(abs(b[0]), abs(c[0])))
-        my = max(abs(a[1]), max(abs(b[1]), abs(c[1])))
-        dz = f32(_gam(3) * mz)
-        dx = f32(_gam(5) * f32(mx + mz))
-        dy = f32(_gam(5) * f32(my + mz))
-        de = f32(f32(2) * f32(f32(f32(f32(_gam(2) * mx) * my) + f32(dy * mx)) + f32(dx * my)))
-        me = max(abs(e0), max(abs(e1), abs(e2)))
-        dt = f32(f32(f32(3) * f32(f32(f32(f32(_gam(3) * me) * mz) + f32(de * mz)) + f32(dz * me))) * abs(inv))
-        if t <= dt:
-            return None
-        sums = [f32(f32(abs(f32(b0 * p0[k])) + abs(f32(b1 * p1[k]))) + abs(f32(b2 * p2[k]))) for k in range(3)]
-        perr = mul(tuple(sums), _gam(7))
-        p = add(add(mul(p0, b0), mul(p1, b1)), mul(p2, b2))
-        return t, p, perr
-
-    def intersect(self, o, d):
-        best = None
-        tmax = INF
-        for i, T in enumerate(self.tris):
-            h = self.hit_tri(T, o, d, tmax)
-            if h is None:
-                continue
-            tmax = h[0]
-            best = (h[1], h[2], i)
-        return best, tmax
-
-    def sample_tri(self, T, u0, u1):
-        """Triangle::Sample (triangle.cpp:543-568): point, pError, normal, area pdf."""
-        su0 = f32(np.sqrt(u0))
-        b0, b1 = f32(f32(1) - su0), f32(u1 * su0)
-        b2 = f32(f32(f32(1) - b0) - b1)
-        p0, p1, p2 = T["p"]
-        a, b, c = mul(p0, b0), mul(p1, b1), mul(p2, b2)
-        p = add(add(a, b), c)
-        perr = mul(add(add(vabs(a), vabs(b)), vabs(c)), _gam(6))
-        return p, perr, T["ns"], f32(f32(1) / T["area"])
-
-    def tr(self, d, tmax):
-        x = f32(tmax * length(d))
-        x = MAXF if MAXF < x else x
-        return tuple(expf(f32(f32(-st) * x)) for st in self.sigma_t)
+def sample_tri(T, u0, u1):
+    """Triangle::Sample (triangle.cpp:543-568): point, pError, normal, area pdf."""
+    su0 = f32(np.sqrt(u0))
+    b0, b1 = f32(f32(1) - su0), f32(u1 * su0)
+    b2 = f32(f32(f32(1) - b0) - b1)
+    p0, p1, p2 = T["p"]
+    a, b, c = mul(p0, b0), mul(p1, b1), mul(p2, b2)
+    p = add(add(a, b), c)
+    perr = mul(add(add(vabs(a), vabs(b)), vabs(c)), gamma(6))
+    return p, perr, T["ns"], f32(f32(1) / T["area"])
 
 
 # ---- GridDensityMedium (grid.cpp:46-118; grid.h:84-88) ----
@@ -454,115 +371,6 @@ def grid_tr(sc, rng, o, d, tmax):
             if rng.uniform() < q:
                 return f32(0)
             tr = f32(tr / f32(f32(1) - q))
-
-
-def trace_photon(sc: Scene, seq: int, max_depth: int, radius: float):
-    """Beams of one photon, in the reference's push order: list of (start, end, radius, power)."""
-    rng = RNG(seq)
-    out = []
-    ln, light_pdf = sc.sample_light(rng.uniform())  # lightDistr->SampleDiscrete
-    u0 = rng.get2d()
-    u1 = rng.get2d()
-    rng.uniform()  # time
-    L = sc.tris[sc.lights[ln]]
-    p, perr, nl, pdf_pos = sc.sample_tri(L, *u0)
-    wl = cosine_hemisphere(*u1)
-    pdf_dir = f32(wl[2] * INV_PI)
-    v1, v2 = coordinate_system(nl)
-    w = add(add(mul(v1, wl[0]), mul(v2, wl[1])), mul(nl, wl[2]))
-    o = offset_origin(p, perr, nl, w)
-    Le = L["Le"] if dot(nl, w) > 0 else (f32(0),) * 3
-    if pdf_pos == 0 or pdf_dir == 0 or all(x == 0 for x in Le):
-        return out
-    ad = f32(abs(dot(nl, w)))
-    den = f32(f32(light_pdf * pdf_pos) * pdf_dir)
-    beta = tuple(f32(f32(ad * x) / den) for x in Le)
-    if all(x == 0 for x in beta):
-        return out
-
-    def rec(o, d, depth, beta):
-        while depth < max_depth:
-            hit, tmax = sc.intersect(o, d)
-            if hit is None:
-                return
-            scattered = False
-            if sc.medium and sc.grid:
-                t = grid_sample(sc, rng, o, d, tmax)
-                scattered = t is not None
-            elif sc.medium:
-                ch = min(int(f32(rng.uniform() * f32(3))), 2)
-                dist = f32(-logf(f32(f32(1) - rng.uniform())) / sc.sigma_t[ch])
-                dl = f32(dist * length(d))
-                t = tmax if tmax < dl else dl
-                scattered = bool(t < tmax)
-            if all(x == 0 for x in beta):
-                return
-            if scattered:
-                hx, hy = rng.get2d()
-                wi = hg_sample(sc.g, tuple(-x for x in d), hx, hy)
-                trv = (grid_tr(sc, rng, o, d, tmax),) * 3 if sc.grid else sc.tr(d, tmax)
-                rec(add(o, mul(d, t)), wi, depth + 1, tuple(f32(b * x) for b, x in zip(beta, trv)))
-            if sc.medium and sc.grid:
-                bm = (grid_tr(sc, rng, o, d, tmax),) * 3
-            else:
-                bm = sc.tr(d, tmax) if sc.medium else (f32(1),) * 3
-            out.append((o, hit[0], f32(radius), tuple(f32(a * b) for a, b in zip(bm, beta))))
-            q = sc.tris[hit[2]]
-            ux, uy = rng.get2d()
-            if all(x == 0 for x in q["kd"]):
-                return
-            wo = tuple(-x for x in d)
-            woz = dot(wo, q["n"])
-            if woz == 0:
-                return
-            wil = list(cosine_hemisphere(ux, uy))
-            if woz < 0:
-                wil[2] = f32(wil[2] * f32(-1))
-            pdf = f32(abs(wil[2]) * INV_PI) if f32(woz * wil[2]) > 0 else f32(0)
-            fr = tuple(f32(k * INV_PI) for k in q["kd"])
-            if pdf == 0 or all(x == 0 for x in fr):
-                return
-            ss, ts, n = q["ss"], q["ts"], q["n"]
-            wi = tuple(f32(f32(f32(ss[i] * wil[0]) + f32(ts[i] * wil[1])) + f32(n[i] * wil[2])) for i in range(3))
-            adw = f32(abs(dot(wi, n)))
-            bn = tuple(f32(f32(f32(f32(bm[c] * beta[c]) * fr[c]) * adw) / pdf) for c in range(3))
-            o = offset_origin(hit[0], hit[1], n, wi)
-            d = wi
-
-            def y(s):
-                return f32(f32(f32(f32(0.212671) * s[0]) + f32(f32(0.715160) * s[1])) + f32(f32(0.072169) * s[2]))
-
-            ratio = f32(f32(1) - f32(y(bn) / y(beta)))
-            qrr = ratio if f32(0) < ratio else f32(0)
-            if rng.uniform() < qrr:
-                return
-            beta = tuple(f32(x / f32(f32(1) - qrr)) for x in bn)
-            depth += 1
-
-    rec(o, w, 0, beta)
-    return out
-
-
-def trace_photons(scene_struct, n_photons, iteration=0, max_depth=5, radius=0.01, first=None):
-    """Photons [0, first or n_photons) of a pass of n_photons (sequences iteration*N + i + 1)."""
-    sc = Scene(scene_struct)
-    beams = []
-    counts = []
-    for i in range(first if first is not None else n_photons):
-        b = trace_photon(sc, iteration * n_photons + i + 1, max_depth, radius)
-        counts.append(len(b))
-        beams.extend(b)
-    n = len(beams)
-    arr = {"start": np.zeros((n, 3), np.float32), "end": np.zeros((n, 3), np.float32),
-           "radius": np.zeros(n, np.float32), "power": np.zeros((n, 3), np.float32)}
-    for k, (s, e, r, pw) in enumerate(beams):
-        arr["start"][k] = s
-        arr["end"][k] = e
-        arr["radius"][k] = r
-        arr["power"][k] = pw
-    arr["counts"] = np.array(counts, np.int32)
-    return arr
-
 
 
 # ---- HaltonSampler restated (src/samplers/halton.cpp:63-127, lowdiscrepancy.cpp) ----

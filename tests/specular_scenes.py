@@ -95,23 +95,3 @@ def build(name):
     materials, tri_mat = sm.scene_materials(meshes)
     assert scene.n_triangles <= 40
     return scene, lights, materials, tri_mat
-
-
-# The restatement is the slow side (seconds per pass): each reference is computed once per (scene, iteration)
-# and shared by every test of the session; the returned arrays are not to be modified.
-@functools.lru_cache(maxsize=None)
-def photon_ref(name, iteration):
-    import refpy_specular as rs
-
-    stats = rs.new_stats()
-    ref = rs.trace_photons(*build(name), N_PHOTONS, iteration, MAX_DEPTH, RADIUS, stats=stats)
-    return ref, stats
-
-
-@functools.lru_cache(maxsize=None)
-def camera_ref(name, iteration):
-    import refpy_specular as rs
-
-    stats = rs.new_stats()
-    ref = rs.camera_pass(*build(name), CAM_W, CAM_H, iteration, CAM_DEPTH, stats=stats)
-    return ref, stats

@@ -1,9 +1,10 @@
-"""Point and spot lights on the GPU (bre_set_lights) against the pure-Python float32 restatements
-tests/refpy_lights.py (photon pass) and tests/refpy_camera.py (camera pass), bit for bit, and the
+"""Point and spot lights on the GPU (bre_set_lights) against the pure-Python float32 restatement
+tests/refpy_passes.py (photon pass and camera pass), bit for bit, and the
 whole iteration, the context walk, the sharded render and the .pbrt front end to the project's image bar
 (relative L2 <= 1e-5, every pixel above 1e-3 of the maximum within 1e-4).
 
-The restatements are the slow side: each reference is computed once per (scene, iteration) and shared.
+The restatement is the slow side: each reference is computed once per (scene, iteration) and shared
+(tests/pass_refs.py).
 """
 import functools
 import importlib
@@ -12,11 +13,12 @@ import numpy as np
 import pytest
 
 import lights_scenes as ls
-import refpy_lights as rl
+import pass_refs
+import refpy_passes as rpass
+from lights_scenes import CAM_DEPTH, CAM_H, CAM_W, MAX_DEPTH, N_PHOTONS, RADIUS
 
 pytestmark = pytest.mark.gpu
 
-N_PHOTONS, MAX_DEPTH, RADIUS = 256, 5, 0.01
 BEAM_KEYS = ("start", "end", "radius", "power")
 
 
@@ -25,26 +27,17 @@ def scene_of(name):
     return ls.build(name)
 
 
-@functools.lru_cache(maxsize=None)
-def photon_ref(name, iteration):
-    scene, lights = scene_of(name)
-    infos = []
-    ref = rl.trace_photons(scene, lights, N_PHOTONS, iteration, MAX_DEPTH, RADIUS, infos=infos)
-    ref["infos"] = infos
-    return ref
-
-
 def bits(a):
     return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 # ---------------- 1. photon pass ----------------
 @pytest.mark.parametrize("form", [1, 2, 0], ids=["default", "two-slot", "two-trace"])
-@pytest.mark.parametrize("iteration", [0, 2])
-@pytest.mark.parametrize("name", ["point", "spot", "floor", "mixed", "grid"])
+@pytest.mark.parametrize("iteration", ls.PHOTON_ITERATIONS)
+@pytest.mark.parametrize("name", ls.PHOTON_NAMES)
 def test_photon_pass_bit_exact(bre, name, iteration, form):
     scene, lights = scene_of(name)
-    ref = photon_ref(name, iteration)
+    ref, _ = pass_refs.photon_ref(ls, name, iteration)
     infos = ref["infos"]
     if name == "spot":  # the cone's flat part and its falloff band are both exercised
         fo = [float(i["falloff"]) for i in infos]
@@ -71,21 +64,6 @@ def test_photon_pass_bit_exact(bre, name, iteration, form):
 
 
 # ---------------- 2. camera pass ----------------
-CAM_W = CAM_H = 16
-CAM_DEPTH = 4
-
-
-@functools.lru_cache(maxsize=None)
-def camera_ref(name, iteration):
-    import refpy_camera as rc
-
-    scene, lights = scene_of(name)
-    stats = {}
-    ref = rc.camera_pass(scene, lights, CAM_W, CAM_H, iteration, CAM_DEPTH, stats=stats)
-    ref["stats"] = stats
-    return ref
-
-
 def _sorted(seg):
     order = np.lexsort((seg["depth"], seg["pixel"]))
     return {k: seg[k][order] for k in ("o", "p", "d", "tmax", "pixel", "depth")}
@@ -105,15 +83,15 @@ def _camera(bre, scene, lights, iteration):
     return seg
 
 
-@pytest.mark.parametrize("iteration", [0, 3])
-@pytest.mark.parametrize("name", ["point", "mixed", "grid", "blocker", "floor"])
+@pytest.mark.parametrize("iteration", ls.CAMERA_ITERATIONS)
+@pytest.mark.parametrize("name", ls.CAMERA_NAMES)
 def test_camera_pass_bit_exact(bre, name, iteration):
     """Segments (a missing shadow-ray Tr in the grid medium would shift the sampler's dimensions and so
     the bounce segments) and surface radiance, bit for bit."""
     scene, lights = scene_of(name)
-    ref = camera_ref(name, iteration)
+    ref, stats = pass_refs.camera_ref(ls, name, iteration)
     if name == "blocker":  # some shadow rays are blocked, some reach the light
-        assert ref["stats"]["shadow_blocked"] > 0 and ref["stats"]["shadow_clear"] > 0
+        assert stats["shadow_blocked"] > 0 and stats["shadow_clear"] > 0
     if name == "floor":  # camera rays that miss the quad leave their pixels at 0
         assert 0 < len(set(ref["pixel"].tolist())) < CAM_W * CAM_H
         assert (ref["surface"].max(axis=1) == 0).any() and ref["surface"].max() > 0
@@ -150,14 +128,13 @@ def _render_iteration(bre, g, scene, params):
 
 
 def test_render_iteration_spot_fog(bre, oracle, scene_mod_gpu):
-    import refpy_camera as rc
-
     scene, lights = scene_of("spot")
     w = h = 32
     R = 0.05
     p = scene_mod_gpu.render_params(w, h, iterations=1, photons=2000, max_depth=5, radius=R, alpha=0.5)
-    beams = rl.trace_photons(scene, lights, 2000, 0, 5, R)
-    cam = rc.camera_pass(scene, lights, w, h, 0, 5)
+    sc = pass_refs.scene(ls, "spot")
+    beams = rpass.trace_photons(sc, 2000, 0, 5, R)
+    cam = rpass.camera_pass(sc, w, h, 0, 5)
     bf = oracle.bruteforce(beams, cam, R)
     ref = cam["surface"].astype(np.float64)
     np.add.at(ref, cam["pixel"], bf["seg_rgb_exact"])

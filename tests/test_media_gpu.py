@@ -1,15 +1,16 @@
 """Media bounded by surfaces on the GPU (bre_set_media, BRE_MATERIAL_INTERFACE) against the pure-Python float32
-restatement tests/refpy_media.py, bit for bit: the photon pass in its three forms and the camera pass on the
+restatement tests/refpy_passes.py, bit for bit: the photon pass in its three forms and the camera pass on the
 scenes of tests/media_scenes.py.  The whole iteration, the context walk and the sharded render are held to the
 project's image bar (relative L2 <= 1e-5, every pixel above 1e-3 of the maximum within 1e-4).
 
-The restatement is the slow side: media_scenes computes each reference once per (scene, iteration).
+The restatement is the slow side: tests/pass_refs.py computes each reference once per (scene, iteration).
 """
 import numpy as np
 import pytest
 
 import media_scenes as ms
-import refpy_media as rm
+import pass_refs
+import refpy_passes as rpass
 
 pytestmark = pytest.mark.gpu
 
@@ -39,7 +40,7 @@ def assert_image_bar(got, ref, l2=1e-5):
 @pytest.mark.parametrize("name", ms.NAMES)
 def test_photon_pass_bit_exact(bre, name, iteration, form):
     case = ms.build(name)
-    ref, _ = ms.photon_ref(name, iteration)
+    ref, _ = pass_refs.photon_ref(ms, name, iteration)
     with bre.BeamGather(0) as g:
         g.set_option(116, form)
         ms.apply(g, case)
@@ -87,7 +88,7 @@ def test_camera_pass_bit_exact(bre, name, iteration):
     """The set of segments, each with its ordinal along the pixel's path, and the surface radiance, bit for bit:
     pixels with more segments than maxdepth included (the default budget holds `slab`'s three crossings)."""
     case = ms.build(name)
-    ref, _ = ms.camera_ref(name, iteration)
+    ref, _ = pass_refs.camera_ref(ms, name, iteration)
     with bre.BeamGather(0) as g:
         ms.apply(g, case)
         gpu, surf = _camera(g, case, iteration)
@@ -114,8 +115,9 @@ def test_render_iteration_nested(bre, oracle, scene_mod_gpu):
     w = h = 32
     R = 0.05
     p = scene_mod_gpu.render_params(w, h, iterations=1, photons=3000, max_depth=5, radius=R, alpha=0.5)
-    beams = rm.trace_photons(*case, 3000, 0, 5, R)
-    cam = rm.camera_pass(*case, w, h, 0, 5)
+    sc = pass_refs.scene(ms, "nested")
+    beams = rpass.trace_photons(sc, 3000, 0, 5, R)
+    cam = rpass.camera_pass(sc, w, h, 0, 5)
     bf = oracle.bruteforce(beams, cam, R)
     ref = cam["surface"].astype(np.float64)
     np.add.at(ref, cam["pixel"], bf["seg_rgb_exact"])
@@ -142,7 +144,7 @@ def test_segment_budget_overrun_is_reported(bre):
         ms.apply(g, box)
         g.set_option(bre.OPT_SEGMENT_BUDGET, 16)
         gpu, surf = _camera(g, box, 0)
-        assert_camera_equal(gpu, surf, ms.camera_ref("box", 0)[0])
+        assert_camera_equal(gpu, surf, pass_refs.camera_ref(ms, "box", 0)[0])
         for bad in (-1, 241):
             with pytest.raises(bre.BreError):
                 g.set_option(bre.OPT_SEGMENT_BUDGET, bad)

@@ -1,6 +1,6 @@
-"""Media bounded by surfaces without a GPU: the restatement tests/refpy_media.py against the restatement it is
-built on, hand-derived known answers of the pass-through, the condition that the scenes of the GPU tests reach
-every branch, and the Python view of the media."""
+"""Media bounded by surfaces without a GPU: the restatement (tests/refpy_passes.py) with a media table of one
+against the scene's own medium, hand-derived known answers of the pass-through, the condition that the scenes of
+the GPU tests reach every branch, and the Python view of the media."""
 import ctypes
 import importlib
 
@@ -8,8 +8,9 @@ import numpy as np
 import pytest
 
 import media_scenes as ms
+import pass_refs
 import refpy_media as rm
-import refpy_specular as rs
+import refpy_passes as rpass
 import specular_scenes as ss
 from refpy_photon import RNG, expf, offset_origin
 
@@ -25,7 +26,7 @@ def bits(a):
     return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
-# ---------------- a table of one, no transition anywhere, is the one-medium restatement ----------------
+# ---------------- a table of one, no transition anywhere, is the scene's own medium ----------------
 @pytest.mark.parametrize("name", ["prism", "grid"])
 def test_one_entry_table_equals_the_specular_restatement(sm, name):
     scene, lights, mats, tri_mat = ss.build(name)
@@ -40,16 +41,17 @@ def test_one_entry_table_equals_the_specular_restatement(sm, name):
     bare = type(scene).from_buffer_copy(scene)
     bare.has_medium = sm.MEDIUM_NONE
     media = ([medium], [0] * n, [0] * n, 0, [0] * len(lights))
+    own, tabled = rpass.Scene(scene, lights, mats, tri_mat), rpass.Scene(bare, lights, mats, tri_mat, *media)
     for it in (0, 2):
-        want = rs.trace_photons(scene, lights, mats, tri_mat, 150, it, 5, 0.01)
-        stats = rm.new_stats()
-        got = rm.trace_photons(bare, lights, mats, tri_mat, *media, 150, it, 5, 0.01, stats=stats)
+        want = rpass.trace_photons(own, 150, it, 5, 0.01)
+        stats = rpass.new_stats()
+        got = rpass.trace_photons(tabled, 150, it, 5, 0.01, stats=stats)
         assert np.array_equal(got["counts"], want["counts"]) and want["counts"].sum() > 100
         for k in ("start", "end", "radius", "power"):
             assert np.array_equal(bits(got[k]), bits(want[k])), (name, it, k)
-        assert not any(stats[k] for k in rm.COUNTERS)
-    want = rs.camera_pass(scene, lights, mats, tri_mat, 10, 10, 1, 4)
-    got = rm.camera_pass(bare, lights, mats, tri_mat, *media, 10, 10, 1, 4)
+        assert not any(stats[k] for k in rpass.MEDIA_COUNTERS)
+    want = rpass.camera_pass(own, 10, 10, 1, 4)
+    got = rpass.camera_pass(tabled, 10, 10, 1, 4)
     for k in ("o", "p", "d", "tmax", "surface"):
         assert np.array_equal(bits(got[k]), bits(want[k])), (name, k)
     assert np.array_equal(got["pixel"], want["pixel"]) and np.array_equal(got["depth"], want["depth"])
@@ -82,7 +84,7 @@ def slab_case(sm):
 
 def test_photon_through_a_slab_makes_three_beams(sm):
     case = slab_case(sm)
-    sc = rm.Scene(*case)
+    sc = rpass.Scene(*case)
     assert all(t["n"] == (f32(-1), f32(0), f32(0)) for t in sc.tris) and sc.iface == [True] * 4 + [False] * 2
     o, d = (f32(0), f32(0.5), f32(0.25)), (f32(1), f32(0), f32(0))
     beta = (f32(2), f32(3), f32(4))
@@ -96,9 +98,9 @@ def test_photon_through_a_slab_makes_three_beams(sm):
     assert (h1[2] // 2, h2[2] // 2, h3[2] // 2) == (0, 1, 2)
     assert o2[0] > h1[0][0] and o3[0] > h2[0][0] and abs(float(L) - (X1 - X0)) < 1e-6
     seq = next(s for s in range(1, 50) if rm.med_sample(sc.media[0], RNG(s), o2, d, L) is None)  # no scattering event
-    stats = rm.new_stats()
+    stats = rpass.new_stats()
     rng, out = RNG(seq), []
-    rm.walk(sc, rng, out, o, d, 0, beta, -1, 5, 0.01, stats)
+    rpass.walk(sc, rng, out, o, d, 0, beta, -1, 5, 0.01, stats)
     assert len(out) == 3 and stats["photon_pass"] == 2 and stats["vacuum_segment"] == 2
     assert [b[0] for b in out] == [o, o2, o3] and [b[1] for b in out] == [h1[0], h2[0], h3[0]]
     tr = expf(f32(f32(-sigma_t) * L))
@@ -114,8 +116,8 @@ def test_photon_through_a_slab_makes_three_beams(sm):
 
 def test_camera_path_through_a_slab_has_three_segments_at_depth_zero(sm):
     case = slab_case(sm)
-    stats = rm.new_stats()
-    out = rm.camera_pass(*case, 1, 1, 0, 1, stats=stats)  # maxdepth 1: everything happens at depth 0
+    stats = rpass.new_stats()
+    out = rpass.camera_pass(rpass.Scene(*case), 1, 1, 0, 1, stats=stats)  # maxdepth 1: everything happens at depth 0
     assert out["o"].shape[0] == 3 and list(out["depth"]) == [0, 1, 2] and list(out["pixel"]) == [0, 0, 0]
     assert stats["camera_pass"] == 2 and stats["vacuum_segment"] == 2 and stats["camera_pass_roulette"] == 0
     assert np.allclose(out["p"][:, 0], [X0, X1, 1.0], atol=1e-6) and (out["o"][1:, 0] > out["p"][:-1, 0]).all()
@@ -127,25 +129,25 @@ def test_camera_path_through_a_slab_has_three_segments_at_depth_zero(sm):
     assert X1 - X0 - 1e-6 <= float(x) <= (X1 - X0) / np.cos(np.radians(15.0))  # the pixel's ray is oblique
     assert np.array_equal(bits(out["surface"][0]), bits(np.array([f32(tr * f32(v)) for v in LE], np.float32)))
     # with rendersurfaces off the path still passes through the interfaces and ends at the first BSDF
-    off = rm.camera_pass(*case, 1, 1, 0, 1, render_surfaces=False)
+    off = rpass.camera_pass(rpass.Scene(*case), 1, 1, 0, 1, render_surfaces=False)
     assert off["o"].shape[0] == 3 and not off["surface"].any()
 
 
 # ---------------- the scenes of the GPU tests reach every branch ----------------
 def test_gpu_scenes_take_every_branch_at_least_20_times():
-    total = rm.new_stats()
+    total = rpass.new_stats()
     over = {}
     for name in ms.NAMES:
         assert ms.build(name).scene.n_triangles <= 60
         for it in ms.PHOTON_ITERATIONS:
-            for k, v in ms.photon_ref(name, it)[1].items():
+            for k, v in pass_refs.photon_ref(ms, name, it)[1].items():
                 total[k] += v
         for it in ms.CAMERA_ITERATIONS:
-            ref, stats = ms.camera_ref(name, it)
+            ref, stats = pass_refs.camera_ref(ms, name, it)
             for k, v in stats.items():
                 total[k] += v
             over[name, it] = int((np.bincount(ref["pixel"]) > ms.CAM_DEPTH).sum())
-    for k in rm.COUNTERS:
+    for k in rpass.MEDIA_COUNTERS:
         assert total[k] >= 20, (k, total)
     # pixels whose path records more segments than maxdepth: the camera pass needs its segment budget
     assert all(over[name, it] > 0 for name in ("box", "camera_in") for it in ms.CAMERA_ITERATIONS), over

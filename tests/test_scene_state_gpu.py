@@ -1,9 +1,8 @@
 """One context walked through every kind of sticky scene state (bre_set_lights, bre_set_media,
 bre_set_materials): set, replaced and cleared in turn.  At every stop the photon pass's beams and the camera
-pass's segments and surface radiance equal, bit for bit, the pure-Python restatement of that state (refpy_media
-while media are held, else refpy_lights / refpy_photon with refpy_camera); no image is rendered and no run of
-the library is compared with another.  Then bre_render_sharded refuses two contexts of one device whose states
-differ in one part, naming that part's setter.
+pass's segments and surface radiance equal, bit for bit, the pure-Python restatement of that state
+(tests/refpy_passes.py); no image is rendered and no run of the library is compared with another.  Then
+bre_render_sharded refuses two contexts of one device whose states differ in one part, naming that part's setter.
 
 The triangles are media_scenes' `area` (an area light, an interface box, an opaque quad: 28 triangles) with
 lights_scenes' spot added, so that every stop has a light.  While the context holds media the scene has no
@@ -90,22 +89,16 @@ def walked(bre):
     return out
 
 
-def restatement(scene, lights, materials, tri_mat, media, iteration):
-    import refpy_camera as rc
-    import refpy_lights as rl
-    import refpy_media as rm
-    import refpy_photon as rp
+@functools.lru_cache(maxsize=None)
+def restatement(stop):
+    """Both passes of the state at `stop`, computed once per session (tests/test_refpy_golden.py pins them too)."""
+    import refpy_passes as rpass
 
-    if media is not None:
-        state = (scene, lights, materials, tri_mat) + tuple(media)
-        return (rm.trace_photons(*state, N_PHOTONS, iteration, MAX_DEPTH, RADIUS),
-                rm.camera_pass(*state, W, H, iteration, MAX_DEPTH))
-    assert not materials  # an interface entry never outlives the media
-    if lights:
-        beams = rl.trace_photons(scene, lights, N_PHOTONS, iteration, MAX_DEPTH, RADIUS)
-    else:
-        beams = rp.trace_photons(scene, N_PHOTONS, iteration, MAX_DEPTH, RADIUS)
-    return beams, rc.camera_pass(scene, lights, W, H, iteration, MAX_DEPTH)
+    scene, lights, materials, tri_mat, media, iteration = stops()[stop][2:]
+    assert media is not None or not materials  # an interface entry never outlives the media
+    sc = rpass.Scene(scene, lights, materials, tri_mat, *(media or ()))
+    return (rpass.trace_photons(sc, N_PHOTONS, iteration, MAX_DEPTH, RADIUS),
+            rpass.camera_pass(sc, W, H, iteration, MAX_DEPTH))
 
 
 def sorted_segments(seg):
@@ -116,7 +109,7 @@ def sorted_segments(seg):
 @pytest.mark.parametrize("stop", range(N_STOPS))
 def test_walk_stop_equals_its_restatement(walked, stop):
     what = stops()[stop][0]
-    ref_beams, ref_cam = restatement(*stops()[stop][2:])
+    ref_beams, ref_cam = restatement(stop)
     nb, beams, ns, seg, surf = walked[stop]
     assert nb == int(ref_beams["counts"].sum()) and nb > 0, what
     for k in BEAM_KEYS:

@@ -1,10 +1,10 @@
 """Mirror and glass on the GPU (bre_set_materials, bre_device_check kind 12) against the pure-Python float32
-restatement tests/refpy_specular.py, bit for bit: the lobe on its own, the photon pass and the camera pass
+restatement (tests/refpy_specular.py, tests/refpy_passes.py), bit for bit: the lobe on its own, the two passes
 on the scenes of tests/specular_scenes.py.  The whole iteration, the context walk, the sharded render and
 the .pbrt front end are held to the project's image bar (relative L2 <= 1e-5, every pixel
 above 1e-3 of the maximum within 1e-4).
 
-The restatement is the slow side: specular_scenes computes each reference once per (scene, iteration).
+The restatement is the slow side: tests/pass_refs.py computes each reference once per (scene, iteration).
 """
 import importlib
 import os
@@ -12,6 +12,8 @@ import os
 import numpy as np
 import pytest
 
+import pass_refs
+import refpy_passes as rpass
 import refpy_specular as rs
 import specular_scenes as ss
 from refpy_photon import ONE_MINUS_EPS
@@ -96,7 +98,7 @@ def test_specular_lobe_bit_exact(bre):
 @pytest.mark.parametrize("name", ss.NAMES)
 def test_photon_pass_bit_exact(bre, name, iteration, form):
     scene, lights, mats, tri_mat = ss.build(name)
-    ref, _ = ss.photon_ref(name, iteration)
+    ref, _ = pass_refs.photon_ref(ss, name, iteration)
     with bre.BeamGather(0) as g:
         g.set_option(116, form)
         g.set_lights(lights)
@@ -127,7 +129,7 @@ def test_camera_pass_bit_exact(bre, name, iteration):
     import torch
 
     scene, lights, mats, tri_mat = ss.build(name)
-    ref, _ = ss.camera_ref(name, iteration)
+    ref, _ = pass_refs.camera_ref(ss, name, iteration)
     surf = torch.zeros((ss.CAM_W * ss.CAM_H, 3), dtype=torch.float32, device="cuda")
     with bre.BeamGather(0) as g:
         g.set_lights(lights)
@@ -158,8 +160,9 @@ def test_render_iteration_prism(bre, oracle, scene_mod_gpu):
     w = h = 32
     R = 0.05
     p = scene_mod_gpu.render_params(w, h, iterations=1, photons=3000, max_depth=5, radius=R, alpha=0.5)
-    beams = rs.trace_photons(scene, lights, mats, tri_mat, 3000, 0, 5, R)
-    cam = rs.camera_pass(scene, lights, mats, tri_mat, w, h, 0, 5)
+    sc = pass_refs.scene(ss, "prism")
+    beams = rpass.trace_photons(sc, 3000, 0, 5, R)
+    cam = rpass.camera_pass(sc, w, h, 0, 5)
     bf = oracle.bruteforce(beams, cam, R)
     ref = cam["surface"].astype(np.float64)
     np.add.at(ref, cam["pixel"], bf["seg_rgb_exact"])

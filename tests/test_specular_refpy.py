@@ -1,6 +1,6 @@
-"""Mirror and glass without a GPU: the restatement tests/refpy_specular.py against the restatements it is
-built on, hand-derived known answers of its lobe, the condition that the scenes of the GPU tests reach every
-branch, and the .pbrt front end and Python view of the materials."""
+"""Mirror and glass without a GPU: the restatement (tests/refpy_passes.py) with an all-matte material map against
+none at all, hand-derived known answers of the lobe (tests/refpy_specular.py), the condition that the scenes of
+the GPU tests reach every branch, and the .pbrt front end and Python view of the materials."""
 import ctypes
 import importlib
 import math
@@ -10,8 +10,8 @@ import numpy as np
 import pytest
 
 import lights_scenes as ls
-import refpy_camera as rc
-import refpy_lights as rl
+import pass_refs
+import refpy_passes as rpass
 import refpy_specular as rs
 import specular_scenes as ss
 from refpy_photon import ONE_MINUS_EPS
@@ -35,22 +35,23 @@ def bits(a):
     return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
-# ---------------- the restatement without a material is the restatement it is built on ----------------
+# ---------------- a table no triangle uses is no table ----------------
 @pytest.mark.parametrize("name", ["spot", "mixed", "grid"])
 def test_all_matte_map_equals_the_light_restatements(sm, name):
     scene, lights = ls.build(name)
     table, tri_mat = [sm.mirror(0.9), sm.glass()], [-1] * scene.n_triangles
+    plain, mapped = rpass.Scene(scene, lights), rpass.Scene(scene, lights, table, tri_mat)
     for it in (0, 2):
-        want = rl.trace_photons(scene, lights, 150, it, 5, 0.01)
-        stats = rs.new_stats()
-        got = rs.trace_photons(scene, lights, table, tri_mat, 150, it, 5, 0.01, stats=stats)
+        want = rpass.trace_photons(plain, 150, it, 5, 0.01)
+        stats = rpass.new_stats()
+        got = rpass.trace_photons(mapped, 150, it, 5, 0.01, stats=stats)
         assert np.array_equal(got["counts"], want["counts"]) and want["counts"].sum() > 100
         for k in ("start", "end", "radius", "power"):
             assert np.array_equal(bits(got[k]), bits(want[k])), (name, it, k)
         assert not any(stats.values())
-    want = rc.camera_pass(scene, lights, 10, 10, 1, 4)
+    want = rpass.camera_pass(plain, 10, 10, 1, 4)
     for materials, m in ((table, tri_mat), ((), ())):
-        got = rs.camera_pass(scene, lights, materials, m, 10, 10, 1, 4)
+        got = rpass.camera_pass(rpass.Scene(scene, lights, materials, m), 10, 10, 1, 4)
         for k in ("o", "p", "d", "tmax", "surface"):
             assert np.array_equal(bits(got[k]), bits(want[k])), (name, k)
         assert np.array_equal(got["pixel"], want["pixel"]) and np.array_equal(got["depth"], want["depth"])
@@ -158,17 +159,17 @@ def test_scenes_are_small_and_boxes_face_outward():
 
 
 def test_every_branch_is_taken_at_least_20_times():
-    total = rs.new_stats()
+    total = rpass.new_stats()
     for name in ss.NAMES:
         for it in ss.PHOTON_ITERATIONS:
-            for k, v in ss.photon_ref(name, it)[1].items():
+            for k, v in pass_refs.photon_ref(ss, name, it)[1].items():
                 total[k] += v
     for name in ss.CAMERA_NAMES:
         for it in ss.CAMERA_ITERATIONS:
-            for k, v in ss.camera_ref(name, it)[1].items():
+            for k, v in pass_refs.camera_ref(ss, name, it)[1].items():
                 total[k] += v
     print(total)
-    for k in rs.COUNTERS:
+    for k in rpass.MATERIAL_COUNTERS:
         if k != "refract_fail":
             assert total[k] >= 20, (k, total)
 
