@@ -72,7 +72,7 @@ class Stats(ctypes.Structure):
                 ("photon_ms", ctypes.c_double),
                 ("n_camera_segments", ctypes.c_int64),
                 ("camera_ms", ctypes.c_double), ("n_chunks", ctypes.c_int64),
-                ("queued_pairs", ctypes.c_int64)]
+                ("queued_pairs", ctypes.c_int64), ("tile_variant", ctypes.c_int64)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}

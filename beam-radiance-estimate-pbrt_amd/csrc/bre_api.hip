@@ -195,6 +195,10 @@ const IntOption kIntOptions[] = {
     // 0's device in place and stages only the other devices' through hipMemcpyPeerAsync / 1 stages every non-root
     // source (tests: the cross-device path on one GPU)
     {122, &bre_ctx::stage_all, 0, 1, "collective staging must be 0 or 1"},
+    // internal: the tile kernel's specialised production instantiation (TileProd, bre_gather.hip), 1 allowed
+    // (default) whenever a launch's bound options and beam set match it / 0 always the generic one (A/B).
+    // bre_stats::tile_variant reports which one the last gather ran.
+    {123, &bre_ctx::tile_spec, 0, 1, "tile specialisation must be 0 or 1"},
 };
 }  // namespace
 

@@ -165,6 +165,9 @@ bre_status gather_device(bre_ctx *c, int64_t nseg, const SegView &seg, float R, 
     a.tscan = c->tscan >= 0 ? c->tscan : tscan_for(R + c->bset.radius);
     a.margin = c->margin;
     a.stack_cap = c->stack_cap;
+    a.tile_spec = c->tile_spec;
+    c->stats.tile_variant = 0;
+    a.tile_variant = &c->stats.tile_variant;
     c->stats.n_segments = nseg;
     if (c->nvalid == 0) {
         // empty PhotonBeamBVH: Intersect returns nothing (photonbeambvh.cpp:687)

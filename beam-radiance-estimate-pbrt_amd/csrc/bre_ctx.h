@@ -218,7 +218,7 @@ struct bre_ctx {
     int64_t partial_cap = (int64_t)4 << 30;                                            // 109, in bytes
     int beam_key = 2, margin = 1, tile_axis = 1, split_records = 0, film_compose = 1;  // 110 .. 114
     int photon_single = 1, pass_priority = 1, kernel_readback = BRE_KERNEL_READBACK;   // 116 .. 118
-    int slot_passes = 1, coarse_keys = 0, stage_all = 0;                               // 119, 121, 122
+    int slot_passes = 1, coarse_keys = 0, stage_all = 0, tile_spec = 1;                // 119, 121, 122, 123
     // beam set
     int64_t nbeams = 0, nvalid = 0, nnodes = 0;
     bre::BeamSet bset;  // the built set's radius layout (BeamRec)

@@ -415,6 +415,9 @@ struct TileShared {
 // The exact stage for n queued prefilter survivors q[first, first + n) (one per lane; all lanes
 // call): the reference's box test on the beam's (group) box, then ComputeClosestPoints + kernel.
 // The pair's segment comes from its SegRec, the beam line from L2.
+// UNI: the set is known to be uniform-radius at compile time (the specialised instantiation of
+// k_gather_tile): radius and power come from `bset` and the record, and no `pw` load path exists.
+template <bool UNI>
 __device__ __forceinline__ void tile_exact(TileShared &sh, int first, int n, const SegRec *__restrict__ srec,
                                            const float *__restrict__ sd, int64_t seg0,
                                            const BeamRec *__restrict__ recs, const float4 *__restrict__ pw,
@@ -447,7 +450,12 @@ __device__ __forceinline__ void tile_exact(TileShared &sh, int first, int n, con
     const f3 au_ = (mag_a != 0.0f) ? scale3(sub3(mk(s1.x, s1.y, s1.z), mk(s0.x, s0.y, s0.z)), s3.w) : mk(0.f, 0.f, 0.f);
     const float4 s2 = make_float4(au_.x, au_.y, au_.z, 0.f);
     // a uniform-radius set's power is in the record's last three words (BeamRec): seven loads per pair
-    const float4 pv = bset.uniform ? make_float4(bw.y, bw.z, bw.w, 0.f) : pw[b];
+    const bool uniform = UNI || bset.uniform;
+    float4 pv;
+    if constexpr (UNI)
+        pv = make_float4(bw.y, bw.z, bw.w, 0.f);
+    else
+        pv = bset.uniform ? make_float4(bw.y, bw.z, bw.w, 0.f) : pw[b];
     // phase 1: the box test (segment o, tmax, 1/d; the beam's box)
     const f3 o = mk(s0.x, s0.y, s0.z);
     const float tmax = s0.w;
@@ -469,7 +477,7 @@ __device__ __forceinline__ void tile_exact(TileShared &sh, int first, int n, con
     float4 v = make_float4(0.f, 0.f, 0.f, 1.f);
     bool contrib = false;
     if (hit) {
-        const float maxd = R + beam_radius(bset, bw.y);  // MaxDistance = currentBeamRadius + beam->radius
+        const float maxd = R + (UNI ? bset.radius : beam_radius(bset, bw.y));  // MaxDistance = currentBeamRadius + beam->radius
         float d2, unused;
         const bool ok = closest_distance_t<false, true>(o, mk(s1.x, s1.y, s1.z), mk(s2.x, s2.y, s2.z), mag_a,
                                                         mk(by.z, by.w, bz.x), mk(bz.y, bz.z, bz.w), bw.x, d2, unused);
@@ -486,7 +494,7 @@ __device__ __forceinline__ void tile_exact(TileShared &sh, int first, int n, con
             // gather: the correctly rounded quotient from its reciprocal (div_by_shared, bit-identical to
             // the division; a quotient below 2^-126 gives r^2 = 0 and w = 1 either way)
             float rr;
-            if (bset.uniform)
+            if (uniform)
                 rr = div_by_shared(dist, maxd, inv_maxd);
             else
                 rr = dist / maxd;
@@ -561,14 +569,36 @@ __device__ __forceinline__ void tile_exact(TileShared &sh, int first, int n, con
 // C), plus traversal statistics; the queue of pairs and hence every sum are the same as without.
 // pcnt (runtime, wave-uniform): count the contributions per segment in the production
 // instantiation, with the production control flow (per-subtree counts in pcnt[.][1]).
-template <bool COUNT, int MINW>
+//
+// CFG: the launch constants.  TileGeneric reads every option from the kernel's arguments.  TileProd
+// states the values every default context binds (prefilter on, margin mode 1, the LPT block map,
+// 64-beam leaves, a tile-axis table, no contribution counts, a uniform-radius set) as template
+// constants: the other settings' code is never instantiated and the arguments that carry them are
+// never read.  The two give the same bits for those settings; launch_gather_tile picks per launch.
+template <bool FIXED_>
+struct TileCfg {
+    static constexpr bool kFixed = FIXED_;
+    static constexpr int kPrefilter = 1, kMargin = 1, kMap = 3, kLeaf = 64;  // read when kFixed only
+};
+using TileGeneric = TileCfg<false>;
+using TileProd = TileCfg<true>;
+template <bool COUNT, int MINW, class CFG = TileGeneric>
 __global__ __launch_bounds__(kTileBlock, MINW) void k_gather_tile(
     int64_t nseg, const float *__restrict__ so, const float *__restrict__ sp_, const float *__restrict__ sd,
     const float *__restrict__ stmax, const SegRec *__restrict__ srec, float R, float *__restrict__ partial,
-    int32_t *__restrict__ pcnt, const BeamRec *__restrict__ recs, const float4 *__restrict__ pw, BeamSet bset,
-    const Node *__restrict__ nodes, const Node4 *__restrict__ nodes4, int64_t nvalid, int leaf_size,
-    const int32_t *__restrict__ roots, int S, DevCounters *ctr, int stack_cap, int prefilter, int map, int tscan,
-    int margin, const TileAxis *__restrict__ tax) {
+    int32_t *__restrict__ pcnt_arg, const BeamRec *__restrict__ recs, const float4 *__restrict__ pw, BeamSet bset_arg,
+    const Node *__restrict__ nodes, const Node4 *__restrict__ nodes4, int64_t nvalid, int leaf_size_arg,
+    const int32_t *__restrict__ roots, int S, DevCounters *ctr, int stack_cap, int prefilter_arg, int map_arg, int tscan,
+    int margin_arg, const TileAxis *__restrict__ tax) {
+    constexpr bool FIXED = CFG::kFixed;
+    static_assert(!(FIXED && COUNT), "the counting instantiation is generic");
+    // (constant expressions when FIXED: the branches on them below are decided at compile time)
+    const int prefilter = FIXED ? CFG::kPrefilter : prefilter_arg;
+    const int map = FIXED ? CFG::kMap : map_arg;
+    const int margin = FIXED ? CFG::kMargin : margin_arg;
+    const int leaf_size = FIXED ? CFG::kLeaf : leaf_size_arg;
+    int32_t *const pcnt = FIXED ? nullptr : pcnt_arg;
+    const BeamSet bset{FIXED ? 1 : bset_arg.uniform, bset_arg.radius};
     __shared__ TileShared shm[kTileBlock / 64];
     // Block -> (subtree, packet group).  map 1: block b works on packet group b / S and subtree
     // (b + b / S) mod S, so under the round-robin dispatch over the 8 XCDs every XCD sees every
@@ -652,7 +682,7 @@ __global__ __launch_bounds__(kTileBlock, MINW) void k_gather_tile(
         int h = 0;
         while (t1 - h >= 64) {
             if (COUNT && lane == 0) ++pf.ccp_waves;
-            tile_exact(sh, h, 64, srec, sd, seg0, recs, pw, bset, R, inv_maxd, count_c, L);
+            tile_exact<FIXED>(sh, h, 64, srec, sd, seg0, recs, pw, bset, R, inv_maxd, count_c, L);
             if (!COUNT) pf.queued += 64;  // the production queue's length (counted per batch)
             h += 64;
             __builtin_amdgcn_wave_barrier();
@@ -679,7 +709,7 @@ __global__ __launch_bounds__(kTileBlock, MINW) void k_gather_tile(
             ++pf.leaves;
             pf.beams += nb;
         }
-        if (!COUNT && tax != nullptr) {
+        if (!COUNT && (FIXED || tax != nullptr)) {
             // the per-lane tile line reject: lanes whose segment line is too far from the tile's axis
             // line leave the tile; a tile no lane keeps is skipped before it is staged
             const float4 *tq = reinterpret_cast<const float4 *>(tax + (int64_t)(~c));
@@ -898,7 +928,7 @@ __global__ __launch_bounds__(kTileBlock, MINW) void k_gather_tile(
         __builtin_amdgcn_wave_barrier();
         if (t1 > 0) {
             if (COUNT && lane == 0) ++pf.ccp_waves;
-            tile_exact(sh, 0, t1, srec, sd, seg0, recs, pw, bset, R, inv_maxd, count_c, L);
+            tile_exact<FIXED>(sh, 0, t1, srec, sd, seg0, recs, pw, bset, R, inv_maxd, count_c, L);
             if (!COUNT) pf.queued += (unsigned long long)t1;
         }
         t1 = 0;
@@ -1080,25 +1110,34 @@ hipError_t launch_gather_tile(const GatherArgs &a, bool counters, hipStream_t s)
         const hipError_t es = hipEventRecord(a.user_start, s);
         if (es != hipSuccess) return es;
     }
-#define BRE_LAUNCH_TILE(C, W)                                                                                    \
-    hipLaunchKernelGGL((k_gather_tile<C, W>), grid4, dim3(kTileBlock), 0, s, a.nseg, a.seg.o, a.seg.p, a.seg.d,  \
-                       a.seg.t, a.segrec, a.R, a.partial, pcnt, a.recs, a.pow, a.bset, a.nodes, a.nodes4,        \
-                       a.nvalid, a.leaf_size, a.roots, a.split, a.ctr, stack_cap, (int)a.prefilter, block_map,   \
-                       a.tscan, a.margin, tax)
+    // The specialised instantiation (TileProd) when this launch's bound options and beam set are the ones
+    // it states as constants, at the default register budget; the generic one for every other setting,
+    // for contribution counts and under internal option 123 = 0.  Decided per launch.
+    const bool fixed = a.tile_spec && !counters && pcnt == nullptr && a.occupancy == 6 && a.prefilter &&
+                       a.margin == TileProd::kMargin && block_map == TileProd::kMap &&
+                       a.leaf_size == TileProd::kLeaf && tax != nullptr && a.bset.uniform != 0;
+    if (a.tile_variant) *a.tile_variant = fixed ? 2 : 1;
+#define BRE_LAUNCH_TILE(C, W, CFG)                                                                               \
+    hipLaunchKernelGGL((k_gather_tile<C, W, CFG>), grid4, dim3(kTileBlock), 0, s, a.nseg, a.seg.o, a.seg.p,      \
+                       a.seg.d, a.seg.t, a.segrec, a.R, a.partial, pcnt, a.recs, a.pow, a.bset, a.nodes,         \
+                       a.nodes4, a.nvalid, a.leaf_size, a.roots, a.split, a.ctr, stack_cap, (int)a.prefilter,    \
+                       block_map, a.tscan, a.margin, tax)
     if (counters) {
-        BRE_LAUNCH_TILE(true, 1);
+        BRE_LAUNCH_TILE(true, 1, TileGeneric);
+    } else if (fixed) {
+        BRE_LAUNCH_TILE(false, 6, TileProd);
     } else if (a.occupancy == 1) {
-        BRE_LAUNCH_TILE(false, 1);
+        BRE_LAUNCH_TILE(false, 1, TileGeneric);
     } else if (a.occupancy == 4) {
-        BRE_LAUNCH_TILE(false, 4);
+        BRE_LAUNCH_TILE(false, 4, TileGeneric);
     } else if (a.occupancy == 5) {
-        BRE_LAUNCH_TILE(false, 5);
+        BRE_LAUNCH_TILE(false, 5, TileGeneric);
     } else if (a.occupancy == 6) {
-        BRE_LAUNCH_TILE(false, 6);
+        BRE_LAUNCH_TILE(false, 6, TileGeneric);
     } else if (a.occupancy == 8) {
-        BRE_LAUNCH_TILE(false, 8);
+        BRE_LAUNCH_TILE(false, 8, TileGeneric);
     } else {
-        BRE_LAUNCH_TILE(false, 7);
+        BRE_LAUNCH_TILE(false, 7, TileGeneric);
     }
 #undef BRE_LAUNCH_TILE
     hipError_t e4 = hipGetLastError();

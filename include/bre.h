@@ -164,6 +164,10 @@ typedef struct bre_stats {
                                 exact stage (box test + ComputeClosestPoints); counted with counters,
                                 and by the production instantiation itself whenever per-segment
                                 counts are requested (read back with counters or timing on) */
+    int64_t tile_variant;    /* kernels 0/4: the tile kernel instantiation the last gather launched, 1 generic
+                                (options as kernel arguments) / 2 specialised on the default options; 0 when
+                                the last gather launched no tile kernel.  Appended like queued_pairs: the
+                                struct grows, so callers of bre_get_stats build against this header */
 } bre_stats;
 
 /* ---- context ---- */
