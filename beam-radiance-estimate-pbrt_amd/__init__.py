@@ -46,7 +46,7 @@ EXPORTS = [
     "bre_render_progressive", "bre_shard_segments", "bre_set_beams_sharded", "bre_gather_sharded",
     "bre_device_check", "bre_resolve_classes", "bre_film_add", "bre_set_gather_after", "bre_set_gather_events",
     "bre_render_sharded", "bre_render_progressive_sharded", "bre_set_lights", "bre_set_materials",
-    "bre_set_media",
+    "bre_set_media", "bre_set_materials_ex",
 ]
 # bre_image_fn: int on_image(int32 iteration, const float *image_rgb, void *user)
 IMAGE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_int32, ctypes.POINTER(ctypes.c_float), ctypes.c_void_p)
@@ -134,6 +134,9 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     if hasattr(lib, "bre_set_materials"):
         lib.bre_set_materials.argtypes = [P, P, I32, P, I64]
         lib.bre_set_materials.restype = I32
+    if hasattr(lib, "bre_set_materials_ex"):
+        lib.bre_set_materials_ex.argtypes = [P, P, I32, P, I64]
+        lib.bre_set_materials_ex.restype = I32
     if hasattr(lib, "bre_set_media"):
         lib.bre_set_media.argtypes = [P, P, I32, P, P, I64, I32, P, I32]
         lib.bre_set_media.restype = I32
@@ -348,14 +351,23 @@ class BeamGather:
 
     # ---- materials ----
     def set_materials(self, materials=(), triangle_material=()):
-        """bre_set_materials: the mirror / glass table (scene.Material: scene.mirror, scene.glass, a parsed
-        scene's .materials) and each scene triangle's index into it (-1: its own matte kd), as
-        scene.scene_materials returns them; used by every later pass and render of this context.  An empty
-        table clears them."""
-        from .scene import Material
+        """bre_set_materials / bre_set_materials_ex: the material table (scene.Material: scene.mirror, scene.glass,
+        a parsed scene's .materials; or scene.MaterialEx: scene.plastic, scene.metal, scene.matte) and each scene
+        triangle's index into it (-1: its own matte kd), as scene.scene_materials returns them; used by every
+        later pass and render of this context.  Either record is taken; one MaterialEx sends the whole table
+        through the wide setter.  An empty table clears them."""
+        from .scene import Material, MaterialEx, widen
 
         materials = list(materials)
         tm = np.ascontiguousarray(triangle_material, np.int32).reshape(-1)
+        if any(isinstance(m, MaterialEx) for m in materials):
+            # bre_set_materials_ex: a table with a scene.MaterialEx (scene.plastic, scene.metal, scene.matte) goes
+            # in whole in its wide form
+            wide = [widen(m) for m in materials]
+            arr = (MaterialEx * len(wide))(*wide)
+            self._check(self.lib.bre_set_materials_ex(self.h, arr, len(wide), tm.ctypes.data if tm.size else None,
+                                                      tm.size))
+            return
         arr = (Material * max(len(materials), 1))(*materials)
         self._check(self.lib.bre_set_materials(self.h, arr if materials else None, len(materials),
                                                tm.ctypes.data if tm.size else None, tm.size))
@@ -496,6 +508,22 @@ class BeamGather:
         y = np.zeros_like(x)
         self._check(self.lib.bre_device_check(self.h, 12, x.size, _ptr(x), 0, None, _ptr(y)))
         return y[:, :3].copy(), y[:, 3].copy(), y[:, 4].copy(), y[:, 5].copy().view(np.int32)
+
+    def bsdf_check(self, materials, records):
+        """bre_device_check kind 13: the passes' general BSDF in the frame ss = x, ts = y, n = z on records [n, 9] of
+        (wo xyz, u0, u1, wi2 xyz, index into `materials`, a list of scene.MaterialEx of type matte / plastic /
+        metal).  Returns a dict: wi [n, 3], pdf [n], f [n, 3], type int32 [n] of BSDF::Sample_f (all zero where it
+        returns 0), and f2 [n, 3], pdf2 [n]: BSDF::f and BSDF::Pdf of (wo, wi2)."""
+        from .scene import MaterialEx
+
+        mats = list(materials)
+        aux = np.frombuffer(b"".join(m.to_bytes() for m in mats), np.float32).copy()
+        assert aux.size == len(mats) * ctypes.sizeof(MaterialEx) // 4
+        x = np.ascontiguousarray(records, dtype=np.float32).reshape(-1, 9)
+        y = np.zeros((x.shape[0], 12), np.float32)
+        self._check(self.lib.bre_device_check(self.h, 13, x.size, _ptr(x), aux.size, _ptr(aux), _ptr(y)))
+        return {"wi": y[:, :3].copy(), "pdf": y[:, 3].copy(), "f": y[:, 4:7].copy(),
+                "type": y[:, 7].copy().view(np.int32), "f2": y[:, 8:11].copy(), "pdf2": y[:, 11].copy()}
 
     def slot_sort(self, keys, begin_bit: int = 0, end_bit: int | None = None):
         """bre_device_check kinds 6 / 8: the pass chain's stable radix sort (bre_slot.hip) of uint64 or

@@ -1,6 +1,7 @@
 // bre_api_check.hip — bre_device_check, the test hooks of the C ABI: device functions, the pass
 // chain's one-wave primitives and the hierarchy kernels on caller data, and the read-back of the
 // context's current build.
+#include <cmath>
 #include <cstring>
 #include <vector>
 
@@ -120,7 +121,7 @@ extern "C" {
 bre_status bre_device_check(bre_ctx *c, int32_t kind, int64_t n, const float *x, int32_t n_aux, const float *aux,
                             float *y) {
     if (!c) return BRE_ERR_INVALID_ARG;
-    if (kind < 0 || kind > 12) return fail(c, BRE_ERR_INVALID_ARG, "bre_device_check: kind %d not in [0, 12]", kind);
+    if (kind < 0 || kind > 13) return fail(c, BRE_ERR_INVALID_ARG, "bre_device_check: kind %d not in [0, 13]", kind);
     if (kind == 10) return check_hierarchy(c, n, x, n_aux, aux, y);
     if (kind == 11) return check_read_tree(c, n, y);
     if (n < 0 || (n > 0 && (!x || !y))) return fail(c, BRE_ERR_INVALID_ARG, "bre_device_check: bad arrays");
@@ -135,6 +136,42 @@ bre_status bre_device_check(bre_ctx *c, int32_t kind, int64_t n, const float *x,
         HIPCHK(c, hipMemcpyAsync(dx, x, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, launch_check_specular(n / 6, dx, dy, c->stream));
         HIPCHK(c, hipMemcpyAsync(y, dy, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return BRE_OK;
+    }
+    if (kind == 13) {
+        // the general BSDF of the photon and camera passes: records of 9 floats against a table of
+        // bre_material_ex records in aux (layout: include/bre.h)
+        constexpr int kWords = (int)(sizeof(bre_material_ex) / 4);
+        if (n % 9 || n_aux < kWords || n_aux % kWords || !aux)
+            return fail(c, BRE_ERR_INVALID_ARG, "bre_device_check: kind 13 needs whole records of 9 floats and, in aux, "
+                        "whole bre_material_ex records of %d words", kWords);
+        const int n_mats = n_aux / kWords;
+        std::vector<bre_material_ex> mats((size_t)n_mats);
+        std::memcpy(mats.data(), aux, (size_t)n_aux * 4);
+        std::vector<DevBsdf> table((size_t)n_mats);
+        for (int k = 0; k < n_mats; ++k) {
+            const std::string what = check_glossy_material(mats[(size_t)k]);
+            if (!what.empty())
+                return fail(c, BRE_ERR_INVALID_ARG, "bre_device_check: kind 13: material %d has %s", k, what.c_str());
+            table[(size_t)k] = make_bsdf(mats[(size_t)k]);
+        }
+        for (int64_t i = 0; i < n / 9; ++i)
+            if (!(x[9 * i + 8] >= 0 && x[9 * i + 8] < (float)n_mats) || x[9 * i + 8] != std::floor(x[9 * i + 8]))
+                return fail(c, BRE_ERR_INVALID_ARG, "bre_device_check: kind 13: record %lld names material %g of %d",
+                            (long long)i, (double)x[9 * i + 8], n_mats);
+        if (n == 0) return BRE_OK;
+        BRE_TRY(set_device(c));
+        float *dx = nullptr, *dy = nullptr;
+        DevBsdf *dt = nullptr;
+        const size_t outs = (size_t)(n / 9) * 12;
+        HIPCHK(c, c->chk_x.get((size_t)n, &dx));
+        HIPCHK(c, c->chk_y.get(outs, &dy));
+        HIPCHK(c, c->chk_aux.get((size_t)n_mats, &dt));
+        HIPCHK(c, hipMemcpyAsync(dx, x, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(dt, table.data(), table.size() * sizeof(DevBsdf), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, launch_check_bsdf(n / 9, dx, dt, n_mats, dy, c->stream));
+        HIPCHK(c, hipMemcpyAsync(y, dy, outs * 4, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         return BRE_OK;
     }

@@ -4,7 +4,9 @@
 #include <algorithm>
 #include <cmath>
 #include <cstddef>
+#include <cstdio>
 #include <cstring>
+#include <string>
 #include <vector>
 
 #include "bre_ctx.h"
@@ -73,7 +75,7 @@ bool same_bytes(const KeyPart &a, const KeyPart &b) {
 }
 void state_key(const SceneState &h, KeyPart part[3]) {
     part[0] = {h.lights.data(), h.lights.size() * sizeof(bre_light)};
-    part[1] = {h.mats.data(), h.mats.size() * sizeof(bre_material)};
+    part[1] = {h.mats.data(), h.mats.size() * sizeof(bre_material_ex)};
     part[2] = {h.tri_mat.data(), h.tri_mat.size() * sizeof(int32_t)};
 }
 // the ranges of SceneDevice::bytes: the scene's triangles, then the state's three
@@ -104,9 +106,111 @@ uint64_t hash_geometry(const bre_scene *s, const KeyPart part[4]) {
     return h | 1ull;  // never 0 (= no scene)
 }
 
+// One record of the table as the context keeps it: checked, colours clamped, unused fields left as given (equal
+// tables compare equal).  `wide`: types past BRE_MATERIAL_INTERFACE are known.  Returns "", or what the material
+// has that is wrong (the narrow cases in bre_set_materials's words).
+std::string check_material(bre_material_ex &m, bool wide, bool media, bool *is_interface) {
+    *is_interface = false;
+    const auto finite3 = [](const float v[3]) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); };
+    const auto clamp3 = [](float v[3]) {
+        for (int j = 0; j < 3; ++j) v[j] = v[j] < 0.f ? 0.f : (v[j] > 1.f ? 1.f : v[j]);
+    };
+    char buf[160];
+    if (m.reserved[0] || m.reserved[1] || m.reserved[2]) return "non-zero reserved words";
+    if (m.type == BRE_MATERIAL_INTERFACE && media) {
+        // no BSDF: every parameter is ignored (kept as zeros, so that equal tables compare equal)
+        m = bre_material_ex{};
+        m.type = BRE_MATERIAL_INTERFACE;
+        *is_interface = true;
+        return "";
+    }
+    if (m.type == BRE_MATERIAL_MIRROR || m.type == BRE_MATERIAL_GLASS) {
+        if (!std::isfinite(m.eta) || !(m.eta > 0)) {
+            snprintf(buf, sizeof(buf), "eta %g (must be finite and > 0)", m.eta);
+            return buf;
+        }
+        if (!finite3(m.kr) || !finite3(m.kt)) return "a non-finite Kr or Kt";
+        // Kr->Evaluate(*si).Clamp() (mirror.cpp:52, glass.cpp:54-55) bounds the value below by 0; the ABI
+        // also bounds it above by 1 (a reflectance), which a physical scene file never exceeds
+        clamp3(m.kr);
+        clamp3(m.kt);
+        return "";
+    }
+    if (!wide || m.type < BRE_MATERIAL_MATTE || m.type > BRE_MATERIAL_METAL) {
+        snprintf(buf, sizeof(buf), "unknown type %d%s", m.type,
+                 m.type == BRE_MATERIAL_INTERFACE ? " (BRE_MATERIAL_INTERFACE needs bre_set_media first)" : "");
+        return buf;
+    }
+    if (m.type == BRE_MATERIAL_MATTE) {
+        if (!finite3(m.kd) || !std::isfinite(m.sigma)) return "a non-finite Kd or sigma";
+        clamp3(m.kd);
+        return "";
+    }
+    if (m.remap != 0 && m.remap != 1) return "a remap that is not 0 or 1";
+    if (m.type == BRE_MATERIAL_PLASTIC) {
+        if (!finite3(m.kd) || !finite3(m.ks) || !std::isfinite(m.roughness)) return "a non-finite Kd, Ks or roughness";
+        if (!(m.roughness > 0)) return "a roughness that is not > 0";
+        clamp3(m.kd);
+        clamp3(m.ks);
+        return "";
+    }
+    if (!finite3(m.ceta) || !finite3(m.ck) || !std::isfinite(m.roughness) || !std::isfinite(m.uroughness) ||
+        !std::isfinite(m.vroughness))
+        return "a non-finite eta, k or roughness";
+    if (m.ceta[0] == 0 || m.ceta[1] == 0 || m.ceta[2] == 0) return "an eta channel of 0";
+    const float u = m.uroughness != 0 ? m.uroughness : m.roughness, v = m.vroughness != 0 ? m.vroughness : m.roughness;
+    if (!(u > 0) || !(v > 0)) return "a roughness that is not > 0 (uroughness / vroughness after the fallback to roughness)";
+    return "";
+}
+
+bre_status set_material_table(bre_ctx *c, const char *fn, const bre_material_ex *materials, int32_t n_materials,
+                              const int32_t *triangle_material, int64_t n_triangles, bool wide) {
+    if (n_materials < 0 || n_materials > BRE_MAX_MATERIALS)
+        return fail(c, BRE_ERR_INVALID_ARG, "%s: material count must be in 0..%d", fn, BRE_MAX_MATERIALS);
+    if (n_materials == 0) {
+        c->held.mats.clear();
+        c->held.tri_mat.clear();
+        c->held.has_interface = false;
+        c->held.glossy = false;
+        return BRE_OK;
+    }
+    if (n_triangles < 0 || n_triangles > BRE_MAX_SCENE_TRIANGLES)
+        return fail(c, BRE_ERR_INVALID_ARG, "%s: the material map's triangle count must be in 0..%d", fn,
+                    BRE_MAX_SCENE_TRIANGLES);
+    if (!materials || (n_triangles > 0 && !triangle_material))
+        return fail(c, BRE_ERR_INVALID_ARG, "%s: null material table or triangle_material map", fn);
+    std::vector<bre_material_ex> mats(materials, materials + n_materials);
+    std::vector<char> is_interface((size_t)n_materials, 0);
+    bool glossy = false;
+    for (int k = 0; k < n_materials; ++k) {
+        bool iface = false;
+        const std::string what = check_material(mats[(size_t)k], wide, !c->held.media.empty(), &iface);
+        if (!what.empty()) return fail(c, BRE_ERR_INVALID_ARG, "%s: material %d has %s", fn, k, what.c_str());
+        is_interface[(size_t)k] = iface;
+        glossy = glossy || mats[(size_t)k].type >= BRE_MATERIAL_MATTE;
+    }
+    for (int64_t i = 0; i < n_triangles; ++i)
+        if (triangle_material[i] < -1 || triangle_material[i] >= n_materials)
+            return fail(c, BRE_ERR_INVALID_ARG, "%s: triangle %lld has material index %d outside [-1, %d)", fn,
+                        (long long)i, triangle_material[i], n_materials);
+    c->held.mats.swap(mats);
+    c->held.tri_mat.assign(triangle_material, triangle_material + n_triangles);
+    c->held.has_interface = false;
+    c->held.glossy = glossy;
+    for (int64_t i = 0; i < n_triangles; ++i)
+        if (triangle_material[i] >= 0 && is_interface[(size_t)triangle_material[i]]) c->held.has_interface = true;
+    return BRE_OK;
+}
+
 }  // namespace
 
 namespace bre {
+
+std::string check_glossy_material(bre_material_ex &m) {
+    bool iface;
+    if (m.type < BRE_MATERIAL_MATTE) return "a type outside BRE_MATERIAL_MATTE .. BRE_MATERIAL_METAL";
+    return check_material(m, true, false, &iface);
+}
 
 const char *scene_state_differs(const SceneState &a, const SceneState &b) {
     KeyPart ka[3], kb[3];
@@ -213,6 +317,7 @@ bre_status upload_scene(bre_ctx *c, const bre_scene *scene) {
         HIPCHK(c, upload(c, dv.light_cdf, hs.light_cdf, &dv.head.light_cdf));
         HIPCHK(c, upload(c, dv.dlights, hs.dlights, &dv.head.dlights));
         HIPCHK(c, upload(c, dv.mats, hs.mats, &dv.head.mats));
+        HIPCHK(c, upload(c, dv.bsdfs, hs.bsdfs, &dv.head.bsdfs));
         HIPCHK(c, hipStreamSynchronize(c->stream));  // the host vectors go out of scope
         dv.hash = hash;
         for (int k = 0; k < 4; ++k) {
@@ -260,59 +365,23 @@ bre_status bre_set_lights(bre_ctx *c, const bre_light *lights, int32_t n) {
     return BRE_OK;
 }
 
+bre_status bre_set_materials_ex(bre_ctx *c, const bre_material_ex *materials, int32_t n_materials,
+                                const int32_t *triangle_material, int64_t n_triangles) {
+    if (!c) return BRE_ERR_INVALID_ARG;
+    return set_material_table(c, "bre_set_materials_ex", materials, n_materials, triangle_material, n_triangles, true);
+}
+
+// the widening of its records: the same table
 bre_status bre_set_materials(bre_ctx *c, const bre_material *materials, int32_t n_materials,
                              const int32_t *triangle_material, int64_t n_triangles) {
     if (!c) return BRE_ERR_INVALID_ARG;
-    const char *fn = "bre_set_materials";
-    if (n_materials < 0 || n_materials > BRE_MAX_MATERIALS)
-        return fail(c, BRE_ERR_INVALID_ARG, "%s: material count must be in 0..%d", fn, BRE_MAX_MATERIALS);
-    if (n_materials == 0) {
-        c->held.mats.clear();
-        c->held.tri_mat.clear();
-        c->held.has_interface = false;
-        return BRE_OK;
+    std::vector<bre_material_ex> wide;
+    if (materials && n_materials > 0 && n_materials <= BRE_MAX_MATERIALS) {
+        wide.assign((size_t)n_materials, bre_material_ex{});
+        for (int k = 0; k < n_materials; ++k) std::memcpy(&wide[(size_t)k], &materials[k], sizeof(bre_material));
     }
-    if (n_triangles < 0 || n_triangles > BRE_MAX_SCENE_TRIANGLES)
-        return fail(c, BRE_ERR_INVALID_ARG, "%s: the material map's triangle count must be in 0..%d", fn,
-                    BRE_MAX_SCENE_TRIANGLES);
-    if (!materials || (n_triangles > 0 && !triangle_material))
-        return fail(c, BRE_ERR_INVALID_ARG, "%s: null material table or triangle_material map", fn);
-    std::vector<bre_material> mats(materials, materials + n_materials);
-    std::vector<char> is_interface((size_t)n_materials, 0);
-    for (int k = 0; k < n_materials; ++k) {
-        bre_material &m = mats[(size_t)k];
-        if (m.type == BRE_MATERIAL_INTERFACE && !c->held.media.empty()) {
-            // no BSDF: Kr, Kt and eta are ignored (kept as zeros, so that equal tables compare equal)
-            m = bre_material{};
-            m.type = BRE_MATERIAL_INTERFACE;
-            is_interface[(size_t)k] = 1;
-            continue;
-        }
-        // (an interface on a context without media is refused like an unknown type: bre_set_media comes first)
-        if (m.type != BRE_MATERIAL_MIRROR && m.type != BRE_MATERIAL_GLASS)
-            return fail(c, BRE_ERR_INVALID_ARG, "%s: material %d has unknown type %d%s", fn, k, m.type,
-                        m.type == BRE_MATERIAL_INTERFACE ? " (BRE_MATERIAL_INTERFACE needs bre_set_media first)" : "");
-        if (!std::isfinite(m.eta) || !(m.eta > 0))
-            return fail(c, BRE_ERR_INVALID_ARG, "%s: material %d has eta %g (must be finite and > 0)", fn, k, m.eta);
-        for (int j = 0; j < 3; ++j) {
-            if (!std::isfinite(m.kr[j]) || !std::isfinite(m.kt[j]))
-                return fail(c, BRE_ERR_INVALID_ARG, "%s: material %d has a non-finite Kr or Kt", fn, k);
-            // Kr->Evaluate(*si).Clamp() (mirror.cpp:52, glass.cpp:54-55) bounds the value below by 0; the ABI
-            // also bounds it above by 1 (a reflectance), which a physical scene file never exceeds
-            m.kr[j] = m.kr[j] < 0.f ? 0.f : (m.kr[j] > 1.f ? 1.f : m.kr[j]);
-            m.kt[j] = m.kt[j] < 0.f ? 0.f : (m.kt[j] > 1.f ? 1.f : m.kt[j]);
-        }
-    }
-    for (int64_t i = 0; i < n_triangles; ++i)
-        if (triangle_material[i] < -1 || triangle_material[i] >= n_materials)
-            return fail(c, BRE_ERR_INVALID_ARG, "%s: triangle %lld has material index %d outside [-1, %d)", fn,
-                        (long long)i, triangle_material[i], n_materials);
-    c->held.mats.swap(mats);
-    c->held.tri_mat.assign(triangle_material, triangle_material + n_triangles);
-    c->held.has_interface = false;
-    for (int64_t i = 0; i < n_triangles; ++i)
-        if (triangle_material[i] >= 0 && is_interface[(size_t)triangle_material[i]]) c->held.has_interface = true;
-    return BRE_OK;
+    return set_material_table(c, "bre_set_materials", materials ? wide.data() : nullptr, n_materials, triangle_material,
+                              n_triangles, false);
 }
 
 bre_status bre_set_media(bre_ctx *c, const bre_medium *media, int32_t n_media, const int32_t *tri_inside,

@@ -311,7 +311,9 @@ __device__ __forceinline__ float power_heuristic(float fpdf, float gpdf) {
 // MED (bre_set_media): the shaded vertex lies on triangle `tri`, reached by a ray in medium `med`; the shadow
 // ray is VisibilityTester::Tr as a loop (light.cpp:63-81) and the BSDF-sampled ray Scene::IntersectTr
 // (scene.cpp:62-75): both step through interface triangles and multiply each segment's Tr in order.
-template <bool MED>
+// GL (bre_set_materials_ex): a plastic, metal or matte vertex goes through the general BSDF (bre_trace.h), whose
+// Pdf is not the cosine's; the early out stays for mirror, glass and interface entries.
+template <bool MED, bool GL>
 __device__ void estimate_direct(const DevScene &S, HaltonDev &hs, f3 p, f3 perr, const PTri &q, f3 wo, int li,
                                 float usx, float usy, float ulx, float uly, float Ld[3], int tri, int med) {
     const bool delta = li < 0;
@@ -320,7 +322,15 @@ __device__ void estimate_direct(const DevScene &S, HaltonDev &hs, f3 p, f3 perr,
     // A specular vertex (bsdfFlags = BSDF_ALL & ~BSDF_SPECULAR matches no BxDF of a mirror or glass): bsdf.f
     // is 0, so there is no shadow ray and no Tr draw (:132-152), and the BSDF-sampling half's Sample_f has
     // matchingComps == 0 (f = 0, pdf = 0).  Ld = 0 without a draw.
-    if (q.mat >= kMatTable) return;
+    const DevBsdf *gm = nullptr;
+    if (q.mat >= kMatTable) {
+        if constexpr (GL) {
+            if (S.bsdfs[q.mat - kMatTable].type == 0) return;
+            gm = &S.bsdfs[q.mat - kMatTable];
+        } else {
+            return;
+        }
+    }
     float scat_pdf = 0.f;
     f3 wi = mk(0, 0, 0);
     float Li[3] = {0.f, 0.f, 0.f};
@@ -358,10 +368,11 @@ __device__ void estimate_direct(const DevScene &S, HaltonDev &hs, f3 p, f3 perr,
     const f3 sp = ps.p;
     if (light_pdf > 0 && !black3(Li)) {
         float f[3];
-        bsdf_f(q, wo, wi, f);
+        if (GL && gm) bsdf_f(q, *gm, wo, wi, f);
+        else bsdf_f(q, wo, wi, f);
         const float ad = fabsf(dot3(wi, q.n));
         for (int c = 0; c < 3; ++c) f[c] = f[c] * ad;
-        scat_pdf = bsdf_pdf(q, wo, wi);
+        scat_pdf = (GL && gm) ? bsdf_pdf(q, *gm, wo, wi) : bsdf_pdf(q, wo, wi);
         if (!black3(f)) {
             // VisibilityTester::Tr over Interaction::SpawnRayTo(pShape)
             f3 ro = offset_origin(p, perr, q.n, sub3(sp, p));
@@ -410,7 +421,9 @@ __device__ void estimate_direct(const DevScene &S, HaltonDev &hs, f3 p, f3 perr,
     // BSDF sampling
     {
         float f[3];
-        bsdf_sample(q, wo, usx, usy, wi, scat_pdf, f);
+        int type;
+        if (GL && gm) bsdf_sample(q, *gm, wo, usx, usy, wi, scat_pdf, f, type);
+        else bsdf_sample(q, wo, usx, usy, wi, scat_pdf, f);
         const float ad = fabsf(dot3(wi, q.n));
         for (int c = 0; c < 3; ++c) f[c] = f[c] * ad;
         if (!black3(f) && scat_pdf > 0) {
@@ -460,8 +473,10 @@ __device__ void estimate_direct(const DevScene &S, HaltonDev &hs, f3 p, f3 perr,
 // MED: the context holds media: the ray carries its medium, an interface triangle is passed through with the
 // depth not counted (:515-517), and a segment's slot plane is its ordinal along the path (`planes` of them)
 // instead of its depth.  MED false is the one-medium walk, the code it was before media.
-template <bool MED>
-__global__ __launch_bounds__(kCamBlock, 6) void k_camera(const DevScene *__restrict__ Sp, const DevCamera *__restrict__ Cp,
+// GL: the general BSDF for the table's plastic, metal and matte entries, at kGlossyWaves waves per SIMD; GL false
+// is the code it was before them, held to 80 VGPRs.
+template <bool MED, bool GL>
+__global__ __launch_bounds__(kCamBlock, GL ? kGlossyWaves : 6) void k_camera(const DevScene *__restrict__ Sp, const DevCamera *__restrict__ Cp,
                                                      const uint16_t *__restrict__ perms, int iteration, int max_depth,
                                                      int render_surfaces, int render_media, int64_t nslots,
                                                      float *__restrict__ so, float *__restrict__ sp_,
@@ -568,7 +583,13 @@ __global__ __launch_bounds__(kCamBlock, 6) void k_camera(const DevScene *__restr
             hs.get2d(usx, usy);
             float ed[3];
             const int lt = S.light_tri[ln];
-            estimate_direct<MED>(S, hs, hit.p, hit.perr, q, normalize3(wo), lt, usx, usy, ulx, uly, ed, hit.tri, med);
+            if constexpr (GL) {
+                // inlined here: as a call the general BSDF's estimate_direct takes the sampler through memory
+                [[clang::always_inline]] estimate_direct<MED, GL>(S, hs, hit.p, hit.perr, q, normalize3(wo), lt, usx, usy,
+                                                                  ulx, uly, ed, hit.tri, med);
+            } else {
+                estimate_direct<MED, GL>(S, hs, hit.p, hit.perr, q, normalize3(wo), lt, usx, usy, ulx, uly, ed, hit.tri, med);
+            }
             for (int c = 0; c < 3; ++c) Ld[c] = Ld[c] + beta[c] * (ed[c] / light_pdf);
             if (depth < max_depth - 1) {
                 float ux, uy, pdf = 0.f, f[3];
@@ -576,7 +597,11 @@ __global__ __launch_bounds__(kCamBlock, 6) void k_camera(const DevScene *__restr
                 f3 wi;
                 int type = 0;  // the sampled BxDFType's specular bit; a Lambertian lobe has none
                 bool ok;
-                if (q.mat >= kMatTable) {
+                bool general = false;
+                if constexpr (GL) general = q.mat >= kMatTable && S.bsdfs[q.mat - kMatTable].type != 0;
+                if (general) {
+                    ok = bsdf_sample(q, S.bsdfs[q.mat - kMatTable], wo, ux, uy, wi, pdf, f, type);
+                } else if (q.mat >= kMatTable) {
                     // mirror / glass: the one specular lobe, TransportMode::Radiance (:514)
                     f3 wil;
                     ok = specular_sample(S.mats[q.mat - kMatTable], to_local(q, wo), ux, kModeRadiance, wil, pdf, f, type);
@@ -634,7 +659,7 @@ int64_t camera_slots(int width, int height) {
 hipError_t launch_camera(const DevScene *scene, int stack_depth, const DevCamera *cam, const uint16_t *perms, int width,
                          int height, int iteration, int max_depth, int render_surfaces, int render_media,
                          const CamSlots &s, float *surface, unsigned int *flags, int shard_rank, int shard_count,
-                         int shard_block, int classes, int planes, bool media, hipStream_t stream) {
+                         int shard_block, int classes, int planes, bool media, bool glossy, hipStream_t stream) {
     const int64_t nslots = camera_slots(width, height);
     if (nslots == 0) return hipSuccess;
     const auto go = [&](auto kernel) {
@@ -644,7 +669,8 @@ hipError_t launch_camera(const DevScene *scene, int stack_depth, const DevCamera
                            s.valid, surface, flags, shard_rank, shard_count, shard_block, classes < 1 ? 1 : classes,
                            planes);
     };
-    media ? go(k_camera<true>) : go(k_camera<false>);
+    if (glossy) media ? go(k_camera<true, true>) : go(k_camera<false, true>);
+    else media ? go(k_camera<true, false>) : go(k_camera<false, false>);
     return hipGetLastError();
 }
 

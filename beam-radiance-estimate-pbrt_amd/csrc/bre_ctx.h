@@ -165,9 +165,11 @@ struct Stream : NoCopy {
 // The scene state the sticky setters store on a context, beside the bre_scene every pass is given
 struct SceneState {
     std::vector<bre_light> lights;   // bre_set_lights: the delta lights every pass adds to its scene
-    std::vector<bre_material> mats;  // bre_set_materials: the mirror / glass table (Kr, Kt clamped) ...
+    // bre_set_materials / bre_set_materials_ex: the one table in its wide form (colours clamped) ...
+    std::vector<bre_material_ex> mats;
     std::vector<int32_t> tri_mat;    // ... and each triangle's index into it (-1: its own matte kd)
     bool has_interface = false;      // ... one of which leads to a BRE_MATERIAL_INTERFACE entry
+    bool glossy = false;             // the table holds a type >= BRE_MATERIAL_MATTE: the passes' glossy kernels
     // bre_set_media: the table (grid_density pointing into media_grid), the triangles' (inside, outside) pairs
     // interleaved, the delta lights' media, the camera's; media_key: all of it as bytes, the grids for the pointers
     std::vector<bre_medium> media;
@@ -180,7 +182,7 @@ struct SceneState {
 // What upload_scene keeps on the device, and the host bytes it compares the next call's scene against
 struct SceneDevice {
     // geometry: triangles, BVHAccel nodes + primitive order, scene.lights, the delta lights and the materials
-    DevMem tris, nodes, prims, light_tri, light_func, light_cdf, dlights, mats;
+    DevMem tris, nodes, prims, light_tri, light_func, light_cdf, dlights, mats, bsdfs;
     DevScene head;                     // its fields of the record below
     uint64_t hash = 0;                 // hash of the uploaded triangles, lights and materials (0: none)
     // the uploaded triangles' bytes, the lights', the materials' and the map's: a hash match is confirmed by memcmp
@@ -267,6 +269,7 @@ struct bre_ctx {
     int cam_w = -1, cam_h = -1;  // film the Halton / camera tables were prepared for
     bre_scene cam_scene;         // scene the camera tables were prepared for
     bre::DevMem chk_x, chk_aux, chk_y;  // bre_device_check staging
+    int lds_per_block = 0;              // the device's LDS per workgroup, asked once (the glossy photon kernels' frames)
     bre_stats stats;
     // bre_set_gather_after: this context's tile kernels wait for `after`'s last one (after->tile_ev)
     bre_ctx *after = nullptr;
@@ -313,6 +316,9 @@ bre_status check_medium(bre_ctx *c, const bre_scene *scene, const char *fn);
 bre_status upload_scene(bre_ctx *c, const bre_scene *scene);
 // the part that differs, "lights (bre_set_lights)", "materials ..." or "media ...", or null: the same state
 const char *scene_state_differs(const SceneState &a, const SceneState &b);
+// a plastic, metal or matte record as bre_set_materials_ex checks and keeps it (colours clamped): "", or what
+// is wrong with it
+std::string check_glossy_material(bre_material_ex &m);
 // bre_api_build.hip
 bre_status build(bre_ctx *c, int64_t n, const BeamView &in);
 

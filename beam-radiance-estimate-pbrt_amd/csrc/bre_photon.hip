@@ -56,8 +56,16 @@ struct FrameMed : Frame {
 // MED: the context holds media: the ray carries its medium (an index into S.media, -1 vacuum), taken by
 // GetMedium at every spawn, and an interface triangle is passed through (photonbeam.cpp:300-304).  MED false
 // is the one-medium walk, the code it was before media.
-template <int MODE, bool MED>
-__global__ __launch_bounds__(kPhotonBlock, 6) void k_photons(const DevScene *__restrict__ Sp, int64_t n, uint64_t seq0,
+// GL: the context's table holds a plastic, metal or matte entry (bre_set_materials_ex): such a triangle scatters
+// through the general BSDF (bsdf_sample, bre_trace.h).  GL false is the code it was before them, held to 80 VGPRs
+// because its waves run inside another context's gather; the glossy kernels carry the
+// microfacet lobe's registers and take kGlossyWaves waves per SIMD instead.
+// GL keeps the suspended frames in the block's dynamic LDS, behind the scene traversal stack, instead of a
+// per-thread array: word w of thread t's frame k at [(k * kFrameWords + w) * kPhotonBlock + t].  A path holds at
+// most max_depth frames (each push adds one to depth), so the launch sizes the region to max_depth frames.
+constexpr int kFrameWords = 19;  // o, d, tmax, p, perr, tri, depth, beta, med
+template <int MODE, bool MED, bool GL>
+__global__ __launch_bounds__(kPhotonBlock, GL ? kGlossyWaves : 6) void k_photons(const DevScene *__restrict__ Sp, int64_t n, uint64_t seq0,
                                                           int max_depth, float radius, int32_t *__restrict__ counts,
                                                           const int64_t *__restrict__ offsets, float *__restrict__ bs,
                                                           float *__restrict__ be, float *__restrict__ br,
@@ -124,7 +132,12 @@ __global__ __launch_bounds__(kPhotonBlock, 6) void k_photons(const DevScene *__r
     }
 
     // ---- TracePhotonBeamRecursive as a state machine ----
-    typename std::conditional<MED, FrameMed, Frame>::type stk[BRE_MAX_DEPTH];
+    typename std::conditional<GL, char, typename std::conditional<MED, FrameMed, Frame>::type>::type
+        stk[GL ? 1 : BRE_MAX_DEPTH];
+    extern __shared__ int bre_scene_stack[];  // GL: the frames follow intersect_scene's stack_depth * blockDim words
+    float *const frames = reinterpret_cast<float *>(bre_scene_stack) +
+                          (GL ? (S.stack_depth > 0 ? S.stack_depth : 1) * kPhotonBlock + (int)threadIdx.x : 0);
+    (void)stk;
     int sp = 0;
     int depth = 0;
     float tmax = 0;
@@ -152,18 +165,29 @@ __global__ __launch_bounds__(kPhotonBlock, 6) void k_photons(const DevScene *__r
                     const f3 wi = hg_sample(g, neg3(d), hx, hy);
                     float tr[3];
                     ray_medium_tr<MED>(S, med, rng, o, d, tmax, tr);
-                    auto &f = stk[sp++];
-                    f.o = o;
-                    f.d = d;
-                    f.tmax = tmax;
-                    f.p = hit.p;
-                    f.perr = hit.perr;
-                    f.tri = hit.tri;
-                    f.depth = depth;
-                    if constexpr (MED) f.med = med;  // the child stays in it too (MediumInterface(this))
-                    for (int c = 0; c < 3; ++c) {
-                        f.beta[c] = beta[c];
-                        beta[c] = beta[c] * tr[c];
+                    if constexpr (GL) {
+                        float *f = frames + sp++ * (kFrameWords * kPhotonBlock);
+                        const float w[kFrameWords] = {o.x, o.y, o.z, d.x, d.y, d.z, tmax, hit.p.x, hit.p.y, hit.p.z,
+                                                      hit.perr.x, hit.perr.y, hit.perr.z, __int_as_float(hit.tri),
+                                                      __int_as_float(depth), beta[0], beta[1], beta[2],
+                                                      __int_as_float(med)};
+#pragma unroll
+                        for (int k = 0; k < kFrameWords; ++k) f[k * kPhotonBlock] = w[k];
+                        for (int c = 0; c < 3; ++c) beta[c] = beta[c] * tr[c];
+                    } else {
+                        auto &f = stk[sp++];
+                        f.o = o;
+                        f.d = d;
+                        f.tmax = tmax;
+                        f.p = hit.p;
+                        f.perr = hit.perr;
+                        f.tri = hit.tri;
+                        f.depth = depth;
+                        if constexpr (MED) f.med = med;  // the child stays in it too (MediumInterface(this))
+                        for (int c = 0; c < 3; ++c) {
+                            f.beta[c] = beta[c];
+                            beta[c] = beta[c] * tr[c];
+                        }
                     }
                     o = ray_at(o, d, ts);  // MediumInteraction::SpawnRay: no offset
                     d = wi;
@@ -212,9 +236,15 @@ __global__ __launch_bounds__(kPhotonBlock, 6) void k_photons(const DevScene *__r
                 if (woz == 0) {
                     stop = true;
                 } else {
-                    f3 wil;
+                    f3 wil, wiw;
                     float pdf, fr[3];
-                    if (q.mat >= kMatTable) {
+                    bool world = false;  // GL: wiw is BSDF::Sample_f's own LocalToWorld(wi)
+                    if constexpr (GL) world = q.mat >= kMatTable && S.bsdfs[q.mat - kMatTable].type != 0;
+                    if (world) {
+                        int type;
+                        pdf = 0.f;
+                        bsdf_sample(q, S.bsdfs[q.mat - kMatTable], wo, ux, uy, wiw, pdf, fr, type);
+                    } else if (q.mat >= kMatTable) {
                         int type;
                         specular_sample(S.mats[q.mat - kMatTable], mk(dot3(wo, q.ss), dot3(wo, q.ts), woz), ux,
                                         kModeImportance, wil, pdf, fr, type);
@@ -227,7 +257,7 @@ __global__ __launch_bounds__(kPhotonBlock, 6) void k_photons(const DevScene *__r
                     if (pdf == 0 || black3(fr)) {
                         stop = true;
                     } else {
-                        const f3 wi = to_world(q, wil);
+                        const f3 wi = world ? wiw : to_world(q, wil);
                         const float ad = fabsf(dot3(wi, q.n));
                         float bn[3];
                         for (int c = 0; c < 3; ++c) bn[c] = bm[c] * beta[c] * fr[c] * ad / pdf;
@@ -248,16 +278,32 @@ __global__ __launch_bounds__(kPhotonBlock, 6) void k_photons(const DevScene *__r
         }
         // this path ends: resume the innermost suspended parent after its recursive call
         if (sp == 0) break;
-        const auto &f = stk[--sp];
-        o = f.o;
-        d = f.d;
-        tmax = f.tmax;
-        hit.p = f.p;
-        hit.perr = f.perr;
-        hit.tri = f.tri;
-        depth = f.depth;
-        for (int c = 0; c < 3; ++c) beta[c] = f.beta[c];
-        if constexpr (MED) med = f.med;
+        if constexpr (GL) {
+            const float *f = frames + --sp * (kFrameWords * kPhotonBlock);
+            float w[kFrameWords];
+#pragma unroll
+            for (int k = 0; k < kFrameWords; ++k) w[k] = f[k * kPhotonBlock];
+            o = mk(w[0], w[1], w[2]);
+            d = mk(w[3], w[4], w[5]);
+            tmax = w[6];
+            hit.p = mk(w[7], w[8], w[9]);
+            hit.perr = mk(w[10], w[11], w[12]);
+            hit.tri = __float_as_int(w[13]);
+            depth = __float_as_int(w[14]);
+            for (int c = 0; c < 3; ++c) beta[c] = w[15 + c];
+            if constexpr (MED) med = __float_as_int(w[18]);
+        } else {
+            const auto &f = stk[--sp];
+            o = f.o;
+            d = f.d;
+            tmax = f.tmax;
+            hit.p = f.p;
+            hit.perr = f.perr;
+            hit.tri = f.tri;
+            depth = f.depth;
+            for (int c = 0; c < 3; ++c) beta[c] = f.beta[c];
+            if constexpr (MED) med = f.med;
+        }
         resume = true;
     }
     if (MODE != 1) counts[i] = cnt;
@@ -315,18 +361,30 @@ inline unsigned grid_of(int64_t n) { return (unsigned)((n + kPhotonBlock - 1) / 
 
 }  // namespace
 
+size_t photon_lds_bytes(int stack_depth, int max_depth, bool glossy) {
+    const size_t frames = (size_t)(max_depth > 0 ? max_depth : 1) * kFrameWords * kPhotonBlock * sizeof(float);
+    return scene_stack_bytes(stack_depth, kPhotonBlock) + (glossy ? frames : 0);
+}
+
 hipError_t launch_photons(const DevScene *scene, int stack_depth, int64_t n, uint64_t seq0, int max_depth,
                           float radius, int32_t *counts, const int64_t *offsets, const BeamOut &out, int mode,
-                          int over, bool media, hipStream_t s) {
+                          int over, bool media, bool glossy, hipStream_t s) {
     if (n == 0) return hipSuccess;
-    const size_t lds = scene_stack_bytes(stack_depth, kPhotonBlock);
+    // the glossy kernels keep their frames in LDS too (the caller has checked the device's room: photon_lds_bytes)
+    const size_t lds = photon_lds_bytes(stack_depth, max_depth, glossy);
     const auto go = [&](auto kernel, int ov) {
         hipLaunchKernelGGL(kernel, dim3(grid_of(n)), dim3(kPhotonBlock), lds, s, scene, n, seq0, max_depth, radius,
                            counts, offsets, out.start, out.end, out.radius, out.power, ov);
     };
-    if (mode == 1) media ? go(k_photons<1, true>, over) : go(k_photons<1, false>, over);
-    else if (mode == 2) media ? go(k_photons<2, true>, over) : go(k_photons<2, false>, over);
-    else media ? go(k_photons<0, true>, 0) : go(k_photons<0, false>, 0);
+    if (glossy) {
+        if (mode == 1) media ? go(k_photons<1, true, true>, over) : go(k_photons<1, false, true>, over);
+        else if (mode == 2) media ? go(k_photons<2, true, true>, over) : go(k_photons<2, false, true>, over);
+        else media ? go(k_photons<0, true, true>, 0) : go(k_photons<0, false, true>, 0);
+        return hipGetLastError();
+    }
+    if (mode == 1) media ? go(k_photons<1, true, false>, over) : go(k_photons<1, false, false>, over);
+    else if (mode == 2) media ? go(k_photons<2, true, false>, over) : go(k_photons<2, false, false>, over);
+    else media ? go(k_photons<0, true, false>, 0) : go(k_photons<0, false, false>, 0);
     return hipGetLastError();
 }
 

@@ -75,11 +75,73 @@ static float light_power_y(const DLight &D) {
     return lum3(pw);
 }
 
+// PlasticMaterial / MetalMaterial / MatteMaterial::ComputeScatteringFunctions (plastic.cpp:45-70, metal.cpp:59-80,
+// matte.cpp:45-62) on the record's constants (the setter has clamped Kd and Ks and checked the roughnesses)
+DevBsdf make_bsdf(const bre_material_ex &m) {
+    DevBsdf b{};
+    if (m.type < BRE_MATERIAL_MATTE) return b;
+    b.type = m.type;
+    b.ax = b.ay = 1.f;
+    if (m.type == BRE_MATERIAL_MATTE) {
+        const float sig = clampf_ref(m.sigma, 0.f, 90.f);
+        if (!black3(m.kd)) b.lobes = kLobeDiffuse;
+        for (int c = 0; c < 3; ++c) b.kd[c] = m.kd[c];
+        if (sig != 0) {  // OrenNayar's constructor, reflection.h:417-423
+            const float sigma = (kPi / 180) * sig;
+            const float sigma2 = sigma * sigma;
+            b.A = 1.f - (sigma2 / (2.f * (sigma2 + 0.33f)));
+            b.B = 0.45f * sigma2 / (sigma2 + 0.09f);
+            b.oren = 1;
+        }
+    } else if (m.type == BRE_MATERIAL_PLASTIC) {
+        if (!black3(m.kd)) b.lobes |= kLobeDiffuse;
+        if (!black3(m.ks)) b.lobes |= kLobeMicro;
+        for (int c = 0; c < 3; ++c) {
+            b.kd[c] = m.kd[c];
+            b.ks[c] = m.ks[c];
+        }
+        float rough = m.roughness;
+        if (m.remap) rough = roughness_to_alpha(rough);
+        b.ax = b.ay = rough;
+    } else {
+        float u = m.uroughness != 0 ? m.uroughness : m.roughness;
+        float v = m.vroughness != 0 ? m.vroughness : m.roughness;
+        if (m.remap) {
+            u = roughness_to_alpha(u);
+            v = roughness_to_alpha(v);
+        }
+        b.ax = u;
+        b.ay = v;
+        b.lobes = kLobeMicro;
+        b.conductor = 1;
+        for (int c = 0; c < 3; ++c) {
+            b.ks[c] = 1.f;
+            b.ceta[c] = m.ceta[c];
+            b.ck[c] = m.ck[c];
+        }
+    }
+    return b;
+}
+
 void prepare_geometry(const bre_scene *s, HostScene *out, const bre_light *lights, int n_lights,
                       const MaterialMap &mm) {
     DevScene &d = out->head;
     d.n_tris = s->n_triangles;
-    out->mats.assign(mm.mats, mm.mats + mm.n_mats);
+    // the table twice: the narrow records of the mirror / glass / interface entries, and beside them the BSDFs of
+    // the plastic / metal / matte ones
+    out->mats.resize((size_t)mm.n_mats);
+    out->bsdfs.resize((size_t)mm.n_mats);
+    for (int k = 0; k < mm.n_mats; ++k) {
+        const bre_material_ex &m = mm.mats[k];
+        bre_material &n = out->mats[(size_t)k];
+        n.type = m.type;
+        for (int c = 0; c < 3; ++c) {
+            n.kr[c] = m.kr[c];
+            n.kt[c] = m.kt[c];
+        }
+        n.eta = m.eta;
+        out->bsdfs[(size_t)k] = make_bsdf(m);
+    }
     const bre_triangle *tri = scene_triangles(s);
     out->tris.resize((size_t)s->n_triangles);
     out->light_tri.clear();
@@ -126,10 +188,19 @@ void prepare_geometry(const bre_scene *s, HostScene *out, const bre_light *light
         T.mat = black3(t.kd) ? kMatNone : kMatMatte;
         if (mm.n_mats > 0 && mm.tri_mat[i] >= 0) {
             // mirror.cpp:50-56, glass.cpp:53-64: black Kr (and Kt) adds no BxDF
-            const bre_material &m = mm.mats[mm.tri_mat[i]];
+            const bre_material_ex &m = mm.mats[mm.tri_mat[i]];
             const bool none = black3(m.kr) && (m.type == BRE_MATERIAL_MIRROR || black3(m.kt));
             T.mat = none ? kMatNone : kMatTable + mm.tri_mat[i];
             if (m.type == BRE_MATERIAL_INTERFACE) T.mat = kMatInterface;  // GetMaterial() == nullptr: no BSDF
+            if (m.type >= BRE_MATERIAL_MATTE) {
+                const DevBsdf &b = out->bsdfs[(size_t)mm.tri_mat[i]];
+                T.mat = b.lobes == 0 ? kMatNone : kMatTable + mm.tri_mat[i];
+                if (b.type == BRE_MATERIAL_MATTE && !b.oren) {
+                    // matte.cpp:57-58: the Lambertian lobe of a triangle's own kd, with the entry's Kd
+                    for (int k = 0; k < 3; ++k) T.kd[k] = b.kd[k];
+                    if (b.lobes) T.mat = kMatMatte;
+                }
+            }
         }
         T.emit = t.emit != 0;
         if (T.emit) {

@@ -158,11 +158,28 @@ constexpr int kMatMatte = 0, kMatNone = 1, kMatTable = 2;
 constexpr int kMatInterface = -1;  // BRE_MATERIAL_INTERFACE: no BSDF at all, the walks pass through
 
 // BxDFType bits (reflection.h:126-134) of the lobes sampled here
-constexpr int kBsdfReflection = 1, kBsdfTransmission = 2, kBsdfSpecular = 16;
+constexpr int kBsdfReflection = 1, kBsdfTransmission = 2, kBsdfDiffuse = 4, kBsdfGlossy = 8, kBsdfSpecular = 16;
 constexpr int kModeImportance = 0, kModeRadiance = 1;  // TransportMode of a specular_sample call
 
 // The specular materials on the device are the context's bre_material records (Kr, Kt clamped)
 static_assert(sizeof(bre_material) == 32, "bre_material has no padding: the geometry cache compares its bytes");
+static_assert(sizeof(bre_material_ex) == 112, "bre_material_ex has no padding: the geometry cache compares its bytes");
+
+// A plastic, metal or matte table entry (bre_material_ex, type >= BRE_MATERIAL_MATTE) as its material's
+// ComputeScatteringFunctions leaves the BSDF (make_bsdf): the BxDFs added, in the order added, and what they hold.
+// An entry of the narrow kinds has type 0 here (its record is DevScene::mats[k]).
+constexpr int kLobeDiffuse = 1, kLobeMicro = 2;
+struct DevBsdf {
+    int type;             // BRE_MATERIAL_MATTE / _PLASTIC / _METAL, or 0
+    int lobes;            // kLobeDiffuse (first), kLobeMicro (second)
+    float kd[3];          // LambertianReflection / OrenNayar R
+    float ks[3];          // MicrofacetReflection R (metal: 1)
+    float ceta[3], ck[3]; // metal: FresnelConductor(1, eta, k); plastic: FresnelDielectric(1.5, 1)
+    float ax, ay;         // TrowbridgeReitzDistribution alphax, alphay (RoughnessToAlpha applied on the host)
+    float A, B;           // OrenNayar's constants
+    int oren;             // the diffuse lobe is an OrenNayar
+    int conductor;        // the microfacet lobe's Fresnel term is the conductor's
+};
 
 // One node of the scene's bounding volume hierarchy: the reference's BVHAccel LinearBVHNode
 // (src/accelerators/bvh.cpp, 32 B, depth-first order: an interior node's first child follows it).
@@ -224,6 +241,7 @@ struct DevScene {
     const int32_t *tri_med;    // 2 * n_tris
     const int32_t *light_med;  // one per entry of dlights
     int n_media, cam_med;
+    const DevBsdf *bsdfs;  // beside mats, one per table entry (bre_set_materials_ex); last: the layout before it stays
 };
 
 // Host side of the scene: everything prepare_geometry derives, in host memory; the context uploads
@@ -237,12 +255,13 @@ struct HostScene {
     std::vector<DLight> dlights;
     std::vector<float> light_func, light_cdf;
     std::vector<bre_material> mats;
+    std::vector<DevBsdf> bsdfs;
     int depth = 0;  // deepest node of the BVH (root = 1)
 };
 
-// The context's specular materials (bre_set_materials): the table and the per-triangle index (-1: matte)
+// The context's materials (bre_set_materials, bre_set_materials_ex): the table and the per-triangle index (-1: matte)
 struct MaterialMap {
-    const bre_material *mats = nullptr;
+    const bre_material_ex *mats = nullptr;
     int n_mats = 0;
     const int32_t *tri_mat = nullptr;  // one per scene triangle when n_mats > 0
 };
@@ -255,6 +274,9 @@ void prepare_geometry(const bre_scene *s, HostScene *out, const bre_light *light
                       const MaterialMap &mm = MaterialMap());
 // a bre_light as the PointLight / SpotLight constructor leaves it
 DLight prepare_light(const bre_light &l);
+// a table entry as its material leaves the BSDF (plastic.cpp:45-70, metal.cpp:59-80, matte.cpp:45-62); type 0 for
+// a mirror, glass or interface
+DevBsdf make_bsdf(const bre_material_ex &m);
 // a medium as its constructor leaves it: sigma_t = sigma_a + sigma_s per channel; for a grid, channel 0 of it,
 // 1 / max_density and `d_density`, the device copy of the grid (the grid arguments are not read otherwise)
 DevMedium make_medium(int type, const float sigma_a[3], const float sigma_s[3], float g, const int32_t grid_n[3],
@@ -739,6 +761,271 @@ BRE_TD bool specular_sample(const bre_material &m, f3 wo, float u0, int mode, f3
     return true;
 }
 
+// ---- plastic, metal and rough matte: the lobes (reflection.{h,cpp}, microfacet.{h,cpp}) and the general BSDF ----
+BRE_TD bool is_inf(float v) { return fabsf(v) == __builtin_huge_valf(); }
+// the shading-frame trigonometry of reflection.h:56-83
+BRE_TD float cos2_theta(f3 w) { return w.z * w.z; }
+BRE_TD float sin2_theta(f3 w) { return smax(0.f, 1.f - cos2_theta(w)); }
+BRE_TD float sin_theta(f3 w) { return sqrtf(sin2_theta(w)); }
+BRE_TD float tan_theta(f3 w) { return sin_theta(w) / w.z; }
+BRE_TD float tan2_theta(f3 w) { return sin2_theta(w) / cos2_theta(w); }
+BRE_TD float cos_phi(f3 w) {
+    const float s = sin_theta(w);
+    return (s == 0) ? 1.f : clampf_ref(w.x / s, -1.f, 1.f);
+}
+BRE_TD float sin_phi(f3 w) {
+    const float s = sin_theta(w);
+    return (s == 0) ? 0.f : clampf_ref(w.y / s, -1.f, 1.f);
+}
+
+// TrowbridgeReitzDistribution::RoughnessToAlpha, microfacet.h:123-128 (host: a constant of the material)
+BRE_TD float roughness_to_alpha(float roughness) {
+    roughness = smax(roughness, 1e-3f);
+    const float x = bre_logf(roughness);
+    return 1.62142f + 0.819955f * x + 0.1734f * x * x + 0.0171201f * x * x * x + 0.000640711f * x * x * x * x;
+}
+// TrowbridgeReitzDistribution::D, microfacet.cpp:155-163
+BRE_TD float tr_D(float ax, float ay, f3 wh) {
+    const float tan2 = tan2_theta(wh);
+    if (is_inf(tan2)) return 0.f;
+    const float cos4 = cos2_theta(wh) * cos2_theta(wh);
+    const float cp = cos_phi(wh), sp = sin_phi(wh);
+    const float e = ((cp * cp) / (ax * ax) + (sp * sp) / (ay * ay)) * tan2;
+    return 1 / (kPi * ax * ay * cos4 * (1 + e) * (1 + e));
+}
+// TrowbridgeReitzDistribution::Lambda, microfacet.cpp:176-184
+BRE_TD float tr_lambda(float ax, float ay, f3 w) {
+    const float abs_tan = fabsf(tan_theta(w));
+    if (is_inf(abs_tan)) return 0.f;
+    const float cp = cos_phi(w), sp = sin_phi(w);
+    const float alpha = sqrtf((cp * cp) * ax * ax + (sp * sp) * ay * ay);
+    const float a2t2 = (alpha * abs_tan) * (alpha * abs_tan);
+    return (-1 + sqrtf(1.f + a2t2)) / 2;
+}
+// MicrofacetDistribution::G1 and G, microfacet.h:54-60
+BRE_TD float tr_G1(float ax, float ay, f3 w) { return 1 / (1 + tr_lambda(ax, ay, w)); }
+BRE_TD float tr_G(float ax, float ay, f3 wo, f3 wi) { return 1 / (1 + tr_lambda(ax, ay, wo) + tr_lambda(ax, ay, wi)); }
+// TrowbridgeReitzSample11, microfacet.cpp:238-282.  Its normal-incidence branch compares against a double and
+// calls the double sqrt, cos and sin (unqualified names on Floats): (float)sqrt((double)x) is sqrtf(x) (a
+// correctly rounded root of a 24-bit value survives the second rounding), the double product is an IEEE
+// operation, and cos / sin are bre_sincos_2pi, the one place where "bit-exact" carries a stated exception
+// (DESIGN.md section 23).  The CHECKs of :280-281 are not reproduced.
+BRE_TD void tr_sample11(float cos_t, float U1, float U2, float &slope_x, float &slope_y) {
+    if ((double)cos_t > .9999) {
+        const float r = sqrtf(U1 / (1 - U1));
+        const float phi = (float)(6.28318530718 * (double)U2);
+        double s, c;
+        bre_sincos_2pi((double)phi, &s, &c);
+        slope_x = (float)((double)r * c);
+        slope_y = (float)((double)r * s);
+        return;
+    }
+    const float sin_t = sqrtf(smax(0.f, 1.f - cos_t * cos_t));
+    const float tan_t = sin_t / cos_t;
+    const float a = 1 / tan_t;
+    const float G1 = 2 / (1 + sqrtf(1.f + 1.f / (a * a)));
+    const float A = 2 * U1 / G1 - 1;
+    float tmp = 1.f / (A * A - 1.f);
+    if ((double)tmp > 1e10) tmp = (float)1e10;
+    const float B = tan_t;
+    const float D = sqrtf(smax(B * B * tmp * tmp - (A * A - B * B) * tmp, 0.f));
+    const float sx1 = B * tmp - D;
+    const float sx2 = B * tmp + D;
+    slope_x = (A < 0 || sx2 > 1.f / tan_t) ? sx1 : sx2;
+    float S;
+    if (U2 > 0.5f) {
+        S = 1.f;
+        U2 = 2.f * (U2 - .5f);
+    } else {
+        S = -1.f;
+        U2 = 2.f * (.5f - U2);
+    }
+    const float z = (U2 * (U2 * (U2 * 0.27385f - 0.73369f) + 0.46341f)) /
+                    (U2 * (U2 * (U2 * 0.093073f + 0.309420f) - 1.000000f) + 0.597999f);
+    slope_y = S * z * sqrtf(1.f + slope_x * slope_x);
+}
+// TrowbridgeReitzDistribution::Sample_wh on its sampleVisibleArea branch (microfacet.cpp:330-334) over
+// TrowbridgeReitzSample (:284-305)
+BRE_TD f3 tr_sample_wh(float ax, float ay, f3 wo, float u0, float u1) {
+    const bool flip = wo.z < 0;
+    const f3 wi = flip ? neg3(wo) : wo;
+    const f3 ws = normalize3(mk(ax * wi.x, ay * wi.y, wi.z));
+    float sx, sy;
+    tr_sample11(ws.z, u0, u1, sx, sy);
+    const float cp = cos_phi(ws), sp = sin_phi(ws);
+    const float tmp = cp * sx - sp * sy;
+    sy = sp * sx + cp * sy;
+    sx = tmp;
+    sx = ax * sx;
+    sy = ay * sy;
+    const f3 wh = normalize3(mk(-sx, -sy, 1.f));
+    return flip ? neg3(wh) : wh;
+}
+// MicrofacetDistribution::Pdf with sampleVisibleArea, microfacet.cpp:338-341
+BRE_TD float tr_pdf(float ax, float ay, f3 wo, f3 wh) {
+    return tr_D(ax, ay, wh) * tr_G1(ax, ay, wo) * fabsf(dot3(wo, wh)) / fabsf(wo.z);
+}
+// FrConductor, reflection.cpp:71-95, one channel of it with etai = 1 (FresnelConductor(1., eta, k))
+BRE_TD float fr_conductor(float cos_i, float etat, float k) {
+    cos_i = clampf_ref(cos_i, -1.f, 1.f);
+    const float eta = etat / 1.f, etak = k / 1.f;
+    const float cos2 = cos_i * cos_i;
+    const float sin2 = (float)(1. - (double)cos2);
+    const float eta2 = eta * eta, etak2 = etak * etak;
+    const float t0 = eta2 - etak2 - sin2;
+    const float a2b2 = sqrtf(t0 * t0 + eta2 * 4.f * etak2);
+    const float t1 = a2b2 + cos2;
+    const float a = sqrtf((a2b2 + t0) * 0.5f);
+    const float t2 = a * ((float)2 * cos_i);
+    const float Rs = (t1 - t2) / (t1 + t2);
+    const float t3 = a2b2 * cos2 + sin2 * sin2;
+    const float t4 = t2 * sin2;
+    const float Rp = Rs * (t3 - t4) / (t3 + t4);
+    return (Rp + Rs) * 0.5f;
+}
+
+// BxDF::f of lobe `lobe` (kLobeDiffuse: LambertianReflection::f, reflection.cpp:178-180, or OrenNayar::f,
+// :197-219; kLobeMicro: MicrofacetReflection::f, :226-236); wo, wi in the shading frame
+BRE_TD void lobe_f(const DevBsdf &m, int lobe, f3 wo, f3 wi, float f[3]) {
+    if (lobe == kLobeDiffuse) {
+        if (!m.oren) {
+            for (int c = 0; c < 3; ++c) f[c] = m.kd[c] * kInvPi;
+            return;
+        }
+        const float sin_i = sin_theta(wi), sin_o = sin_theta(wo);
+        float max_cos = 0;
+        if ((double)sin_i > 1e-4 && (double)sin_o > 1e-4) {
+            const float spi = sin_phi(wi), cpi = cos_phi(wi);
+            const float spo = sin_phi(wo), cpo = cos_phi(wo);
+            const float d_cos = cpi * cpo + spi * spo;
+            max_cos = smax(0.f, d_cos);
+        }
+        float sin_alpha, tan_beta;
+        if (fabsf(wi.z) > fabsf(wo.z)) {
+            sin_alpha = sin_o;
+            tan_beta = sin_i / fabsf(wi.z);
+        } else {
+            sin_alpha = sin_i;
+            tan_beta = sin_o / fabsf(wo.z);
+        }
+        const float s = m.A + m.B * max_cos * sin_alpha * tan_beta;
+        for (int c = 0; c < 3; ++c) f[c] = m.kd[c] * kInvPi * s;
+        return;
+    }
+    f[0] = f[1] = f[2] = 0.f;
+    const float cos_o = fabsf(wo.z), cos_i = fabsf(wi.z);
+    f3 wh = add3(wi, wo);
+    if (cos_i == 0 || cos_o == 0) return;
+    if (wh.x == 0 && wh.y == 0 && wh.z == 0) return;
+    wh = normalize3(wh);
+    const float ci = dot3(wi, wh);
+    const float D = tr_D(m.ax, m.ay, wh), G = tr_G(m.ax, m.ay, wo, wi);
+    const float den = 4 * cos_i * cos_o;
+    if (m.conductor) {
+        for (int c = 0; c < 3; ++c) f[c] = m.ks[c] * D * G * fr_conductor(fabsf(ci), m.ceta[c], m.ck[c]) / den;
+    } else {
+        const float F = fr_dielectric(ci, 1.5f, 1.f);
+        for (int c = 0; c < 3; ++c) f[c] = m.ks[c] * D * G * F / den;
+    }
+}
+// BxDF::Pdf (reflection.cpp:387-389) or MicrofacetReflection::Pdf (:419-423)
+BRE_TD float lobe_pdf(const DevBsdf &m, int lobe, f3 wo, f3 wi) {
+    if (lobe == kLobeDiffuse) return (wo.z * wi.z > 0) ? fabsf(wi.z) * kInvPi : 0.f;
+    if (!(wo.z * wi.z > 0)) return 0.f;
+    const f3 wh = normalize3(add3(wo, wi));
+    return tr_pdf(m.ax, m.ay, wo, wh) / (4 * dot3(wo, wh));
+}
+// BxDF::Sample_f (reflection.cpp:378-385) or MicrofacetReflection::Sample_f (:405-417); pdf arrives as 0 and
+// stays 0 where the lobe returns early; wo.z != 0
+BRE_TD void lobe_sample(const DevBsdf &m, int lobe, f3 wo, float u0, float u1, f3 &wi, float &pdf, float f[3]) {
+    f[0] = f[1] = f[2] = 0.f;
+    if (lobe == kLobeDiffuse) {
+        wi = cosine_hemisphere(u0, u1);
+        if (wo.z < 0) wi.z *= -1;
+        pdf = lobe_pdf(m, lobe, wo, wi);
+        lobe_f(m, lobe, wo, wi, f);
+        return;
+    }
+    const f3 wh = tr_sample_wh(m.ax, m.ay, wo, u0, u1);
+    const float d = dot3(wo, wh);
+    wi = add3(neg3(wo), scale3(wh, 2 * d));  // Reflect, reflection.h:92-94
+    if (!(wo.z * wi.z > 0)) return;
+    pdf = tr_pdf(m.ax, m.ay, wo, wh) / (4 * dot3(wo, wh));
+    lobe_f(m, lobe, wo, wi, f);
+}
+
+// BSDF::f (reflection.cpp:670-683) for flags that match every lobe here (BSDF_ALL, or BSDF_ALL & ~BSDF_SPECULAR):
+// all of them reflect, so f is their sum on the geometric normal's reflecting side and 0 on the other
+BRE_TD void bsdf_f(const PTri &q, const DevBsdf &m, f3 wo_w, f3 wi_w, float f[3]) {
+    f[0] = f[1] = f[2] = 0.f;
+    const f3 wi = to_local(q, wi_w), wo = to_local(q, wo_w);
+    if (wo.z == 0) return;
+    if (!(dot3(wi_w, q.n) * dot3(wo_w, q.n) > 0)) return;
+    for (int lobe = kLobeDiffuse; lobe <= kLobeMicro; lobe <<= 1) {
+        if (!(m.lobes & lobe)) continue;
+        float fl[3];
+        lobe_f(m, lobe, wo, wi, fl);
+        for (int c = 0; c < 3; ++c) f[c] = f[c] + fl[c];
+    }
+}
+// BSDF::Pdf, reflection.cpp:770-785
+BRE_TD float bsdf_pdf(const PTri &q, const DevBsdf &m, f3 wo_w, f3 wi_w) {
+    if (m.lobes == 0) return 0.f;
+    const f3 wo = to_local(q, wo_w), wi = to_local(q, wi_w);
+    if (wo.z == 0) return 0.f;
+    float pdf = 0.f;
+    int n = 0;
+    for (int lobe = kLobeDiffuse; lobe <= kLobeMicro; lobe <<= 1) {
+        if (!(m.lobes & lobe)) continue;
+        ++n;
+        pdf += lobe_pdf(m, lobe, wo, wi);
+    }
+    return pdf / (float)n;
+}
+// BSDF::Sample_f, reflection.cpp:703-768: the component by floor(u[0] * matchingComps), u[0] remapped, the
+// lobe's Sample_f, then with two lobes the other's Pdf added and halved and f taken again over both.  Returns
+// false where Sample_f returns 0 before f is known (no lobe, wo.z == 0 with pdf untouched, pdf == 0); type is
+// then 0.
+BRE_TD bool bsdf_sample(const PTri &q, const DevBsdf &m, f3 wo_w, float u0, float u1, f3 &wi_w, float &pdf, float f[3],
+                        int &type) {
+    f[0] = f[1] = f[2] = 0.f;
+    type = 0;
+    const int n = (m.lobes & kLobeDiffuse ? 1 : 0) + (m.lobes & kLobeMicro ? 1 : 0);
+    if (n == 0) {
+        pdf = 0.f;
+        return false;
+    }
+    const int fl = (int)floorf(u0 * (float)n);
+    const int comp = fl < n - 1 ? fl : n - 1;
+    const int lobe = (n == 2) ? (comp == 0 ? kLobeDiffuse : kLobeMicro) : m.lobes;
+    const float ur = smin(u0 * (float)n - (float)comp, kOneMinusEps);
+    const f3 wo = to_local(q, wo_w);
+    if (wo.z == 0) return false;
+    pdf = 0.f;
+    f3 wi = mk(0.f, 0.f, 0.f);
+    lobe_sample(m, lobe, wo, ur, u1, wi, pdf, f);
+    if (pdf == 0) {
+        f[0] = f[1] = f[2] = 0.f;
+        return false;
+    }
+    type = kBsdfReflection | (lobe == kLobeDiffuse ? kBsdfDiffuse : kBsdfGlossy);
+    wi_w = to_world(q, wi);
+    if (n > 1) {
+        const int other = lobe == kLobeDiffuse ? kLobeMicro : kLobeDiffuse;
+        pdf += lobe_pdf(m, other, wo, wi);
+        pdf /= (float)n;
+        const bool reflect = dot3(wi_w, q.n) * dot3(wo_w, q.n) > 0;
+        f[0] = f[1] = f[2] = 0.f;
+        if (reflect)
+            for (int l = kLobeDiffuse; l <= kLobeMicro; l <<= 1) {
+                float fl2[3];
+                lobe_f(m, l, wo, wi, fl2);
+                for (int c = 0; c < 3; ++c) f[c] = f[c] + fl2[c];
+            }
+    }
+    return true;
+}
+
 // ---- camera pass (bre_camera.hip) ----
 constexpr int kHaltonDims = 1000;  // HaltonSampler's PrimeTableSize = AwesomeSampler's limit (photonbeam.cpp:460)
 
@@ -763,11 +1050,12 @@ struct CamSlots {
 void prepare_camera(const bre_scene *s, int width, int height, DevCamera *c, std::vector<uint16_t> *perms);
 int64_t camera_slots(int width, int height);
 // `planes`: the slot planes of `s` (max_depth, plus the segment budget with media and an interface triangle);
-// `media`: the context holds media (the kernel that carries a medium per ray)
+// `media`: the context holds media (the kernel that carries a medium per ray); `glossy`: its table holds a
+// plastic, metal or matte entry (the kernel with the general BSDF)
 hipError_t launch_camera(const DevScene *scene, int stack_depth, const DevCamera *cam, const uint16_t *perms, int width,
                          int height, int iteration, int max_depth, int render_surfaces, int render_media,
                          const CamSlots &s, float *surface, unsigned int *flags, int shard_rank, int shard_count,
-                         int shard_block, int classes, int planes, bool media, hipStream_t stream);
+                         int shard_block, int classes, int planes, bool media, bool glossy, hipStream_t stream);
 constexpr unsigned int kCamFlagBudget = 1u;  // k_camera's flag word: a path overran its segment budget
 size_t camera_scan_temp_bytes(int64_t n);
 hipError_t launch_camera_scan(void *tmp, size_t tmp_bytes, const CamSlots &s, int64_t nslots, int max_depth,
@@ -777,19 +1065,27 @@ hipError_t launch_camera_compact(const CamSlots &s, int64_t nslots, int max_dept
 
 // bre_device_check kind 12 (bre_check.hip): specular_sample on n records of 6 floats, 6 words out each
 hipError_t launch_check_specular(int64_t n, const float *x, float *y, hipStream_t s);
+// kind 13 (bre_check.hip): bsdf_sample, bsdf_f and bsdf_pdf on n records of 9 floats against `table`, 12 words out each
+hipError_t launch_check_bsdf(int64_t n, const float *x, const DevBsdf *table, int n_table, float *y, hipStream_t s);
 
 // dynamic LDS of a photon / camera launch: the scene traversal stack of every thread of a block
 inline size_t scene_stack_bytes(int stack_depth, int block) {
     return (size_t)(stack_depth > 0 ? stack_depth : 1) * (size_t)block * sizeof(int);
 }
 
+// waves per SIMD the glossy (GL) instantiations of k_photons and k_camera are bounded to; the others keep 6
+constexpr int kGlossyWaves = 2;
+
 // photon pass launchers (bre_photon.hip)
+// dynamic LDS of a photon launch: the traversal stack and, for the glossy kernels, max_depth suspended frames a thread
+size_t photon_lds_bytes(int stack_depth, int max_depth, bool glossy);
 // mode 0: count beams per photon; 1: write them at offsets (over > 0: only photons with more than `over`
 // beams); 2: write the first `over` beams to per-photon slots and count them all (single-trace form)
-// `media`: the context holds media (the kernels that carry a medium per ray)
+// `media`: the context holds media (the kernels that carry a medium per ray); `glossy`: its table holds a plastic,
+// metal or matte entry (the kernels with the general BSDF)
 hipError_t launch_photons(const DevScene *scene, int stack_depth, int64_t n, uint64_t seq0, int max_depth,
                           float radius, int32_t *counts, const int64_t *offsets, const BeamOut &out, int mode,
-                          int over, bool media, hipStream_t s);
+                          int over, bool media, bool glossy, hipStream_t s);
 // the single-trace form's copy of each photon's slots to its offsets
 hipError_t launch_photon_slots(int64_t n, int cap, const int32_t *counts, const int64_t *offsets,
                                const BeamView &slots, const BeamOut &out, hipStream_t s);

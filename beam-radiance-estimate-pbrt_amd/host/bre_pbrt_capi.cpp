@@ -76,6 +76,25 @@ bre_status bre_pbrt_get_materials(const bre_pbrt *p, int32_t mat_capacity, bre_m
     const int32_t km = mat_capacity < nm ? mat_capacity : nm;
     const int64_t kt = tri_capacity < nt ? tri_capacity : nt;
     if ((km > 0 && !materials) || (kt > 0 && !triangle_material)) return BRE_ERR_INVALID_ARG;
+    // a plastic, a metal or a matte with sigma does not fit the narrow record: bre_pbrt_get_materials_ex
+    for (int32_t i = 0; i < nm; ++i)
+        if (p->scene.materials[(size_t)i].type >= BRE_MATERIAL_MATTE) return BRE_ERR_STATE;
+    for (int32_t i = 0; i < km; ++i) memcpy(&materials[i], &p->scene.materials[(size_t)i], sizeof(bre_material));
+    for (int64_t i = 0; i < kt; ++i) triangle_material[i] = p->scene.triangleMaterial[(size_t)i];
+    return BRE_OK;
+}
+
+bre_status bre_pbrt_get_materials_ex(const bre_pbrt *p, int32_t mat_capacity, bre_material_ex *materials,
+                                     int32_t *n_materials, int64_t tri_capacity, int32_t *triangle_material,
+                                     int64_t *n_triangles) {
+    if (!p || !p->ok || mat_capacity < 0 || tri_capacity < 0) return BRE_ERR_INVALID_ARG;
+    const int32_t nm = (int32_t)p->scene.materials.size();
+    const int64_t nt = (int64_t)p->scene.triangleMaterial.size();
+    if (n_materials) *n_materials = nm;
+    if (n_triangles) *n_triangles = nt;
+    const int32_t km = mat_capacity < nm ? mat_capacity : nm;
+    const int64_t kt = tri_capacity < nt ? tri_capacity : nt;
+    if ((km > 0 && !materials) || (kt > 0 && !triangle_material)) return BRE_ERR_INVALID_ARG;
     for (int32_t i = 0; i < km; ++i) materials[i] = p->scene.materials[(size_t)i];
     for (int64_t i = 0; i < kt; ++i) triangle_material[i] = p->scene.triangleMaterial[(size_t)i];
     return BRE_OK;

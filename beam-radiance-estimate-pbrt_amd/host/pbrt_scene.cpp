@@ -482,6 +482,13 @@ struct Material {
     // "index" default 1.5, roughness 0): the bre_material of the shapes declared under it
     float kr[3] = {1.f, 1.f, 1.f}, kt[3] = {1.f, 1.f, 1.f};
     float eta = 1.5f;
+    // "plastic" (CreatePlasticMaterial, plastic.cpp:72-83: "Kd" and "Ks" default 0.25, "roughness" 0.1) and "metal"
+    // (CreateMetalMaterial with explicit "eta" and "k": "roughness" 0.01, "uroughness" / "vroughness" 0 = not
+    // given), "remaproughness" true; `kd` above stays the matte default under them, as under a mirror
+    float pkd[3] = {0.25f, 0.25f, 0.25f}, ks[3] = {0.25f, 0.25f, 0.25f};
+    float ceta[3] = {0.f, 0.f, 0.f}, ck[3] = {0.f, 0.f, 0.f};
+    float roughness = 0.1f, uroughness = 0.f, vroughness = 0.f;
+    bool remap = true;
 };
 
 struct GraphicsState {
@@ -779,40 +786,128 @@ void Parser::MakeMaterial(Lexer &lx, int line, const std::string &type, const Pa
         *m = Material();
         return;
     }
+    if (type == "plastic" || type == "metal") {
+        const bool metal = type == "metal";
+        bool ok = true;
+        const auto spectrum = [&](const char *name, float *v) {
+            if (ps.Has(name) && !ps.FindOneSpectrum(name, v)) {
+                Error(lx, line, "%s \"%s\" must be an rgb or xyz value (textures are not supported)", type.c_str(), name);
+                ok = false;
+            }
+        };
+        const auto number = [&](const char *name, float d) {
+            if (ps.Has(name) && !ps.FindFloats(name)) {
+                Error(lx, line, "%s \"%s\" must be a float (textures are not supported)", type.c_str(), name);
+                ok = false;
+            }
+            return ps.FindOneFloat(name, d);
+        };
+        if (metal) {
+            // CreateMetalMaterial's defaults are the copper spectra, through Spectrum::FromSampled and the CIE tables
+            if (!ps.Has("eta") || !ps.Has("k")) {
+                Error(lx, line, "metal needs explicit \"rgb eta\" and \"rgb k\" (the default copper spectra are not "
+                      "supported)");
+                ok = false;
+            }
+            spectrum("eta", m->ceta);
+            spectrum("k", m->ck);
+            m->roughness = number("roughness", 0.01f);
+            m->uroughness = number("uroughness", 0.f);
+            m->vroughness = number("vroughness", 0.f);
+            const float u = m->uroughness != 0.f ? m->uroughness : m->roughness;
+            const float v = m->vroughness != 0.f ? m->vroughness : m->roughness;
+            if (ok && (!(u > 0.f) || !(v > 0.f) || !std::isfinite(u) || !std::isfinite(v))) {
+                Error(lx, line, "metal \"roughness\" / \"uroughness\" / \"vroughness\" must be finite and > 0");
+                ok = false;
+            }
+            if (ok && (m->ceta[0] == 0.f || m->ceta[1] == 0.f || m->ceta[2] == 0.f)) {
+                Error(lx, line, "metal \"eta\" must not be 0 in any channel");
+                ok = false;
+            }
+        } else {
+            spectrum("Kd", m->pkd);
+            spectrum("Ks", m->ks);
+            m->roughness = number("roughness", 0.1f);
+            if (ok && (!(m->roughness > 0.f) || !std::isfinite(m->roughness))) {
+                Error(lx, line, "plastic \"roughness\" must be finite and > 0");
+                ok = false;
+            }
+        }
+        m->remap = ps.FindOneBool("remaproughness", true);
+        if (ps.Has("bumpmap")) {
+            Error(lx, line, "%s \"bumpmap\" is not supported by the GPU scene model", type.c_str());
+            ok = false;
+        }
+        ps.FindOneString("type", "");
+        if (ok) {
+            ReportUnused(lx, line, ps);
+            return;
+        }
+        Error(lx, line, "using \"matte\" in place of this \"%s\"", type.c_str());
+        *m = Material();
+        return;
+    }
     if (type != "matte") {
         if (type == "glass")
             Error(lx, line, "Material \"glass\" is not supported as a direct statement; declare it with "
                   "MakeNamedMaterial \"name\" \"string type\" \"glass\" and NamedMaterial \"name\"; using \"matte\"");
         else
-            Error(lx, line, "Material \"%s\" is not supported (matte, mirror, named glass); using \"matte\"", type.c_str());
+            Error(lx, line, "Material \"%s\" is not supported (matte, plastic, metal, mirror, named glass); using \"matte\"",
+                  type.c_str());
         m->type = "matte";
     }
     if (ps.Has("Kd") && !ps.FindOneSpectrum("Kd", m->kd))
         Error(lx, line, "matte \"Kd\" must be an rgb or xyz value (textures are not supported)");
+    if (ps.Has("sigma") && !ps.FindFloats("sigma"))
+        Error(lx, line, "matte \"sigma\" must be a float (textures are not supported)");
     m->sigma = ps.FindOneFloat("sigma", 0.f);
-    if (m->sigma != 0.f) Error(lx, line, "matte \"sigma\" must be 0 (Oren-Nayar is not supported)");
+    if (!std::isfinite(m->sigma)) {
+        Error(lx, line, "matte \"sigma\" must be finite");
+        m->sigma = 0.f;
+    }
     ps.FindOneString("type", "");
     ReportUnused(lx, line, ps);
 }
 
-// The table entry of a mirror or glass material (-1 for matte): entries are shared by equal materials
+// The table entry of a mirror, glass, plastic or metal material or of a matte with sigma (-1 for a matte with
+// sigma 0, which stays the triangle's own kd): entries are shared by equal materials
 int Parser::SpecularIndex(Lexer &lx, int line, const Material &m) {
-    if (m.type != "mirror" && m.type != "glass" && !m.none) return -1;
-    bre_material b;
+    const bool rough_matte = m.type == "matte" && m.sigma != 0.f;
+    if (m.type != "mirror" && m.type != "glass" && m.type != "plastic" && m.type != "metal" && !rough_matte && !m.none)
+        return -1;
+    bre_material_ex b;
     memset(&b, 0, sizeof(b));
     if (m.none) {
         b.type = BRE_MATERIAL_INTERFACE;  // Material "" / "none": no BSDF (kParseMedia)
+    } else if (rough_matte) {
+        b.type = BRE_MATERIAL_MATTE;
+        memcpy(b.kd, m.kd, sizeof(b.kd));
+        b.sigma = m.sigma;
+    } else if (m.type == "plastic") {
+        b.type = BRE_MATERIAL_PLASTIC;
+        memcpy(b.kd, m.pkd, sizeof(b.kd));
+        memcpy(b.ks, m.ks, sizeof(b.ks));
+        b.roughness = m.roughness;
+        b.remap = m.remap ? 1 : 0;
+    } else if (m.type == "metal") {
+        b.type = BRE_MATERIAL_METAL;
+        memcpy(b.ceta, m.ceta, sizeof(b.ceta));
+        memcpy(b.ck, m.ck, sizeof(b.ck));
+        b.roughness = m.roughness;
+        b.uroughness = m.uroughness;
+        b.vroughness = m.vroughness;
+        b.remap = m.remap ? 1 : 0;
     } else {
         b.type = m.type == "mirror" ? BRE_MATERIAL_MIRROR : BRE_MATERIAL_GLASS;
         memcpy(b.kr, m.kr, sizeof(b.kr));
         if (b.type == BRE_MATERIAL_GLASS) memcpy(b.kt, m.kt, sizeof(b.kt));
         b.eta = b.type == BRE_MATERIAL_GLASS ? m.eta : 1.f;
     }
-    std::vector<bre_material> &table = out_->materials;
+    std::vector<bre_material_ex> &table = out_->materials;
     for (size_t k = 0; k < table.size(); ++k)
         if (memcmp(&table[k], &b, sizeof(b)) == 0) return (int)k;
     if ((int)table.size() >= BRE_MAX_MATERIALS) {
-        Error(lx, line, "more than BRE_MAX_MATERIALS (%d) mirror / glass materials; using \"matte\"", BRE_MAX_MATERIALS);
+        Error(lx, line, "more than BRE_MAX_MATERIALS (%d) table materials; using \"matte\"", BRE_MAX_MATERIALS);
         return -1;
     }
     table.push_back(b);

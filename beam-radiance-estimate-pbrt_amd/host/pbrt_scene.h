@@ -18,10 +18,14 @@
 //     as TriangleMesh does, mesh->p[i] = ObjectToWorld(P[i]), shapes/triangle.cpp; flip =
 //     ReverseOrientation ^ TransformSwapsHandedness); any number up to BRE_MAX_SCENE_TRIANGLES (more
 //     than BRE_MAX_TRIANGLES go through bre_scene.triangles_ext).
-//   * Material "matte" with "Kd" (rgb, default 0.5) and sigma 0; MakeNamedMaterial/NamedMaterial.
+//   * Material "matte" with "Kd" (rgb, default 0.5) and "sigma" (0: the triangle's own kd; otherwise Oren-Nayar, a
+//     table entry); MakeNamedMaterial/NamedMaterial.
+//   * Material "plastic" ("Kd", "Ks" default 0.25, "roughness" 0.1, "remaproughness") and "metal" (explicit
+//     "rgb eta" and "rgb k"; "roughness" 0.01, "uroughness" / "vroughness", "remaproughness"), direct or named:
+//     wide table entries (bre_material_ex).
 //   * Material "mirror" ("Kr", default 0.9), and MakeNamedMaterial with "string type" "mirror" or "glass"
 //     ("Kr", "Kt" default 1; "eta", else "index", default 1.5; "uroughness" / "vroughness" must be 0): a
-//     bre_material in PbrtScene::materials, referred to by the triangles declared under it
+//     bre_material_ex in PbrtScene::materials, referred to by the triangles declared under it
 //     (PbrtScene::triangleMaterial).  "bumpmap" and texture-valued parameters are reported and the statement
 //     falls back to matte.  The direct statement Material "glass" is reported as unsupported.
 //   * AreaLightSource "diffuse" ("L" x "scale", one-sided): every triangle of an emitting mesh is
@@ -136,7 +140,8 @@ struct PbrtScene {
     std::vector<bre_light> lights;    // LightSource "spot" statements, in declaration order (bre_set_lights)
     // Material "mirror" and named "mirror" / "glass" materials in use (bre_set_materials): the table, and per
     // scene triangle its index into it (-1: matte); both empty for a matte-only scene
-    std::vector<bre_material> materials;
+    // (wide records: plastic, metal and matte with "sigma" are entries too, bre_set_materials_ex)
+    std::vector<bre_material_ex> materials;
     std::vector<int32_t> triangleMaterial;
     SceneMedia media;                 // kParseMedia: the scene's media; scene.has_medium is then BRE_MEDIUM_NONE
     FilmDesc film;

@@ -198,7 +198,7 @@ int PhotonBeamIntegrator::OnImage(int32_t, const float *L, void *user) {
 }
 
 bool PhotonBeamIntegrator::Render(const bre_scene &scene, const std::vector<bre_light> &lights,
-                                  const std::vector<bre_material> &materials,
+                                  const std::vector<bre_material_ex> &materials,
                                   const std::vector<int32_t> &triangleMaterial, const SceneMedia *media) {
     if (!ctx_) return false;
     static const SceneMedia none;
@@ -208,8 +208,8 @@ bool PhotonBeamIntegrator::Render(const bre_scene &scene, const std::vector<bre_
             bre_set_media(c, sm.media.data(), (int32_t)sm.media.size(), sm.triInside.data(), sm.triOutside.data(),
                           (int64_t)sm.triInside.size(), sm.cameraMedium, sm.lightMedium.data(),
                           (int32_t)sm.lightMedium.size()) != BRE_OK ||
-            bre_set_materials(c, materials.data(), (int32_t)materials.size(), triangleMaterial.data(),
-                              (int64_t)triangleMaterial.size()) != BRE_OK) {
+            bre_set_materials_ex(c, materials.data(), (int32_t)materials.size(), triangleMaterial.data(),
+                                 (int64_t)triangleMaterial.size()) != BRE_OK) {
             err_ = bre_last_error(c);
             return false;
         }

@@ -153,11 +153,11 @@ class PhotonBeamIntegrator {
 
     // Integrator::Render(const Scene &): false (with LastError) on any failure.
     // `lights`: the scene's point and spot lights, set on every context (bre_set_lights) before the render.
-    // `materials`, `triangleMaterial`: its mirror / glass table and per-triangle map (bre_set_materials), likewise.
+    // `materials`, `triangleMaterial`: its material table (wide records) and per-triangle map (bre_set_materials_ex), likewise.
     // `media`: its media bounded by surfaces (bre_set_media, set before the materials: an interface needs them);
     // null or empty: none.
     bool Render(const bre_scene &scene, const std::vector<bre_light> &lights = {},
-                const std::vector<bre_material> &materials = {}, const std::vector<int32_t> &triangleMaterial = {},
+                const std::vector<bre_material_ex> &materials = {}, const std::vector<int32_t> &triangleMaterial = {},
                 const SceneMedia *media = nullptr);
     // The last image handed to the film, after WriteImage's conversion (top row first, 3 floats
     // per pixel), and how many times the film was written.

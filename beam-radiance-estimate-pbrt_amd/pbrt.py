@@ -16,7 +16,7 @@ import os
 import numpy as np
 
 from . import load_library
-from .scene import Light, Material, Medium, RenderParams, Scene
+from .scene import Light, Material, MaterialEx, Medium, RenderParams, Scene
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 HOST_LIB_PATH = os.path.join(HERE, "libbre_host.so")
@@ -25,7 +25,7 @@ CLI_PATH = os.path.join(HERE, "host", "bre_pbrt")
 PBRT_MEDIA = 1  # BRE_PBRT_MEDIA
 EXPORTS = ["bre_pbrt_parse_file", "bre_pbrt_parse_string", "bre_pbrt_parse_file_ex", "bre_pbrt_parse_string_ex",
            "bre_pbrt_get_media", "bre_pbrt_free", "bre_pbrt_messages",
-           "bre_pbrt_get_scene", "bre_pbrt_get_lights", "bre_pbrt_get_materials", "bre_pbrt_make_spot_light", "bre_pbrt_get_render_params", "bre_pbrt_get_film", "bre_pbrt_render",
+           "bre_pbrt_get_scene", "bre_pbrt_get_lights", "bre_pbrt_get_materials", "bre_pbrt_get_materials_ex", "bre_pbrt_make_spot_light", "bre_pbrt_get_render_params", "bre_pbrt_get_film", "bre_pbrt_render",
            "bre_pbrt_render_devices", "bre_film_finalize", "bre_write_pfm", "bre_read_pfm"]
 
 _HOST = None
@@ -53,6 +53,7 @@ def load_host_library(path: str = HOST_LIB_PATH) -> ctypes.CDLL:
     lib.bre_pbrt_get_scene.argtypes = [P, P]
     lib.bre_pbrt_get_lights.argtypes = [P, I32, P, ctypes.POINTER(I32)]
     lib.bre_pbrt_get_materials.argtypes = [P, I32, P, ctypes.POINTER(I32), I64, P, ctypes.POINTER(I64)]
+    lib.bre_pbrt_get_materials_ex.argtypes = [P, I32, P, ctypes.POINTER(I32), I64, P, ctypes.POINTER(I64)]
     lib.bre_pbrt_make_spot_light.argtypes = [P, P, P, F, F, P, P, I32, P]
     lib.bre_pbrt_get_render_params.argtypes = [P, I32, P, ctypes.POINTER(I32)]
     lib.bre_pbrt_get_film.argtypes = [P, ctypes.POINTER(I32), ctypes.POINTER(I32), ctypes.POINTER(F),
@@ -96,14 +97,21 @@ class PbrtScene:
         self._lights_ref = arr
         # mirror / glass materials and the per-triangle index into them, for BeamGather.set_materials
         nm, nt = ctypes.c_int32(), ctypes.c_int64()
-        assert self._lib.bre_pbrt_get_materials(self._h, 0, None, ctypes.byref(nm), 0, None, ctypes.byref(nt)) == 0
-        marr = (Material * max(nm.value, 1))()
+        # .materials_ex: the table in its wide records (plastic, metal and matte with sigma are entries too);
+        # .materials: the narrow records where the scene has none of those (bre_pbrt_get_materials: BRE_ERR_STATE
+        # otherwise), else the wide ones
+        assert self._lib.bre_pbrt_get_materials_ex(self._h, 0, None, ctypes.byref(nm), 0, None, ctypes.byref(nt)) == 0
+        warr = (MaterialEx * max(nm.value, 1))()
         tm = np.full(nt.value, -1, np.int32)
-        assert self._lib.bre_pbrt_get_materials(self._h, nm.value, marr, None, nt.value,
-                                                tm.ctypes.data if nt.value else None, None) == 0
-        self.materials = [marr[i] for i in range(nm.value)]
+        assert self._lib.bre_pbrt_get_materials_ex(self._h, nm.value, warr, None, nt.value,
+                                                   tm.ctypes.data if nt.value else None, None) == 0
+        self.materials_ex = [warr[i] for i in range(nm.value)]
         self.triangle_material = tm
-        self._materials_ref = marr
+        marr = (Material * max(nm.value, 1))()
+        self.materials_status = self._lib.bre_pbrt_get_materials(self._h, nm.value, marr, None, 0, None, None)
+        assert self.materials_status in (0, 4)
+        self.materials = [marr[i] for i in range(nm.value)] if self.materials_status == 0 else self.materials_ex
+        self._materials_ref = (marr, warr)
         # media bounded by surfaces (parse_*(..., media=True)), for BeamGather.set_media; the grids stay the handle's
         nd, nt, cm, nl = ctypes.c_int32(), ctypes.c_int64(), ctypes.c_int32(), ctypes.c_int32()
         assert self._lib.bre_pbrt_get_media(self._h, 0, None, ctypes.byref(nd), 0, None, None, ctypes.byref(nt),

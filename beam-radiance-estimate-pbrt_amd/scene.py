@@ -96,10 +96,66 @@ def glass(kr=1.0, kt=1.0, eta: float = 1.5) -> Material:
     return Material(MATERIAL_GLASS, _rgb(kr), _rgb(kt), float(eta))
 
 
+MATERIAL_MATTE, MATERIAL_PLASTIC, MATERIAL_METAL = 4, 5, 6
+
+
+class MaterialEx(ctypes.Structure):
+    """bre_material_ex: the wide record (112 bytes), a Material followed by the parameters of pbrt's matte,
+    plastic and metal."""
+    _fields_ = [("type", ctypes.c_int32), ("kr", F3), ("kt", F3), ("eta", ctypes.c_float),
+                ("kd", F3), ("ks", F3), ("ceta", F3), ("ck", F3), ("roughness", ctypes.c_float),
+                ("uroughness", ctypes.c_float), ("vroughness", ctypes.c_float), ("sigma", ctypes.c_float),
+                ("remap", ctypes.c_int32), ("reserved", ctypes.c_int32 * 3)]
+
+    def to_bytes(self) -> bytes:
+        return ctypes.string_at(ctypes.addressof(self), ctypes.sizeof(self))
+
+
+def widen(m) -> "MaterialEx":
+    """A Material as the MaterialEx bre_set_materials makes of it; a MaterialEx as it is."""
+    if isinstance(m, MaterialEx):
+        return m
+    w = MaterialEx()
+    ctypes.memmove(ctypes.addressof(w), ctypes.addressof(m), ctypes.sizeof(Material))
+    return w
+
+
+def matte(kd=0.5, sigma: float = 0.0) -> MaterialEx:
+    """Material "matte" (matte.cpp:64-71): "Kd" (rgb or scalar, default 0.5), "sigma" in degrees (0: Lambertian,
+    otherwise Oren-Nayar)."""
+    m = MaterialEx()
+    m.type, m.kd, m.sigma = MATERIAL_MATTE, _rgb(kd), float(sigma)
+    return m
+
+
+def plastic(kd=0.25, ks=0.25, roughness: float = 0.1, remap: bool = True) -> MaterialEx:
+    """Material "plastic" (plastic.cpp:72-83): "Kd", "Ks" (default 0.25), "roughness" (0.1), "remaproughness"."""
+    m = MaterialEx()
+    m.type, m.kd, m.ks, m.roughness, m.remap = MATERIAL_PLASTIC, _rgb(kd), _rgb(ks), float(roughness), int(bool(remap))
+    return m
+
+
+def metal(eta, k, roughness: float = 0.01, uroughness: float = 0.0, vroughness: float = 0.0,
+          remap: bool = True) -> MaterialEx:
+    """Material "metal" (metal.cpp) with explicit "eta" and "k" (rgb or scalar): "roughness" (default 0.01),
+    "uroughness" / "vroughness" (0: not given, `roughness` is used), "remaproughness"."""
+    m = MaterialEx()
+    m.type, m.ceta, m.ck = MATERIAL_METAL, _rgb(eta), _rgb(k)
+    m.roughness, m.uroughness, m.vroughness, m.remap = float(roughness), float(uroughness), float(vroughness), int(bool(remap))
+    return m
+
+
 def scene_materials(meshes):
     """(materials, triangle_material) of `meshes` for BeamGather.set_materials: one table entry per
-    distinct Material object, in order of first use, and per triangle its index (-1: the mesh has no fifth
-    element, or None there)."""
+    distinct Material / MaterialEx object, in order of first use, and per triangle its index (-1: the mesh has
+    no fifth element, or None there).  With a MaterialEx among them the whole table is returned wide."""
+    table, tri = _scene_materials(meshes)
+    if any(isinstance(m, MaterialEx) for m in table):
+        table = [widen(m) for m in table]
+    return table, tri
+
+
+def _scene_materials(meshes):
     table, index, tri = [], {}, []
     for mesh in meshes:
         m = mesh[4] if len(mesh) > 4 else None

@@ -309,6 +309,18 @@ bre_status bre_set_lights(bre_ctx *ctx, const bre_light *lights, int32_t n);
 bre_status bre_set_materials(bre_ctx *ctx, const bre_material *materials, int32_t n_materials,
                              const int32_t *triangle_material, int64_t n_triangles);
 
+/* ---- the same table in its wide form (bre_material_ex, bre_scene.h): plastic, metal, rough matte ----
+   The semantics of bre_set_materials, over records that can also be BRE_MATERIAL_MATTE, _PLASTIC or _METAL.
+   Both setters write the context's one table (bre_set_materials widens its records): the last call wins.
+   Kd and Ks are clamped to [0, 1] like Kr and Kt.  A plastic with black Kd and Ks, or a matte with black Kd,
+   has no BxDF and absorbs.  A matte with sigma 0 is the Lambertian lobe of a triangle's own kd.
+   BRE_ERR_INVALID_ARG, beside the cases of bre_set_materials: an unknown type; a non-finite parameter of the
+   record's type; a plastic roughness, or a metal u / v roughness after the fallback to `roughness`, that is
+   not > 0 (a negative u / vroughness included); a metal ceta channel of 0; a remap other than 0 / 1; non-zero
+   reserved words.  Needs no device. */
+bre_status bre_set_materials_ex(bre_ctx *ctx, const bre_material_ex *materials, int32_t n_materials,
+                                const int32_t *triangle_material, int64_t n_triangles);
+
 /* ---- media bounded by surfaces (bre_medium, bre_scene.h; pbrt's MediumInterface) ----
    Copies the table media[0 .. n_media) with its density grids, the per-triangle pairs
    tri_inside / tri_outside[0 .. n_triangles) and light_medium[0 .. n_lights) into the context; n_media == 0
@@ -482,6 +494,14 @@ bre_status bre_resolve_image(int64_t npix, const float *ld_rgb, int iteration, f
              floats: wo in the shading frame (xyz), u[0], eta (0: a mirror), the transport mode (0:
              Importance, 1: Radiance); y receives 6 words per record: wi in the shading frame (xyz), pdf,
              the scalar f, and the sampled BxDFType as int32 (all zero where Sample_f returns 0).
+     kind 13: the passes' general BSDF (bsdf_sample, bsdf_f, bsdf_pdf, bre_trace.h: BSDF::Sample_f, f and Pdf
+             over the lobes of a plastic, metal or matte) in the frame ss = x, ts = y, n = ng = z.  aux holds
+             n_aux / 28 bre_material_ex records as words, checked as bre_set_materials_ex checks them (types
+             4 .. 6 only); x holds n / 9 records of 9 floats: wo (xyz), u[0], u[1], a second direction wi2
+             (xyz) and the index of the record's material in aux.  y receives 12 words per record: the
+             sampled wi (xyz), pdf, f (rgb) and the sampled BxDFType as int32 (all zero where Sample_f returns
+             0 or the material has no BxDF), then f(wo, wi2) (rgb) and Pdf(wo, wi2).  Partial records and an
+             index outside aux are refused with BRE_ERR_INVALID_ARG.
    so the tests can hold them against the reference's own primitive tests (src/tests/fp_tests.cpp,
    find_interval.cpp), against the compiler's correctly rounded sqrt and division, and (kinds 10, 11)
    against a host restatement and validator of the hierarchy (tests/refpy_lbvh.py). */

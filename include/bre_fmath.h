@@ -271,4 +271,48 @@ BRE_HD void bre_sincosf(float y, float *sinp, float *cosp) {
     *cosp = bre_sinf_poly(x * s, x * x, t, n ^ 1);
 }
 
+/* ---- double sin / cos on [0, 2 pi] with a derived error bound ----
+ * TrowbridgeReitzSample11's normal-incidence branch (microfacet.cpp:241-247) calls the double cos and sin of
+ * libm on phi = (float)(6.28318530718 * U2).  glibc's are accurate to under 1 ulp but not correctly rounded,
+ * so they are not restated; this pair instead has a relative error of at most E = 2^-50:
+ *   - n = round(phi * 2/pi) in 0..4, r = phi - n pi/2 by a three-part pi/2 (33 + 33 + 53 bits).  phi is a float:
+ *     for n >= 1 it is a multiple of 2^-24 below 8, n * P1 a multiple of 2^-32 below 8, so phi - n P1 is exact;
+ *     the two further subtractions round once each (relative 2^-53 of their results) and P1 + P2 + P3 misses
+ *     pi/2 by less than 2^-121.  No float lies within 2^-27 of a non-zero multiple of pi/2 up to 2 pi (the
+ *     nearest, float(2 pi), is 1.7e-7 away), so |r| >= 2^-27 or r = phi exactly, and r has a relative error
+ *     below 2^-52 + 4 * 2^-121 / 2^-27 < 2^-51.9;
+ *   - on |r| <= pi/4 the two kernels are the minimax polynomials of degree 13 / 14 of fdlibm's k_sin.c and
+ *     k_cos.c, whose stated approximation errors are 2^-58 (relative, sine) and 2^-58 (absolute, cosine);
+ *   - sine: r + r z (S1 + z (...)) has a correction below 0.11 |r| carrying a few rounding errors (< 2^-54 |r|)
+ *     and a final rounding of 2^-53; with the error of r (condition r cot r <= 1): below 2^-51.9 + 2^-53 +
+ *     2^-54 + 2^-58 < 2^-51;
+ *   - cosine: (1 - z/2) + z z (C1 + ...) has two roundings of at most 2^-54 absolute and a small term's; the
+ *     error of r adds |r tan r| 2^-51.9 <= 0.79 * 2^-51.9; over cos r >= 0.707: below 2^-50.
+ * tests/test_glossy_refpy.py holds both to the host libm within 2^-50 + 1 ulp on every float near a multiple
+ * of pi/2 and on a dense set. */
+BRE_HD void bre_sincos_2pi(double phi, double *sinp, double *cosp) {
+    const int n = (int)(phi * 0x1.45f306dc9c883p-1 + 0.5);
+    const double dn = (double)n;
+    double r = phi - dn * 0x1.921fb544p+0;     /* exact */
+    r = r - dn * 0x1.0b4611a6p-34;
+    r = r - dn * 0x1.3198a2e037073p-69;
+    const double z = r * r;
+    const double ps = 0x1.111111110f8a6p-7 +
+                      z * (-0x1.a01a019c161d5p-13 +
+                           z * (0x1.71de357b1fe7dp-19 + z * (-0x1.ae5e68a2b9cebp-26 + z * 0x1.5d93a5acfd57cp-33)));
+    const double s = r + (z * r) * (-0x1.5555555555549p-3 + z * ps);
+    const double pc = z * (0x1.555555555554cp-5 +
+                           z * (-0x1.6c16c16c15177p-10 +
+                                z * (0x1.a01a019cb159p-16 +
+                                     z * (-0x1.27e4f809c52adp-22 +
+                                          z * (0x1.1ee9ebdb4b1c4p-29 + z * -0x1.8fae9be8838d4p-37)))));
+    const double c = (1.0 - 0.5 * z) + z * pc;
+    switch (n & 3) {
+    case 0: *sinp = s; *cosp = c; break;
+    case 1: *sinp = c; *cosp = -s; break;
+    case 2: *sinp = -s; *cosp = -c; break;
+    default: *sinp = -c; *cosp = s; break;
+    }
+}
+
 #endif /* BRE_FMATH_H */

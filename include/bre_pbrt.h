@@ -62,6 +62,13 @@ bre_status bre_pbrt_get_lights(const bre_pbrt *p, int32_t capacity, bre_light *o
 bre_status bre_pbrt_get_materials(const bre_pbrt *p, int32_t mat_capacity, bre_material *materials,
                                   int32_t *n_materials, int64_t tri_capacity, int32_t *triangle_material,
                                   int64_t *n_triangles);
+/* The same table in its wide form (bre_material_ex, for bre_set_materials_ex): Material "plastic" and "metal"
+   (direct or named; metal with explicit "rgb eta" and "rgb k") and Material "matte" with a "sigma" other than 0 are
+   entries of it too.  bre_pbrt_get_materials is unchanged for the scenes it can express and returns BRE_ERR_STATE
+   (with the counts written) for a scene that holds one of these. */
+bre_status bre_pbrt_get_materials_ex(const bre_pbrt *p, int32_t mat_capacity, bre_material_ex *materials,
+                                     int32_t *n_materials, int64_t tri_capacity, int32_t *triangle_material,
+                                     int64_t *n_triangles);
 /* The media of a scene parsed with BRE_PBRT_MEDIA, for bre_set_media: the table (grid_density points into the
    parsed scene and stays valid until bre_pbrt_free), per scene triangle its MediumInterface as indices into it
    (-1: vacuum), the camera's medium (the outside medium at WorldEnd) and each spot light's (the outside medium

@@ -36,6 +36,10 @@
  *                       the camera pass in Radiance (the eta^2 factor), with isect.Le added after a
  *                       specular bounce and no direct light on a specular vertex.  Without bre_set_media
  *                       the scene's one medium fills the glass too.
+ *   - plastic, metal and rough matte (bre_material_ex below; PlasticMaterial, MetalMaterial and MatteMaterial
+ *                       with "sigma"), set with bre_set_materials_ex as the same table in its wide form.  Both
+ *                       passes go through the general BSDF (BSDF::f, Pdf and Sample_f, reflection.cpp:670-785)
+ *                       over a Lambertian or Oren-Nayar lobe and a Trowbridge-Reitz microfacet lobe.
  *   - media bounded by surfaces (bre_medium below; pbrt's MediumInterface): a context holds a table of
  *                       media, a per-triangle (inside, outside) pair, the camera's medium and each delta
  *                       light's (bre_set_media, bre.h).  Every ray carries its medium; a triangle whose
@@ -147,6 +151,33 @@ typedef struct bre_material {
     float kt[3];  /* glass: "Kt", clamped to [0, 1]; ignored for a mirror */
     float eta;    /* glass: "eta" / "index", finite and > 0 (also checked for a mirror, which ignores it) */
 } bre_material;   /* 32 bytes, no padding */
+
+/* Glossy and rough materials: pbrt's PlasticMaterial (src/materials/plastic.cpp: a LambertianReflection plus a
+   Trowbridge-Reitz MicrofacetReflection under FresnelDielectric(1.5, 1)), MetalMaterial (src/materials/metal.cpp:
+   one anisotropic Trowbridge-Reitz MicrofacetReflection under FresnelConductor(1, eta, k)) and MatteMaterial with
+   "sigma" (src/materials/matte.cpp: OrenNayar, or the Lambertian lobe at sigma 0).  They do not fit a bre_material:
+   bre_material_ex is the wide record, a superset of it that holds pbrt's parameters (not derived values), set with
+   bre_set_materials_ex (bre.h).  Its first 32 bytes are a bre_material. */
+#define BRE_MATERIAL_MATTE 4   /* kd, sigma */
+#define BRE_MATERIAL_PLASTIC 5 /* kd, ks, roughness, remap */
+#define BRE_MATERIAL_METAL 6   /* ceta, ck, roughness / uroughness / vroughness, remap */
+
+typedef struct bre_material_ex {
+    int32_t type;     /* BRE_MATERIAL_MIRROR .. BRE_MATERIAL_METAL */
+    float kr[3];      /* as in bre_material */
+    float kt[3];
+    float eta;        /* mirror / glass: finite and > 0; ignored by the other types */
+    float kd[3];      /* matte, plastic: "Kd", clamped to [0, 1]; black = no diffuse lobe */
+    float ks[3];      /* plastic: "Ks", clamped to [0, 1]; black = no glossy lobe */
+    float ceta[3];    /* metal: "eta" (the conductor's index per channel), finite and != 0 */
+    float ck[3];      /* metal: "k" (its absorption per channel) */
+    float roughness;  /* plastic: "roughness" (> 0); metal: "roughness", used where u / vroughness is 0 */
+    float uroughness; /* metal: "uroughness" (>= 0; 0 = not given: `roughness`) */
+    float vroughness; /* metal: "vroughness" (likewise) */
+    float sigma;      /* matte: "sigma" in degrees (clamped to [0, 90]; 0 = Lambertian) */
+    int32_t remap;    /* plastic, metal: "remaproughness" (0 / 1): roughness -> alpha by RoughnessToAlpha */
+    int32_t reserved[3]; /* 0 */
+} bre_material_ex;    /* 112 bytes, no padding */
 
 /* Media bounded by surfaces: pbrt's MediumInterface.  Like the lights and materials they are not part of
    bre_scene: a context holds a table of media, each triangle's (inside, outside) pair, the camera's medium
