@@ -296,6 +296,14 @@ bre_status bre_set_option(bre_ctx *c, int option, int64_t value) {
             return fail(c, BRE_ERR_INVALID_ARG, "occupancy must be 1 or 4..8");
         c->occupancy = (int)value;
         return BRE_OK;
+    case 124:  // internal: register budget of the tile kernel's specialised instantiation (TileProd), 7 (default:
+               // 72 VGPRs and 5,120 B of LDS, seven waves on every SIMD, C2 +2.2%) or 6 waves
+               // per SIMD (A/B): k_gather_tile<false, 7 or 6, TileProd>.  Option 102 keeps its meaning (the generic
+               // instantiations' budget; the specialised one still needs it at its default 6), and
+               // bre_stats::tile_variant is 2 at either budget.  Bound per launch, like option 123.
+        if (value != 6 && value != 7) return fail(c, BRE_ERR_INVALID_ARG, "specialised tile budget must be 6 or 7");
+        c->tile_budget = (int)value;
+        return BRE_OK;
     case 109:  // internal: tile kernel bytes of per-subtree partial sums per launch, in MiB (default 4 GiB; tests
                // force several launches)
         if (value < 1 || value > ((int64_t)1 << 20)) return fail(c, BRE_ERR_INVALID_ARG, "partial cap must be in 1..2^20 MiB");

@@ -166,6 +166,7 @@ bre_status gather_device(bre_ctx *c, int64_t nseg, const SegView &seg, float R, 
     a.margin = c->margin;
     a.stack_cap = c->stack_cap;
     a.tile_spec = c->tile_spec;
+    a.tile_budget = c->tile_budget;
     c->stats.tile_variant = 0;
     a.tile_variant = &c->stats.tile_variant;
     c->stats.n_segments = nseg;

@@ -18,6 +18,12 @@
 #ifndef BRE_KERNEL_READBACK
 #define BRE_KERNEL_READBACK 1
 #endif
+// default of internal option 124: the specialised tile kernel's register budget, 7 waves per SIMD (DESIGN.md
+// section 24; a build with 6 serves A/B runs through bench.py, which has no flag for the option)
+#ifndef BRE_TILE_BUDGET
+#define BRE_TILE_BUDGET 7
+#endif
+static_assert(BRE_TILE_BUDGET == 6 || BRE_TILE_BUDGET == 7, "BRE_TILE_BUDGET must be 6 or 7");
 
 namespace bre {
 
@@ -221,6 +227,7 @@ struct bre_ctx {
     int beam_key = 2, margin = 1, tile_axis = 1, split_records = 0, film_compose = 1;  // 110 .. 114
     int photon_single = 1, pass_priority = 1, kernel_readback = BRE_KERNEL_READBACK;   // 116 .. 118
     int slot_passes = 1, coarse_keys = 0, stage_all = 0, tile_spec = 1;                // 119, 121, 122, 123
+    int tile_budget = BRE_TILE_BUDGET;                                                 // 124
     // beam set
     int64_t nbeams = 0, nvalid = 0, nnodes = 0;
     bre::BeamSet bset;  // the built set's radius layout (BeamRec)

@@ -196,6 +196,7 @@ struct GatherArgs {
     int tscan;             // tile kernel: transposed scan when on-lanes * 8 < kept beams * tscan (0: off)
     int margin;            // tile kernel prefilter margins: 1 = the tight bound (default), 0 = round 2's
     int tile_spec = 1;     // tile kernel: 1 allows the specialised instantiation (internal option 123), 0 the generic one
+    int tile_budget = 7;   // tile kernel: the specialised instantiation's register budget, 7 (default) or 6 waves per SIMD (internal option 124)
     int64_t *tile_variant = nullptr;  // host, may be null: receives 1 (generic) or 2 (specialised) per launch
     TileAxis *tileax;      // tile kernel: per-tile axis bounds (ntiles), null = no tile axis reject
     unsigned int *segbox;  // tile kernel: 6 ordered uints of scratch (the launch's segment box)

@@ -87,16 +87,21 @@ __device__ __forceinline__ float sanitize_inv(float v) {
     return isinf(v) ? copysignf(FLT_MAX, v) : v;
 }
 
+// The lane of a packet's slot past the last segment
+__device__ __forceinline__ void zero_lane(Lane &L) {
+    L.o = L.p = L.au = L.d = L.inv = L.invs = mk(0.f, 0.f, 0.f);
+    L.tmax = 0.f;
+    L.mag_a = 0.f;
+    L.omax = 0.f;
+    L.n0 = L.n1 = L.n2 = 0;
+    L.has_inf = false;
+}
+
 __device__ __forceinline__ bool load_lane(int64_t s, int64_t nseg, const float *__restrict__ o,
                                           const float *__restrict__ p, const float *__restrict__ d,
                                           const float *__restrict__ tmax, Lane &L) {
     if (s >= nseg) {
-        L.o = L.p = L.au = L.d = L.inv = L.invs = mk(0.f, 0.f, 0.f);
-        L.tmax = 0.f;
-        L.mag_a = 0.f;
-        L.omax = 0.f;
-        L.n0 = L.n1 = L.n2 = 0;
-        L.has_inf = false;
+        zero_lane(L);
         return false;
     }
     L.o = mk(o[3 * s], o[3 * s + 1], o[3 * s + 2]);
