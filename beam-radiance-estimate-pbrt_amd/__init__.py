@@ -340,9 +340,9 @@ class BeamGather:
 
     # ---- lights ----
     def set_lights(self, lights=()):
-        """bre_set_lights: the point and spot lights (scene.Light: scene.point_light, scene.spot_light,
-        a parsed scene's .lights) every later pass and render of this context adds to its scene; an
-        empty list clears them."""
+        """bre_set_lights: the point, spot and distant lights (scene.Light: scene.point_light, scene.spot_light,
+        scene.distant_light, a parsed scene's .lights) every later pass and render of this context adds to its
+        scene; an empty list clears them."""
         from .scene import Light
 
         lights = list(lights)

@@ -158,11 +158,15 @@ bre_status bre_camera_pass(bre_ctx *c, const bre_scene *scene, int32_t width, in
     HIPCHK(c, fill_words(c, cam_flags, sizeof(unsigned int)));
     CamSlots cs{c->cs.out(), valid};
     if (c->timing) HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
+    // the kernels with the general BSDF are also the ones that shade under a distant light: the others, whose waves
+    // run inside another context's gather at 80 VGPRs, keep the code and the resources they had
+    bool wide = c->held.glossy;
+    for (const bre_light &l : c->held.lights) wide = wide || l.type == BRE_LIGHT_DISTANT;
     HIPCHK(c, launch_camera(c->dev.record.as<DevScene>(), c->dev.head.stack_depth, c->cam_dev.as<DevCamera>(),
                             c->cam_perms.as<uint16_t>(),
                             width, height, iteration, max_depth, render_surfaces, render_media, cs, d_surface,
                             cam_flags, c->shard_rank, c->shard_count,
-                            c->shard_mode != 0 ? 0 : c->shard_block, c->film_classes, planes, media, c->held.glossy, c->stream));
+                            c->shard_mode != 0 ? 0 : c->shard_block, c->film_classes, planes, media, wide, c->stream));
     // exclusive scan of the slots' valid flags into cam_offs: total = offs[S-1] + valid[S-1]
     HIPCHK(c, launch_camera_scan(c->cam_tmp.ptr, c->cam_tmp.cap, cs, nslots, planes, offs, c->stream,
                                  c->slot_passes != 0));

@@ -261,6 +261,14 @@ bre_status check_scene(bre_ctx *c, const bre_scene *scene, const char *fn) {
     if (!h.mats.empty() && h.tri_mat.size() != (size_t)scene->n_triangles)
         return fail(c, BRE_ERR_INVALID_ARG, "%s: the material map (bre_set_materials) covers %lld triangles, the scene "
                     "has %d", fn, (long long)h.tri_mat.size(), scene->n_triangles);
+    // A DistantLight has an empty MediumInterface (distant.cpp:45): its photons start in vacuum.  The one-medium
+    // model ("every ray travels in it") cannot say that; the media table can, with -1 for the light.
+    bool distant = false;
+    for (size_t k = 0; k < h.lights.size(); ++k) distant = distant || h.lights[k].type == BRE_LIGHT_DISTANT;
+    if (distant && h.media.empty() && scene->has_medium != BRE_MEDIUM_NONE)
+        return fail(c, BRE_ERR_INVALID_ARG, "%s: the context holds a distant light, whose photons start in vacuum: a "
+                    "scene with a medium of its own (has_medium) cannot hold it; bound the medium with surfaces "
+                    "(bre_set_media)", fn);
     if (h.media.empty()) {
         if (h.has_interface)
             return fail(c, BRE_ERR_INVALID_ARG, "%s: a BRE_MATERIAL_INTERFACE triangle needs the context's media "
@@ -277,6 +285,10 @@ bre_status check_scene(bre_ctx *c, const bre_scene *scene, const char *fn) {
     if (h.light_med.size() != h.lights.size())
         return fail(c, BRE_ERR_INVALID_ARG, "%s: the media (bre_set_media) name %lld delta lights, the context holds "
                     "%lld", fn, (long long)h.light_med.size(), (long long)h.lights.size());
+    for (size_t k = 0; k < h.lights.size(); ++k)
+        if (h.lights[k].type == BRE_LIGHT_DISTANT && h.light_med[k] != -1)
+            return fail(c, BRE_ERR_INVALID_ARG, "%s: distant light %d has medium %d (bre_set_media): a distant light "
+                        "is in vacuum, its medium must be -1", fn, (int)k, h.light_med[k]);
     return BRE_OK;
 }
 
@@ -352,7 +364,7 @@ bre_status bre_set_lights(bre_ctx *c, const bre_light *lights, int32_t n) {
     if (n > 0 && !lights) return fail(c, BRE_ERR_INVALID_ARG, "bre_set_lights: null lights");
     for (int k = 0; k < n; ++k) {
         const bre_light &l = lights[k];
-        if (l.type != BRE_LIGHT_POINT && l.type != BRE_LIGHT_SPOT)
+        if (l.type != BRE_LIGHT_POINT && l.type != BRE_LIGHT_SPOT && l.type != BRE_LIGHT_DISTANT)
             return fail(c, BRE_ERR_INVALID_ARG, "bre_set_lights: light %d has unknown type %d", k, l.type);
         if (l.order < 0) return fail(c, BRE_ERR_INVALID_ARG, "bre_set_lights: light %d has a negative order", k);
         bool finite = std::isfinite(l.cone_total_deg) && std::isfinite(l.cone_falloff_start_deg);
@@ -360,6 +372,18 @@ bre_status bre_set_lights(bre_ctx *c, const bre_light *lights, int32_t n) {
         for (int j = 0; j < 16; ++j)
             finite = finite && std::isfinite(l.light_to_world[j]) && std::isfinite(l.world_to_light[j]);
         if (!finite) return fail(c, BRE_ERR_INVALID_ARG, "bre_set_lights: light %d has a non-finite field", k);
+        if (l.type != BRE_LIGHT_DISTANT) continue;
+        // a DistantLight: wLight (light_to_world[0..2]) is a direction, L a radiance, the fields it does not read 0
+        if (l.light_to_world[0] == 0 && l.light_to_world[1] == 0 && l.light_to_world[2] == 0)
+            return fail(c, BRE_ERR_INVALID_ARG, "bre_set_lights: light %d (distant) has a zero wLight", k);
+        if (l.I[0] < 0 || l.I[1] < 0 || l.I[2] < 0)
+            return fail(c, BRE_ERR_INVALID_ARG, "bre_set_lights: light %d (distant) has a negative L", k);
+        bool zero = l.cone_total_deg == 0 && l.cone_falloff_start_deg == 0;
+        for (int j = 3; j < 16; ++j) zero = zero && l.light_to_world[j] == 0;
+        for (int j = 0; j < 16; ++j) zero = zero && l.world_to_light[j] == 0;
+        if (!zero)
+            return fail(c, BRE_ERR_INVALID_ARG, "bre_set_lights: light %d (distant) has a non-zero reserved field "
+                        "(light_to_world[3..15], world_to_light, the cone angles)", k);
     }
     c->held.lights.assign(lights, lights + n);
     return BRE_OK;

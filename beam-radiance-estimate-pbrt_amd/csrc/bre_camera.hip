@@ -307,7 +307,9 @@ __device__ __forceinline__ float power_heuristic(float fpdf, float gpdf) {
 // Sample_Li (point.cpp:44-53, spot.cpp:53-62) gives wi = Normalize(pLight - p), pdf 1 and
 // Li = I * Falloff(-wi) / DistanceSquared(pLight, p); its shadow ray is SpawnRayTo an Interaction with
 // zero normal and zero error (interaction.h:73-78), so OffsetRayOrigin leaves pLight + 0; it has no MIS
-// weight and no BSDF-sampling half (IsDeltaLight, integrator.cpp:155, 167).
+// weight and no BSDF-sampling half (IsDeltaLight, integrator.cpp:155, 167).  A DistantLight's Sample_Li gives its
+// wLight, L itself and a shadow ray to a point outside the world.  A two-sided area light's L() is Lemit seen from
+// either side, in Sample_Li's return and in the BSDF-sampling half.
 // MED (bre_set_media): the shaded vertex lies on triangle `tri`, reached by a ray in medium `med`; the shadow
 // ray is VisibilityTester::Tr as a loop (light.cpp:63-81) and the BSDF-sampled ray Scene::IntersectTr
 // (scene.cpp:62-75): both step through interface triangles and multiply each segment's Tr in order.
@@ -338,12 +340,16 @@ __device__ void estimate_direct(const DevScene &S, HaltonDev &hs, f3 p, f3 perr,
     float light_pdf;
     if (delta) {
         const DLight &D = S.dlights[~li];
-        ps.p = D.p;
         ps.perr = ps.n = mk(0, 0, 0);
         light_pdf = 1.f;
-        wi = normalize3(sub3(D.p, p));
+        // DistantLight::Sample_Li (distant.cpp:49-59): wi = wLight, Li = L, and the shadow ray ends outside the
+        // world, at pOutside = p + wLight * (2 * worldRadius).  Only the GL kernels know it: a context that holds a
+        // distant light takes them (bre_api_pass.hip), so that the others stay the code they were.
+        const bool distant = GL && D.kind == kLightDistant;
+        ps.p = distant ? add3(p, scale3(distant_w(D), 2 * distant_radius(D))) : D.p;
+        wi = distant ? distant_w(D) : normalize3(sub3(ps.p, p));
         const float fo = light_falloff(D, neg3(wi));
-        const float dist2 = lensq3(sub3(D.p, p));
+        const float dist2 = distant ? 1.f : lensq3(sub3(ps.p, p));
         for (int c = 0; c < 3; ++c) Li[c] = (D.I[c] * fo) / dist2;
     } else {
         // DiffuseAreaLight::Sample_Li (diffuse.cpp:68-81) -> Shape::Sample(ref, u) (shape.cpp:56-70)
@@ -361,7 +367,7 @@ __device__ void estimate_direct(const DevScene &S, HaltonDev &hs, f3 p, f3 perr,
             light_pdf = 0;
         } else {
             wi = normalize3(sub3(ps.p, p));
-            if (dot3(ps.n, neg3(wi)) > 0)
+            if (L.emit == BRE_EMIT_TWO_SIDED || dot3(ps.n, neg3(wi)) > 0)  // DiffuseAreaLight::L, diffuse.h:56-58
                 for (int c = 0; c < 3; ++c) Li[c] = L.Le[c];
         }
     }
@@ -463,8 +469,8 @@ __device__ void estimate_direct(const DevScene &S, HaltonDev &hs, f3 p, f3 perr,
                     for (int c = 0; c < 3; ++c) tr[c] = tr[c] * t2[c];
                 }
             }
-            // lightIsect.primitive->GetAreaLight() == &light: the same triangle, one-sided
-            if (found && h.tri == li && dot3(L.n, neg3(wi)) > 0 && !black3(L.Le))
+            // lightIsect.primitive->GetAreaLight() == &light: the same triangle, its L(-wi) one- or two-sided
+            if (found && h.tri == li && (L.emit == BRE_EMIT_TWO_SIDED || dot3(L.n, neg3(wi)) > 0) && !black3(L.Le))
                 for (int c = 0; c < 3; ++c) Ld[c] = Ld[c] + f[c] * L.Le[c] * tr[c] * wgt / scat_pdf;
         }
     }
@@ -473,8 +479,8 @@ __device__ void estimate_direct(const DevScene &S, HaltonDev &hs, f3 p, f3 perr,
 // MED: the context holds media: the ray carries its medium, an interface triangle is passed through with the
 // depth not counted (:515-517), and a segment's slot plane is its ordinal along the path (`planes` of them)
 // instead of its depth.  MED false is the one-medium walk, the code it was before media.
-// GL: the general BSDF for the table's plastic, metal and matte entries, at kGlossyWaves waves per SIMD; GL false
-// is the code it was before them, held to 80 VGPRs.
+// GL: the general BSDF for the table's plastic, metal and matte entries, and the distant lights' Sample_Li, at
+// kGlossyWaves waves per SIMD; GL false is the code it was before them, held to 80 VGPRs.
 template <bool MED, bool GL>
 __global__ __launch_bounds__(kCamBlock, GL ? kGlossyWaves : 6) void k_camera(const DevScene *__restrict__ Sp, const DevCamera *__restrict__ Cp,
                                                      const uint16_t *__restrict__ perms, int iteration, int max_depth,
@@ -571,9 +577,10 @@ __global__ __launch_bounds__(kCamBlock, GL ? kGlossyWaves : 6) void k_camera(con
         } else {
             if (!render_surfaces) break;
             const f3 wo = neg3(d);
-            // isect.Le(wo): the triangle's own area light, one-sided (diffuse.h:56-58), at the first vertex and
-            // after a mirror or glass bounce (:528-529)
-            if ((depth == 0 || specular_bounce) && q.emit && dot3(q.n, wo) > 0)
+            // isect.Le(wo): the triangle's own area light, one- or two-sided (diffuse.h:56-58), at the first vertex
+            // and after a mirror or glass bounce (:528-529)
+            // (emit is 0, BRE_EMIT_ONE_SIDED or BRE_EMIT_TWO_SIDED: seen from behind only the last one shines)
+            if ((depth == 0 || specular_bounce) && q.emit > (dot3(q.n, wo) > 0 ? 0 : BRE_EMIT_ONE_SIDED))
                 for (int c = 0; c < 3; ++c) Ld[c] = Ld[c] + beta[c] * q.Le[c];
             // UniformSampleOneLight (integrator.cpp:54-82): light uniformly, uLight, uScattering
             const int ln = min((int)(hs.get1d() * S.n_lights), S.n_lights - 1);

@@ -80,7 +80,7 @@ __global__ __launch_bounds__(kPhotonBlock, GL ? kGlossyWaves : 6) void k_photons
     int cnt = 0;
 
     // ---- emission, photonbeam.cpp:393-418: a light by power, then its Sample_Le (DiffuseAreaLight on a
-    // triangle, PointLight or SpotLight); the five draws are the same whatever the light ----
+    // triangle, PointLight, SpotLight or DistantLight); the five draws are the same whatever the light ----
     float light_pdf;
     const int ln = sample_light(S, pcg_float(rng), light_pdf);  // lightSample
     float u0x, u0y, u1x, u1y;
@@ -96,15 +96,25 @@ __global__ __launch_bounds__(kPhotonBlock, GL ? kGlossyWaves : 6) void k_photons
         const PTri &L = S.t[lt];
         const ShapeSample ps = sample_tri(L, u0x, u0y);
         const float pdf_pos = ps.pdf;
-        const f3 wl = cosine_hemisphere(u1x, u1y);
-        const float pdf_dir = wl.z * kInvPi;
+        f3 wl;
+        float pdf_dir;
+        if (L.emit == BRE_EMIT_TWO_SIDED) {
+            // diffuse.cpp:100-112: u[0] < .5 picks the side and is remapped to [0, 1); the far side's w.z is negated
+            const bool near = u1x < .5f;
+            wl = cosine_hemisphere(smin(near ? u1x * 2 : (u1x - .5f) * 2, kOneMinusEps), u1y);
+            if (!near) wl.z *= -1;
+            pdf_dir = 0.5f * (fabsf(wl.z) * kInvPi);
+        } else {
+            wl = cosine_hemisphere(u1x, u1y);
+            pdf_dir = wl.z * kInvPi;
+        }
         f3 v1, v2;
         coord_system(ps.n, v1, v2);
         d = add3(add3(scale3(v1, wl.x), scale3(v2, wl.y)), scale3(ps.n, wl.z));
         o = offset_origin(ps.p, ps.perr, ps.n, d);
         // DiffuseAreaLight::Sample_Le: pShape.mediumInterface = mediumInterface, the ray is pShape.SpawnRay(w)
         if constexpr (MED) med = dot3(d, ps.n) > 0 ? S.tri_med[2 * lt + 1] : S.tri_med[2 * lt];
-        const bool front = dot3(ps.n, d) > 0;  // DiffuseAreaLight::L, one-sided
+        const bool front = L.emit == BRE_EMIT_TWO_SIDED || dot3(ps.n, d) > 0;  // DiffuseAreaLight::L (diffuse.h:56-58)
         alive = !(pdf_pos == 0 || pdf_dir == 0 || !front || black3(L.Le));
         if (alive) {
             const float ad = fabsf(dot3(ps.n, d));
@@ -114,18 +124,20 @@ __global__ __launch_bounds__(kPhotonBlock, GL ? kGlossyWaves : 6) void k_photons
         }
     } else {
         // PointLight / SpotLight::Sample_Le: the ray leaves pLight itself, nLight = d, pdfPos = 1; a
-        // direction the two matrices push outside the cone has Falloff 0 and the photon ends (:412)
+        // direction the two matrices push outside the cone has Falloff 0 and the photon ends (:412).
+        // DistantLight::Sample_Le: from the disk outside the world, pdfPos = 1 / (Pi r^2); its medium is -1
+        // (an empty MediumInterface, checked by the host), so the leg down to the first surface is in vacuum
+        // and still leaves a beam
         const DLight &D = S.dlights[~lt];
-        float pdf_dir, fo;
-        light_sample_le(D, u0x, u0y, d, pdf_dir, fo);
-        o = D.p;
+        float pdf_pos, pdf_dir, fo;
+        light_sample_le(D, u0x, u0y, o, d, pdf_pos, pdf_dir, fo);
         if constexpr (MED) med = S.light_med[~lt];  // Ray(pLight, w, Infinity, time, mediumInterface.inside)
         float Le[3];
         for (int c = 0; c < 3; ++c) Le[c] = D.I[c] * fo;
-        alive = !(pdf_dir == 0 || black3(Le));
+        alive = !(pdf_pos == 0 || pdf_dir == 0 || black3(Le));
         if (alive) {
             const float ad = fabsf(dot3(d, d));
-            const float den = light_pdf * 1.f * pdf_dir;
+            const float den = light_pdf * pdf_pos * pdf_dir;
             for (int c = 0; c < 3; ++c) beta[c] = (ad * Le[c]) / den;
             alive = !black3(beta);
         }

@@ -41,10 +41,19 @@ void prepare_medium(const bre_scene *s, DevScene *d, const float *d_density) {
                          type == BRE_MEDIUM_GRID ? grid_max_density(s) : 0.f);
 }
 
-// PointLight / SpotLight constructors (point.h, spot.cpp:44-51) and Light's (light.cpp:46-55)
+// PointLight / SpotLight constructors (point.h, spot.cpp:44-51) and Light's (light.cpp:46-55); a DistantLight's
+// record already holds what its constructor leaves (distant.cpp:43-47), its centre and radius come with the BVH
 DLight prepare_light(const bre_light &l) {
     DLight D{};
     const float *m = l.light_to_world;
+    if (l.type == BRE_LIGHT_DISTANT) {
+        D.kind = kLightDistant;
+        for (int k = 0; k < 3; ++k) {
+            D.l2w[k] = m[k];
+            D.I[k] = l.I[k];
+        }
+        return D;
+    }
     // pLight = LightToWorld(Point3f(0, 0, 0)), Transform::operator()(Point3f) (transform.h:223-233)
     const float x = 0.f, y = 0.f, z = 0.f;
     const float xp = m[0] * x + m[1] * y + m[2] * z + m[3];
@@ -58,8 +67,8 @@ DLight prepare_light(const bre_light &l) {
             D.w2l[3 * r + c] = l.world_to_light[4 * r + c];
         }
     for (int k = 0; k < 3; ++k) D.I[k] = l.I[k];
-    D.spot = l.type == BRE_LIGHT_SPOT;
-    if (D.spot) {  // std::cos(Radians(.)), pbrt.h:295
+    D.kind = l.type == BRE_LIGHT_SPOT ? kLightSpot : kLightPoint;
+    if (D.kind == kLightSpot) {  // std::cos(Radians(.)), pbrt.h:295
         D.cos_total = bre_cosf((kPi / 180) * l.cone_total_deg);
         D.cos_start = bre_cosf((kPi / 180) * l.cone_falloff_start_deg);
     }
@@ -67,12 +76,24 @@ DLight prepare_light(const bre_light &l) {
 }
 
 // Power().y(): 4 * Pi * I (point.cpp:55); I * 2 * Pi * (1 - .5f * (cosFalloffStart + cosTotalWidth))
-// (spot.cpp:75-77)
+// (spot.cpp:75-77); L * Pi * worldRadius * worldRadius (distant.cpp:61-63)
 static float light_power_y(const DLight &D) {
     float pw[3];
-    for (int k = 0; k < 3; ++k)
-        pw[k] = D.spot ? D.I[k] * 2 * kPi * (1 - .5f * (D.cos_start + D.cos_total)) : D.I[k] * (4 * kPi);
+    for (int k = 0; k < 3; ++k) {
+        if (D.kind == kLightDistant) pw[k] = D.I[k] * kPi * distant_radius(D) * distant_radius(D);
+        else pw[k] = D.kind == kLightSpot ? D.I[k] * 2 * kPi * (1 - .5f * (D.cos_start + D.cos_total)) : D.I[k] * (4 * kPi);
+    }
     return lum3(pw);
+}
+
+// Bounds3::BoundingSphere (geometry.h) of Scene::WorldBound(), the root box of the scene's BVHAccel (the union of
+// the Triangle::WorldBound()s, whatever their order), as DistantLight::Preprocess takes it (distant.h)
+static void world_bounding_sphere(const SceneNode &root, f3 *center, float *radius) {
+    const f3 lo = mk(root.lo[0], root.lo[1], root.lo[2]), hi = mk(root.hi[0], root.hi[1], root.hi[2]);
+    *center = div3(add3(lo, hi), 2.f);  // (pMin + pMax) / 2
+    const f3 c = *center;
+    const bool inside = c.x >= lo.x && c.x <= hi.x && c.y >= lo.y && c.y <= hi.y && c.z >= lo.z && c.z <= hi.z;
+    *radius = inside ? len3(sub3(c, hi)) : 0.f;  // Inside(*center, *this) ? Distance(*center, pMax) : 0
 }
 
 // PlasticMaterial / MetalMaterial / MatteMaterial::ComputeScatteringFunctions (plastic.cpp:45-70, metal.cpp:59-80,
@@ -202,19 +223,31 @@ void prepare_geometry(const bre_scene *s, HostScene *out, const bre_light *light
                 }
             }
         }
-        T.emit = t.emit != 0;
+        T.emit = t.emit == BRE_EMIT_TWO_SIDED ? BRE_EMIT_TWO_SIDED : t.emit != 0;
         if (T.emit) {
             delta_up_to(i);
             out->light_tri.push_back(i);
             // DiffuseAreaLight::Power() = (twoSided ? 2 : 1) * Lemit * area * Pi (diffuse.cpp:64-66), .y()
+            const float sides = T.emit == BRE_EMIT_TWO_SIDED ? 2.f : 1.f;
             float pw[3];
-            for (int k = 0; k < 3; ++k) pw[k] = ((T.Le[k] * 1.f) * T.area) * kPi;
+            for (int k = 0; k < 3; ++k) pw[k] = ((T.Le[k] * sides) * T.area) * kPi;
             out->light_func.push_back(lum3(pw));
         }
     }
     delta_up_to(s->n_triangles);
+    out->depth = build_scene_bvh(out->tris, &out->nodes, &out->prims);
+    d.n_nodes = (int)out->nodes.size();
+    d.stack_depth = out->depth;
     const int nl = (int)out->light_tri.size();
     d.n_lights = nl;
+    // DistantLight::Preprocess(scene): the world's bounding sphere, and with it the light's Power()
+    for (int i = 0; i < nl; ++i) {
+        if (out->light_tri[(size_t)i] >= 0) continue;
+        DLight &D = out->dlights[(size_t)~out->light_tri[(size_t)i]];
+        if (D.kind != kLightDistant) continue;
+        world_bounding_sphere(out->nodes[0], &D.p, &D.l2w[3]);
+        out->light_func[(size_t)i] = light_power_y(D);
+    }
     // Distribution1D(func, n) (sampling.h:57-69)
     std::vector<float> &cdf = out->light_cdf;
     const std::vector<float> &func = out->light_func;
@@ -226,9 +259,6 @@ void prepare_geometry(const bre_scene *s, HostScene *out, const bre_light *light
     } else {
         for (int i = 1; i < nl + 1; ++i) cdf[(size_t)i] /= d.light_func_int;
     }
-    out->depth = build_scene_bvh(out->tris, &out->nodes, &out->prims);
-    d.n_nodes = (int)out->nodes.size();
-    d.stack_depth = out->depth;
 }
 
 }  // namespace bre

@@ -103,9 +103,11 @@ BRE_TD f3 offset_origin(f3 p, f3 perr, f3 n, f3 w) {
 }
 
 // ---- sampling (sampling.cpp:113-133, sampling.h:159-165) ----
-BRE_TD f3 cosine_hemisphere(float ux, float uy) {
+// ConcentricSampleDisk, sampling.cpp:113-133
+BRE_TD void concentric_disk(float ux, float uy, float &dx, float &dy) {
     const float ox = 2.f * ux - 1, oy = 2.f * uy - 1;
-    float dx = 0, dy = 0;
+    dx = 0;
+    dy = 0;
     if (!(ox == 0 && oy == 0)) {
         float theta, r;
         if (fabsf(ox) > fabsf(oy)) {
@@ -120,6 +122,11 @@ BRE_TD f3 cosine_hemisphere(float ux, float uy) {
         dx = c * r;
         dy = s * r;
     }
+}
+// CosineSampleHemisphere, sampling.h:159-165
+BRE_TD f3 cosine_hemisphere(float ux, float uy) {
+    float dx, dy;
+    concentric_disk(ux, uy, dx, dy);
     return mk(dx, dy, sqrtf(smax(0.f, 1 - dx * dx - dy * dy)));
 }
 
@@ -196,13 +203,17 @@ constexpr int kSceneStack = 64;  // BVHAccel::Intersect's nodesToVisit[64]: the 
 // A delta light (bre_light: PointLight, src/lights/point.cpp; SpotLight, src/lights/spot.cpp) as its
 // constructor leaves it: pLight = LightToWorld(Point3f(0, 0, 0)), the 3x3 blocks of LightToWorld and
 // WorldToLight (vectors only ever go through them), I, and the two cosines (host, bre_fmath.h).
+// A DistantLight (src/lights/distant.cpp) is the same record read differently, after its constructor and its
+// Preprocess: p = worldCenter, l2w[0..2] = wLight, l2w[3] = worldRadius (Scene::WorldBound().BoundingSphere),
+// I = L; it has no matrices and no cone.
 static_assert(sizeof(bre_light) == 156, "bre_light has no padding: the geometry cache compares its bytes");
+constexpr int kLightPoint = 0, kLightSpot = 1, kLightDistant = 2;
 struct DLight {
     f3 p;
     float l2w[9], w2l[9];  // row-major
     float I[3];
     float cos_total, cos_start;  // cosTotalWidth, cosFalloffStart
-    int spot;                    // 1: SpotLight, 0: PointLight
+    int kind;                    // kLightPoint / kLightSpot / kLightDistant
 };
 
 // A medium as the HomogeneousMedium / GridDensityMedium constructors leave it (make_medium): the scene's own
@@ -459,7 +470,7 @@ BRE_TD f3 xform_vec3(const float *m, f3 v) {
 }
 // SpotLight::Falloff, spot.cpp:64-73 (a PointLight has none: 1)
 BRE_TD float light_falloff(const DLight &D, f3 w) {
-    if (!D.spot) return 1.f;
+    if (D.kind != kLightSpot) return 1.f;
     const float cos_t = normalize3(xform_vec3(D.w2l, w)).z;
     if (cos_t < D.cos_total) return 0.f;
     if (cos_t > D.cos_start) return 1.f;
@@ -469,9 +480,31 @@ BRE_TD float light_falloff(const DLight &D, f3 w) {
 // Sample_Le of a delta light from uLight0 (point.cpp:61-71: UniformSampleSphere, sampling.cpp:98-103;
 // spot.cpp:83-93: UniformSampleCone and UniformConePdf, sampling.cpp:132-142).  The ray starts at
 // D.p; d is not normalised (a spot's goes through LightToWorld); nLight = d, pdfPos = 1.
-BRE_TD void light_sample_le(const DLight &D, float u0, float u1, f3 &d, float &pdf_dir, float &fo) {
+// A DistantLight's (distant.cpp:69-85) starts on the disk of the world's bounding sphere that faces wLight, pushed
+// out by worldRadius along wLight, without an offset (no SpawnRay): d = -wLight, pdfPos = 1 / (Pi r^2), pdfDir = 1.
+BRE_TD f3 distant_w(const DLight &D) { return mk(D.l2w[0], D.l2w[1], D.l2w[2]); }
+BRE_TD float distant_radius(const DLight &D) { return D.l2w[3]; }
+BRE_TD void light_sample_le(const DLight &D, float u0, float u1, f3 &o, f3 &d, float &pdf_pos, float &pdf_dir,
+                            float &fo) {
     float s, c;
-    if (D.spot) {
+    o = D.p;
+    pdf_pos = 1.f;
+    if (D.kind == kLightDistant) {
+        const f3 wl = distant_w(D);
+        const float r = distant_radius(D);
+        f3 v1, v2;
+        coord_system(wl, v1, v2);
+        float cx, cy;
+        concentric_disk(u0, u1, cx, cy);
+        const f3 p_disk = add3(D.p, scale3(add3(scale3(v1, cx), scale3(v2, cy)), r));
+        o = add3(p_disk, scale3(wl, r));
+        d = neg3(wl);
+        pdf_pos = 1 / (kPi * r * r);
+        pdf_dir = 1.f;
+        fo = 1.f;
+        return;
+    }
+    if (D.kind == kLightSpot) {
         const float cos_t = (1.f - u0) + u0 * D.cos_total;
         const float sin_t = sqrtf(1.f - cos_t * cos_t);
         const float phi = u1 * 2 * kPi;

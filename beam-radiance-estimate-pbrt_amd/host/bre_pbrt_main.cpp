@@ -1,7 +1,8 @@
 // bre_pbrt_main.cpp — `bre_pbrt scene.pbrt`: the pbrt command line for scenes whose Integrator
 // is "photonbeam" (src/main/pbrt.cpp: parse, WorldEnd -> Render, film written by the integrator),
 // with the render on an MI355X.  Options: --quick, --outfile FILE, --media (media bounded by surfaces:
-// MediumInterface on shapes and lights, Material "none" boundaries), --device N, --devices A,B,... (the
+// MediumInterface on shapes and lights, Material "none" boundaries), --lights (LightSource "distant" and
+// "point", two-sided area lights), --device N, --devices A,B,... (the
 // render split over several GPUs, one context per entry; a repeated ordinal is allowed); pbrt's
 // --nthreads is accepted and ignored.  Without --devices, a BRE_DEVICES environment value naming more
 // than one device selects them.  Exit status 0 on success.
@@ -15,7 +16,7 @@
 #include "../../include/bre_pbrt.h"
 
 static const char *kUsage =
-    "usage: bre_pbrt [--quick] [--media] [--outfile file.pfm] [--device n | --devices a,b,...] scene.pbrt\n";
+    "usage: bre_pbrt [--quick] [--media] [--lights] [--outfile file.pfm] [--device n | --devices a,b,...] scene.pbrt\n";
 
 // "0,1,2,3" -> ordinals; empty when the text is not a comma-separated list of non-negative integers
 static std::vector<int32_t> ParseDevices(const char *text) {
@@ -37,6 +38,7 @@ int main(int argc, char **argv) {
     for (int i = 1; i < argc; ++i) {
         if (!strcmp(argv[i], "--quick")) quick = 1;
         else if (!strcmp(argv[i], "--media")) flags |= BRE_PBRT_MEDIA;
+        else if (!strcmp(argv[i], "--lights")) flags |= BRE_PBRT_LIGHTS;
         else if (!strcmp(argv[i], "--outfile") && i + 1 < argc) outfile = argv[++i];
         else if (!strcmp(argv[i], "--device") && i + 1 < argc) device = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--devices") && i + 1 < argc) {

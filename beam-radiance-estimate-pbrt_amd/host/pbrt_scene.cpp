@@ -496,6 +496,7 @@ struct GraphicsState {
     std::string namedMaterial;
     std::string inside, outside;
     bool areaLight = false;
+    bool areaTwoSided = false;  // "bool twosided" (kParseLights)
     float areaL[3] = {1, 1, 1};
     bool reverseOrientation = false;
 };
@@ -516,7 +517,8 @@ struct ShapeRec {
 
 class Parser {
   public:
-    Parser(PbrtScene *out, int flags) : out_(out), mediaOk_((flags & kParseMedia) != 0) {}
+    Parser(PbrtScene *out, int flags)
+        : out_(out), mediaOk_((flags & kParseMedia) != 0), lightsOk_((flags & kParseLights) != 0) {}
 
     bool Run(Lexer &lx, int depth);
     bool Finish();
@@ -543,6 +545,7 @@ class Parser {
 
     PbrtScene *out_;
     bool mediaOk_;  // kParseMedia
+    bool lightsOk_;  // kParseLights: LightSource "distant" and "point", two-sided area lights
     Xform ctm_ = Xform::Identity();
     int ctmKind_ = 0;  // 0 identity, 1 exactly one LookAt, 2 anything else
     float lookAt_[9] = {0, 0, 0, 0, 0, 1, 0, 1, 0};
@@ -1025,8 +1028,8 @@ void Parser::Shape(Lexer &lx, int line, const std::string &name, const ParamSet 
         memcpy(sr.tri.kd, mat.kd, sizeof(sr.tri.kd));
         sr.tri.flip = flip ? 1 : 0;
         if (gs_.areaLight) {
-            // pbrtShape: one DiffuseAreaLight per shape of the mesh (api.cpp), one-sided
-            sr.tri.emit = 1;
+            // pbrtShape: one DiffuseAreaLight per shape of the mesh (api.cpp), one- or two-sided
+            sr.tri.emit = gs_.areaTwoSided ? BRE_EMIT_TWO_SIDED : BRE_EMIT_ONE_SIDED;
             memcpy(sr.tri.Le, gs_.areaL, sizeof(sr.tri.Le));
         }
         sr.inside = gs_.inside;
@@ -1269,6 +1272,49 @@ bool Parser::Run(Lexer &lx, int depth) {
                     lightOutside_.push_back(gs_.outside);
                 }
                 ReportUnused(lx, line, ps);
+            } else if (w == "LightSource" && lightsOk_ && (n == "distant" || n == "point")) {
+                bre_light L;
+                memset(&L, 0, sizeof(L));
+                float I[3] = {1, 1, 1}, sc[3] = {1, 1, 1}, from[3] = {0, 0, 0}, to[3] = {0, 0, 1};
+                ps.FindOneSpectrum(n == "distant" ? "L" : "I", I);
+                ps.FindOneSpectrum("scale", sc);
+                ps.FindOnePoint3f("from", from);
+                for (int k = 0; k < 3; ++k) L.I[k] = I[k] * sc[k];
+                L.order = (int)shapes_.size();
+                std::string medium = gs_.outside;
+                if (n == "distant") {
+                    // CreateDistantLight (distant.cpp:94-102): dir = from - to; the constructor leaves
+                    // wLight = Normalize(LightToWorld(dir)) (:47) and an empty MediumInterface (:45): whatever the
+                    // graphics state says, the light's photons start in vacuum
+                    ps.FindOnePoint3f("to", to);
+                    const float dir[3] = {from[0] - to[0], from[1] - to[1], from[2] - to[2]};
+                    float w3[3];
+                    for (int i = 0; i < 3; ++i)  // Transform::operator()(Vector3f), transform.h:236-242
+                        w3[i] = ctm_.m[i][0] * dir[0] + ctm_.m[i][1] * dir[1] + ctm_.m[i][2] * dir[2];
+                    Normalize3(w3, L.light_to_world);
+                    L.type = BRE_LIGHT_DISTANT;
+                    medium.clear();
+                    if (!(std::isfinite(L.light_to_world[0]) && std::isfinite(L.light_to_world[1]) &&
+                          std::isfinite(L.light_to_world[2])))
+                        Error(lx, line, "LightSource \"distant\" has no direction (\"from\" equals \"to\", or the "
+                                        "transform flattens it)");
+                } else {
+                    // CreatePointLight (point.cpp:80-88): Translate(from) * CTM, in the outside medium (MakeLight)
+                    const Xform l2w = Xform::Translate(from[0], from[1], from[2]) * ctm_;
+                    for (int i = 0; i < 4; ++i)
+                        for (int j = 0; j < 4; ++j) {
+                            L.light_to_world[4 * i + j] = l2w.m[i][j];
+                            L.world_to_light[4 * i + j] = l2w.mInv[i][j];
+                        }
+                    L.type = BRE_LIGHT_POINT;
+                }
+                if ((int)out_->lights.size() >= BRE_MAX_LIGHTS) {
+                    Error(lx, line, "more than BRE_MAX_LIGHTS (%d) light sources", BRE_MAX_LIGHTS);
+                } else {
+                    out_->lights.push_back(L);
+                    lightOutside_.push_back(medium);
+                }
+                ReportUnused(lx, line, ps);
             } else if (w == "LightSource") {
                 Error(lx, line, "LightSource \"%s\" is not supported (diffuse area lights only)", n.c_str());
             } else if (w == "AreaLightSource") {
@@ -1280,8 +1326,11 @@ bool Parser::Run(Lexer &lx, int depth) {
                     ps.FindOneSpectrum("L", L);
                     ps.FindOneSpectrum("scale", sc);
                     ps.FindOneInt("samples", ps.FindOneInt("nsamples", 1));
-                    if (ps.FindOneBool("twosided", false))
+                    gs_.areaTwoSided = ps.FindOneBool("twosided", false);
+                    if (gs_.areaTwoSided && !lightsOk_) {
                         Error(lx, line, "two-sided area lights are not supported");
+                        gs_.areaTwoSided = false;
+                    }
                     for (int k = 0; k < 3; ++k) gs_.areaL[k] = L[k] * sc[k];
                     gs_.areaLight = true;
                     ReportUnused(lx, line, ps);
@@ -1338,6 +1387,13 @@ bool Parser::Finish() {
             return fatal("shape " + std::to_string(i) + " has MediumInterface \"" + s.inside + "\" \"" + s.outside +
                          "\"; the GPU scene model has one medium (\"" + M + "\") filling all space");
     }
+    // A distant light's photons start in vacuum (an empty MediumInterface): a medium that fills all space, the
+    // camera's, cannot hold it.  With kParseMedia the medium is bounded by surfaces and the light's entry is -1.
+    for (size_t i = 0; !mediaOk_ && !M.empty() && i < o.lights.size(); ++i)
+        if (o.lights[i].type == BRE_LIGHT_DISTANT)
+            return fatal("light " + std::to_string(i) + " is a distant light, whose photons start in vacuum; the GPU "
+                         "scene model's one medium (\"" + M + "\") fills all space: bound it with surfaces and parse "
+                         "with BRE_PBRT_MEDIA (bre_pbrt --media)");
     for (size_t i = 0; !mediaOk_ && i < lightOutside_.size(); ++i)
         if (lightOutside_[i] != M)
             return fatal("light " + std::to_string(i) + " is declared in medium \"" + lightOutside_[i] +

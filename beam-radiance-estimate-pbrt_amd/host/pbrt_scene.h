@@ -28,15 +28,16 @@
 //     bre_material_ex in PbrtScene::materials, referred to by the triangles declared under it
 //     (PbrtScene::triangleMaterial).  "bumpmap" and texture-valued parameters are reported and the statement
 //     falls back to matte.  The direct statement Material "glass" is reported as unsupported.
-//   * AreaLightSource "diffuse" ("L" x "scale", one-sided): every triangle of an emitting mesh is
-//     its own light, as pbrtShape makes one DiffuseAreaLight per shape (api.cpp).
+//   * AreaLightSource "diffuse" ("L" x "scale"; one-sided, with kParseLights also "bool twosided"): every
+//     triangle of an emitting mesh is its own light, as pbrtShape makes one DiffuseAreaLight per shape (api.cpp).
 //   * media: "homogeneous" or "heterogeneous" (GridDensityMedium).  By default the scene has ONE medium
 //     filling all space, so every shape's inside/outside medium and the camera medium must be
 //     that medium (or all empty = vacuum); with kParseMedia every named medium in use becomes a table
 //     entry and every shape and light keeps its MediumInterface (PbrtScene::media).
 //   * LightSource "spot" ("I" x "scale", "from", "to", "coneangle", "conedeltaangle"): a bre_light with
 //     CreateSpotLight's transform, in PbrtScene::lights; its outside medium must be the scene's medium.
-//     Every other LightSource is reported as unsupported.
+//     Every other LightSource is reported as unsupported, unless kParseLights is given: then "point" ("I" x
+//     "scale", "from") and "distant" ("L" x "scale", "from", "to"; always in vacuum) are bre_lights too.
 //   * Camera "perspective" ("fov", lensradius 0) whose CTM is Identity followed by one LookAt.
 //   * Film "image" (xresolution, yresolution, filename, scale); Integrator "photonbeam".
 //   * Sampler / PixelFilter / Accelerator are accepted and ignored: the photon-beam integrator
@@ -120,6 +121,10 @@ struct FilmDesc {
 // use (equal media share an entry), per scene triangle its MediumInterface as indices into it (-1: vacuum),
 // the camera's medium and each spot light's.  All empty / -1 otherwise.
 constexpr int kParseMedia = 1;  // BRE_PBRT_MEDIA (include/bre_pbrt.h)
+// LightSource "distant" (CreateDistantLight, distant.cpp:94-102) and "point" (CreatePointLight, point.cpp:80-88)
+// become bre_lights and "bool twosided" "true" on an AreaLightSource "diffuse" gives BRE_EMIT_TWO_SIDED triangles,
+// instead of the three refusals of the default parse
+constexpr int kParseLights = 2;  // BRE_PBRT_LIGHTS
 struct SceneMedia {
     std::vector<bre_medium> media;             // grid_density points into `density`
     std::vector<std::vector<float>> density;   // per table entry: a heterogeneous medium's data

@@ -23,6 +23,7 @@ HOST_LIB_PATH = os.path.join(HERE, "libbre_host.so")
 CLI_PATH = os.path.join(HERE, "host", "bre_pbrt")
 
 PBRT_MEDIA = 1  # BRE_PBRT_MEDIA
+PBRT_LIGHTS = 2  # BRE_PBRT_LIGHTS: LightSource "distant" and "point", two-sided area lights
 EXPORTS = ["bre_pbrt_parse_file", "bre_pbrt_parse_string", "bre_pbrt_parse_file_ex", "bre_pbrt_parse_string_ex",
            "bre_pbrt_get_media", "bre_pbrt_free", "bre_pbrt_messages",
            "bre_pbrt_get_scene", "bre_pbrt_get_lights", "bre_pbrt_get_materials", "bre_pbrt_get_materials_ex", "bre_pbrt_make_spot_light", "bre_pbrt_get_render_params", "bre_pbrt_get_film", "bre_pbrt_render",
@@ -93,7 +94,8 @@ class PbrtScene:
         assert self._lib.bre_pbrt_get_lights(self._h, 0, None, ctypes.byref(n)) == 0
         arr = (Light * max(n.value, 1))()
         assert self._lib.bre_pbrt_get_lights(self._h, n.value, arr, ctypes.byref(n)) == 0
-        self.lights = [arr[i] for i in range(n.value)]  # LightSource "spot", for BeamGather.set_lights
+        # LightSource "spot" (with lights=True also "point" and "distant"), for BeamGather.set_lights
+        self.lights = [arr[i] for i in range(n.value)]
         self._lights_ref = arr
         # mirror / glass materials and the per-triangle index into them, for BeamGather.set_materials
         nm, nt = ctypes.c_int32(), ctypes.c_int64()
@@ -167,24 +169,27 @@ class PbrtScene:
             pass
 
 
-def _parse(fn, arg: bytes, quick: bool, media: bool) -> PbrtScene:
+def _parse(fn, arg: bytes, quick: bool, media: bool, lights: bool = False) -> PbrtScene:
     lib = load_host_library()
     h = ctypes.c_void_p()
-    if media:
-        st = getattr(lib, fn + "_ex")(arg, PBRT_MEDIA, ctypes.byref(h))
+    if media or lights:
+        flags = (PBRT_MEDIA if media else 0) | (PBRT_LIGHTS if lights else 0)
+        st = getattr(lib, fn + "_ex")(arg, flags, ctypes.byref(h))
     else:
         st = getattr(lib, fn)(arg, ctypes.byref(h))
     return PbrtScene(h, st == 0, quick)
 
 
-def parse_file(path: str, quick: bool = False, media: bool = False) -> PbrtScene:
+def parse_file(path: str, quick: bool = False, media: bool = False, lights: bool = False) -> PbrtScene:
     """`media`: BRE_PBRT_MEDIA -- media bounded by surfaces are accepted (.media, .tri_inside, .tri_outside,
-    .camera_medium, .light_medium on the result) instead of refused."""
-    return _parse("bre_pbrt_parse_file", os.fsencode(path), quick, media)
+    .camera_medium, .light_medium on the result) instead of refused.
+    `lights`: BRE_PBRT_LIGHTS -- LightSource "distant" and "point" and "bool twosided" "true" on an
+    AreaLightSource "diffuse" are accepted instead of refused."""
+    return _parse("bre_pbrt_parse_file", os.fsencode(path), quick, media, lights)
 
 
-def parse_string(text: str, quick: bool = False, media: bool = False) -> PbrtScene:
-    return _parse("bre_pbrt_parse_string", text.encode(), quick, media)
+def parse_string(text: str, quick: bool = False, media: bool = False, lights: bool = False) -> PbrtScene:
+    return _parse("bre_pbrt_parse_string", text.encode(), quick, media, lights)
 
 
 def make_spot_light(frm, to, I, coneangle: float = 30.0, conedelta: float = 5.0, order: int = 0, ctm=None,

@@ -70,6 +70,39 @@ def spot_light(frm, to, I, coneangle: float = 30.0, conedelta: float = 5.0, orde
     return make_spot_light(frm, to, I, coneangle, conedelta, order, ctm, ctm_inv)
 
 
+LIGHT_DISTANT = 3
+EMIT_ONE_SIDED, EMIT_TWO_SIDED = 1, 2  # bre_triangle.emit
+
+
+class two_sided(tuple):
+    """The Le of a mesh tuple, marked as a two-sided emitter: make_scene sets emit = EMIT_TWO_SIDED."""
+
+
+def distant_light(frm, to, L, order: int = 0, light_to_world=None) -> Light:
+    """LightSource "distant" (distant.cpp:43-47, 94-102): I = L and, in light_to_world[0..2], the world-space
+    wLight = Normalize(LightToWorld(from - to)), computed in float32 with Transform::operator()(Vector3f)'s and
+    Normalize's own operations.  `light_to_world`: the CTM as 16 row-major floats or a 4x4 (None: identity).
+    Every other field of the record stays 0 (bre_scene.h)."""
+    import numpy as np
+
+    f = np.float32
+    m = np.eye(4, dtype=f) if light_to_world is None else np.asarray(light_to_world, f).reshape(4, 4)
+    d = [f(f(frm[k]) - f(to[k])) for k in range(3)]  # Point3f - Point3f
+    # transform.h:236-242: m[i][0] * x + m[i][1] * y + m[i][2] * z
+    w = [f(f(f(m[i][0] * d[0]) + f(m[i][1] * d[1])) + f(m[i][2] * d[2])) for i in range(3)]
+    # Normalize: v / Length(v); Vector3::operator/ multiplies by the reciprocal (geometry.h)
+    length = f(np.sqrt(f(f(f(w[0] * w[0]) + f(w[1] * w[1])) + f(w[2] * w[2]))))
+    with np.errstate(all="ignore"):
+        inv = f(f(1) / length)
+    out = Light()
+    out.type = LIGHT_DISTANT
+    out.I = _f3(L)
+    for k in range(3):
+        out.light_to_world[k] = float(f(w[k] * inv))
+    out.order = int(order)
+    return out
+
+
 MATERIAL_MIRROR, MATERIAL_GLASS = 1, 2
 MAX_MATERIALS = 1024
 
@@ -263,7 +296,8 @@ def _f3(v):
 def make_scene(meshes, sigma_a=None, sigma_s=None, g=0.0,
                cam_pos=(0.5, 0.5, 0.02), cam_look=(0.5, 0.5, 1.0), cam_up=(0.0, 1.0, 0.0), fov=60.0) -> Scene:
     """meshes: list of (P, indices, kd, Le) -- a pbrt "trianglemesh" with world-space points P
-    (list of xyz), index triples, Lambertian kd, and Le (None = not emitting); medium present iff
+    (list of xyz), index triples, Lambertian kd, and Le (None = not emitting; two_sided(Le) = an
+    AreaLightSource with "bool twosided" "true"); medium present iff
     sigma_a is given (RGB or scalar).  More than MAX_TRIANGLES triangles go to an external array
     (Scene.triangles_ext, kept alive on the scene object).  A mesh may carry a fifth element, its
     Material (mirror / glass) or None: the struct does not hold it (scene_materials(meshes) returns
@@ -284,7 +318,7 @@ def make_scene(meshes, sigma_a=None, sigma_s=None, g=0.0,
                 T.p[v] = _f3(P[idx[3 * t + v]])
             T.kd = _f3(kd)
             if Le is not None:
-                T.emit = 1
+                T.emit = EMIT_TWO_SIDED if isinstance(Le, two_sided) else EMIT_ONE_SIDED
                 T.Le = _f3(Le)
             n += 1
     s.n_triangles = n

@@ -281,13 +281,16 @@ bre_status bre_gather_sharded(bre_ctx *const *ctxs, int n_ctx, int64_t nseg, con
                               const int32_t *seg_pixel, float beam_radius_cur, int64_t npix, float *accum_rgb,
                               float *seg_rgb, int32_t *seg_counts);
 
-/* ---- point and spot lights (bre_light, bre_scene.h) ----
+/* ---- point, spot and distant lights (bre_light, bre_scene.h) ----
    Copies lights[0 .. n) into the context; n == 0 clears them.  Sticky like an option: every later pass
    and render of this context that takes a bre_scene uses the scene's triangles plus these lights, merged
    into scene.lights by bre_light.order, until the next call.  A context with lights accepts a scene
    without an emitting triangle.  BRE_ERR_INVALID_ARG (and the context's lights unchanged): a null array
-   with n > 0, n < 0 or n > BRE_MAX_LIGHTS, an unknown type, a negative order, a non-finite field.  An
-   order above the scene's n_triangles is refused by the pass, where both are known.  Contexts of one
+   with n > 0, n < 0 or n > BRE_MAX_LIGHTS, an unknown type, a negative order, a non-finite field; for a
+   BRE_LIGHT_DISTANT a zero wLight, a negative L or a non-zero reserved field.  An order above the scene's
+   n_triangles is refused by the pass, where both are known; so is, while the context holds a distant light
+   (whose photons start in vacuum), a scene with a medium of its own (has_medium; bound the medium with
+   surfaces and use bre_set_media instead) and a bre_set_media light medium other than -1 for it.  Contexts of one
    bre_render_sharded / bre_render_progressive_sharded call must hold equal light arrays
    (BRE_ERR_INVALID_ARG otherwise: their films are summed).  Needs no device. */
 bre_status bre_set_lights(bre_ctx *ctx, const bre_light *lights, int32_t n);

@@ -39,8 +39,13 @@ bre_status bre_pbrt_parse_string(const char *text, bre_pbrt **out);
    MediumInterface on any shape or light, Material "" / "none" shapes as BRE_MATERIAL_INTERFACE triangles --
    and every named medium in use becomes an entry of the table bre_pbrt_get_media returns (equal media share
    one); the bre_scene then has no medium of its own.  An undefined medium name fails the parse, as in pbrt.
+   BRE_PBRT_LIGHTS: LightSource "distant" and LightSource "point" become bre_lights (bre_pbrt_get_lights) and
+   "bool twosided" "true" on an AreaLightSource "diffuse" makes BRE_EMIT_TWO_SIDED triangles.  A distant light is
+   in vacuum whatever MediumInterface is current (its entry of light_medium is -1); a scene whose one medium fills
+   all space cannot hold one: bound the medium with surfaces and add BRE_PBRT_MEDIA.  The flags combine.
    flags 0 is bre_pbrt_parse_file / _string, which keep refusing such scenes. */
 #define BRE_PBRT_MEDIA 1
+#define BRE_PBRT_LIGHTS 2
 bre_status bre_pbrt_parse_file_ex(const char *path, int32_t flags, bre_pbrt **out);
 bre_status bre_pbrt_parse_string_ex(const char *text, int32_t flags, bre_pbrt **out);
 void bre_pbrt_free(bre_pbrt *p);
@@ -50,7 +55,7 @@ const char *bre_pbrt_messages(const bre_pbrt *p, int32_t *n_errors, int32_t *n_w
    BRE_MAX_TRIANGLES triangles) triangles_ext point into the parsed scene and stay valid until
    bre_pbrt_free. */
 bre_status bre_pbrt_get_scene(const bre_pbrt *p, bre_scene *out);
-/* The scene's LightSource "spot" statements as bre_light (bre_scene.h), in declaration order, for
+/* The scene's LightSource "spot" (with BRE_PBRT_LIGHTS also "point" and "distant") statements as bre_light (bre_scene.h), in declaration order, for
    bre_set_lights: at most `capacity` are written to `out`, *n (may be NULL) receives their number.
    bre_pbrt_render sets them on every context it makes. */
 bre_status bre_pbrt_get_lights(const bre_pbrt *p, int32_t capacity, bre_light *out, int32_t *n);

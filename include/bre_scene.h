@@ -17,8 +17,10 @@
  *                       black kd = no BxDF, so a photon hitting it is absorbed,
  *                       reflection.cpp:708-713).  `flip` = ReverseOrientation ^
  *                       TransformSwapsHandedness (the normal is negated, :296-297).
- *   - diffuse area lights: every triangle with `emit` set is its own one-sided DiffuseAreaLight
- *                       (src/lights/diffuse.cpp:89-123; pbrtShape makes one light per shape of an
+ *   - diffuse area lights: every triangle with `emit` set is its own DiffuseAreaLight, one-sided
+ *                       (BRE_EMIT_ONE_SIDED) or "twosided" (BRE_EMIT_TWO_SIDED: both hemispheres emit, the
+ *                       power doubles, L() is Lemit seen from either side) (src/lights/diffuse.cpp:64-66,
+ *                       89-123; pbrtShape makes one light per shape of an
  *                       emitting mesh, api.cpp), in triangle order = scene.lights order.  The photon
  *                       pass picks one by power (ComputeLightPowerDistribution,
  *                       integrator.cpp:217-225); the camera pass uniformly (UniformSampleOneLight).
@@ -28,6 +30,15 @@
  *                       them with their Sample_Le, the camera pass lights surfaces with their Sample_Li
  *                       (no MIS, a shadow ray to the light's position); a scene lit only by them needs
  *                       no emitting triangle.
+ *   - distant lights    (bre_light with BRE_LIGHT_DISTANT; DistantLight, src/lights/distant.cpp), in the same
+ *                       list.  Its disk of emission and the far end of its shadow rays come from the bounding
+ *                       sphere of the scene BVH's root box (Scene::WorldBound().BoundingSphere, as
+ *                       DistantLight::Preprocess takes it).  The reference constructs it with an empty
+ *                       MediumInterface: its photons start in vacuum and reach a medium only through an
+ *                       interface triangle.  So with bre_set_media its light medium must be -1, and a scene
+ *                       with a medium of its own (has_medium != BRE_MEDIUM_NONE, "every ray travels in it")
+ *                       is refused while the context holds a distant light: use bre_set_media.  A photon's
+ *                       leg through vacuum still leaves a beam, as in the reference (photonbeam.cpp:290-294).
  *   - mirror and glass (bre_material below; MirrorMaterial, src/materials/mirror.cpp, and GlassMaterial
  *                       with zero roughness, src/materials/glass.cpp), set on the context with
  *                       bre_set_materials as a table and a per-triangle index.  Both passes sample the one
@@ -73,11 +84,14 @@ extern "C" {
 #define BRE_MEDIUM_GRID 2
 #define BRE_MAX_GRID_CELLS (1 << 26) /* nx*ny*nz accepted for a GridDensityMedium */
 
+#define BRE_EMIT_ONE_SIDED 1 /* DiffuseAreaLight, twoSided = false: emits on the normal's side */
+#define BRE_EMIT_TWO_SIDED 2 /* "bool twosided" "true": emits on both sides (diffuse.cpp:64-66, 100-112) */
+
 typedef struct bre_triangle {
     float p[3][3]; /* world-space vertices mesh->p[v[0..2]] (ObjectToWorld applied) */
     float kd[3];   /* Lambertian reflectance; all-zero = absorbing (no BxDF) */
     float Le[3];   /* DiffuseAreaLight "L" (Lemit) when emit != 0 */
-    int32_t emit;  /* 1: a one-sided diffuse area light */
+    int32_t emit;  /* BRE_EMIT_ONE_SIDED / BRE_EMIT_TWO_SIDED: a diffuse area light; 0: none */
     int32_t flip;  /* 1: ReverseOrientation ^ TransformSwapsHandedness (normal negated) */
 } bre_triangle;
 
@@ -111,17 +125,24 @@ typedef struct bre_scene {
     const bre_triangle *triangles_ext;
 } bre_scene;
 
-/* Delta lights: pbrt's PointLight (src/lights/point.cpp) and SpotLight (src/lights/spot.cpp).  They are
-   not part of bre_scene (its layout is fixed): a context holds them (bre_set_lights, bre.h) and every
-   pass or render that takes a bre_scene uses the scene's triangles plus the context's lights. */
+/* Delta lights: pbrt's PointLight (src/lights/point.cpp), SpotLight (src/lights/spot.cpp) and DistantLight
+   (src/lights/distant.cpp).  They are not part of bre_scene (its layout is fixed): a context holds them
+   (bre_set_lights, bre.h) and every pass or render that takes a bre_scene uses the scene's triangles plus the
+   context's lights.
+   A distant light's record holds what its constructor leaves: I = "L" * "scale", and in light_to_world[0..2] the
+   world-space wLight = Normalize(LightToWorld(from - to)), the direction TOWARDS the light (finite, not zero).
+   It reads nothing else: the rest of light_to_world, world_to_light and the two cone angles are reserved and must
+   be 0, so a point or spot record relabelled as distant is refused.  Point and spot records are unchanged. */
 #define BRE_LIGHT_POINT 1
 #define BRE_LIGHT_SPOT 2
+#define BRE_LIGHT_DISTANT 3
 #define BRE_MAX_LIGHTS 1024 /* delta lights accepted by bre_set_lights */
 
 typedef struct bre_light {
-    int32_t type;               /* BRE_LIGHT_POINT / BRE_LIGHT_SPOT */
-    float I[3];                 /* "I", already multiplied by "scale" */
-    float light_to_world[16];   /* LightToWorld, row-major 4x4 (a point light: Translate(from) * CTM) */
+    int32_t type;               /* BRE_LIGHT_POINT / BRE_LIGHT_SPOT / BRE_LIGHT_DISTANT */
+    float I[3];                 /* "I" (distant: "L"), already multiplied by "scale"; distant: >= 0 */
+    float light_to_world[16];   /* LightToWorld, row-major 4x4 (a point light: Translate(from) * CTM);
+                                   distant: [0..2] = wLight, see above */
     float world_to_light[16];   /* its inverse as the reference tracks it (Transform::mInv), row-major;
                                    SpotLight::Falloff goes through it */
     float cone_total_deg;       /* spot: "coneangle" (totalWidth, degrees) */
