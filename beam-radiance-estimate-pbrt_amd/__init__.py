@@ -46,7 +46,7 @@ EXPORTS = [
     "bre_render_progressive", "bre_shard_segments", "bre_set_beams_sharded", "bre_gather_sharded",
     "bre_device_check", "bre_resolve_classes", "bre_film_add", "bre_set_gather_after", "bre_set_gather_events",
     "bre_render_sharded", "bre_render_progressive_sharded", "bre_set_lights", "bre_set_materials",
-    "bre_set_media", "bre_set_materials_ex",
+    "bre_set_media", "bre_set_materials_ex", "bre_check_material_ex",
 ]
 # bre_image_fn: int on_image(int32 iteration, const float *image_rgb, void *user)
 IMAGE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_int32, ctypes.POINTER(ctypes.c_float), ctypes.c_void_p)
@@ -137,6 +137,9 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     if hasattr(lib, "bre_set_materials_ex"):
         lib.bre_set_materials_ex.argtypes = [P, P, I32, P, I64]
         lib.bre_set_materials_ex.restype = I32
+    if hasattr(lib, "bre_check_material_ex"):
+        lib.bre_check_material_ex.argtypes = [P, ctypes.c_char_p, I32]
+        lib.bre_check_material_ex.restype = I32
     if hasattr(lib, "bre_set_media"):
         lib.bre_set_media.argtypes = [P, P, I32, P, P, I64, I32, P, I32]
         lib.bre_set_media.restype = I32
@@ -522,6 +525,21 @@ class BeamGather:
         x = np.ascontiguousarray(records, dtype=np.float32).reshape(-1, 9)
         y = np.zeros((x.shape[0], 12), np.float32)
         self._check(self.lib.bre_device_check(self.h, 13, x.size, _ptr(x), aux.size, _ptr(aux), _ptr(y)))
+        return {"wi": y[:, :3].copy(), "pdf": y[:, 3].copy(), "f": y[:, 4:7].copy(),
+                "type": y[:, 7].copy().view(np.int32), "f2": y[:, 8:11].copy(), "pdf2": y[:, 11].copy()}
+
+    def lobes_check(self, materials, records):
+        """bre_device_check kind 14: the BSDF of any number of lobes on records [n, 11]: those of bsdf_check, then the
+        transport mode (0 Importance / 1 Radiance) and the flag set (0 BSDF_ALL / 1 BSDF_ALL & ~BSDF_SPECULAR);
+        `materials` may also hold rough glass, uber, translucent and substrate records.  Returns bsdf_check's dict."""
+        from .scene import MaterialEx
+
+        mats = list(materials)
+        aux = np.frombuffer(b"".join(m.to_bytes() for m in mats), np.float32).copy()
+        assert aux.size == len(mats) * ctypes.sizeof(MaterialEx) // 4
+        x = np.ascontiguousarray(records, dtype=np.float32).reshape(-1, 11)
+        y = np.zeros((x.shape[0], 12), np.float32)
+        self._check(self.lib.bre_device_check(self.h, 14, x.size, _ptr(x), aux.size, _ptr(aux), _ptr(y)))
         return {"wi": y[:, :3].copy(), "pdf": y[:, 3].copy(), "f": y[:, 4:7].copy(),
                 "type": y[:, 7].copy().view(np.int32), "f2": y[:, 8:11].copy(), "pdf2": y[:, 11].copy()}
 

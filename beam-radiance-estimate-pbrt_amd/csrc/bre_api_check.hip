@@ -121,7 +121,7 @@ extern "C" {
 bre_status bre_device_check(bre_ctx *c, int32_t kind, int64_t n, const float *x, int32_t n_aux, const float *aux,
                             float *y) {
     if (!c) return BRE_ERR_INVALID_ARG;
-    if (kind < 0 || kind > 13) return fail(c, BRE_ERR_INVALID_ARG, "bre_device_check: kind %d not in [0, 13]", kind);
+    if (kind < 0 || kind > 14) return fail(c, BRE_ERR_INVALID_ARG, "bre_device_check: kind %d not in [0, 14]", kind);
     if (kind == 10) return check_hierarchy(c, n, x, n_aux, aux, y);
     if (kind == 11) return check_read_tree(c, n, y);
     if (n < 0 || (n > 0 && (!x || !y))) return fail(c, BRE_ERR_INVALID_ARG, "bre_device_check: bad arrays");
@@ -171,6 +171,47 @@ bre_status bre_device_check(bre_ctx *c, int32_t kind, int64_t n, const float *x,
         HIPCHK(c, hipMemcpyAsync(dx, x, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipMemcpyAsync(dt, table.data(), table.size() * sizeof(DevBsdf), hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, launch_check_bsdf(n / 9, dx, dt, n_mats, dy, c->stream));
+        HIPCHK(c, hipMemcpyAsync(y, dy, outs * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return BRE_OK;
+    }
+    if (kind == 14) {
+        // the BSDF of any number of lobes: kind 13's records with a transport mode and a flag set, against a table
+        // of bre_material_ex records of types 4 .. 6 and 8 .. 11 (layout: include/bre.h)
+        constexpr int kWords = (int)(sizeof(bre_material_ex) / 4), kRec = 11;
+        if (n % kRec || n_aux < kWords || n_aux % kWords || !aux)
+            return fail(c, BRE_ERR_INVALID_ARG, "bre_device_check: kind 14 needs whole records of %d floats and, in aux, "
+                        "whole bre_material_ex records of %d words", kRec, kWords);
+        const int n_mats = n_aux / kWords;
+        std::vector<bre_material_ex> mats((size_t)n_mats);
+        std::memcpy(mats.data(), aux, (size_t)n_aux * 4);
+        std::vector<DevLobes> table((size_t)n_mats);
+        for (int k = 0; k < n_mats; ++k) {
+            const std::string what = check_lobed_or_glossy_material(mats[(size_t)k]);
+            if (!what.empty())
+                return fail(c, BRE_ERR_INVALID_ARG, "bre_device_check: kind 14: material %d has %s", k, what.c_str());
+            table[(size_t)k] = make_lobes(mats[(size_t)k]);
+        }
+        for (int64_t i = 0; i < n / kRec; ++i) {
+            const float *r = x + kRec * i;
+            if (!(r[8] >= 0 && r[8] < (float)n_mats) || r[8] != std::floor(r[8]))
+                return fail(c, BRE_ERR_INVALID_ARG, "bre_device_check: kind 14: record %lld names material %g of %d",
+                            (long long)i, (double)r[8], n_mats);
+            if ((r[9] != 0.f && r[9] != 1.f) || (r[10] != 0.f && r[10] != 1.f))
+                return fail(c, BRE_ERR_INVALID_ARG, "bre_device_check: kind 14: record %lld has a mode or a flag set "
+                            "that is not 0 or 1", (long long)i);
+        }
+        if (n == 0) return BRE_OK;
+        BRE_TRY(set_device(c));
+        float *dx = nullptr, *dy = nullptr;
+        DevLobes *dt = nullptr;
+        const size_t outs = (size_t)(n / kRec) * 12;
+        HIPCHK(c, c->chk_x.get((size_t)n, &dx));
+        HIPCHK(c, c->chk_y.get(outs, &dy));
+        HIPCHK(c, c->chk_aux.get((size_t)n_mats, &dt));
+        HIPCHK(c, hipMemcpyAsync(dx, x, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(dt, table.data(), table.size() * sizeof(DevLobes), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, launch_check_lobes(n / kRec, dx, dt, n_mats, dy, c->stream));
         HIPCHK(c, hipMemcpyAsync(y, dy, outs * 4, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         return BRE_OK;

@@ -63,24 +63,27 @@ bre_status bre_trace_photons(bre_ctx *c, const bre_scene *scene, int64_t n_photo
     int cap = c->photon_single ? (int)std::min<int64_t>(64, ((int64_t)5 << 29) / (40 * std::max<int64_t>(n_photons, 1))) : 0;
     if (cap < 4) cap = 0;
     if (c->photon_single >= 2) cap = c->photon_single;  // tests: a forced slot count (overflow paths)
+    const int tier = c->held.lobed ? 2 : (c->held.glossy ? 1 : 0);
     if (c->held.glossy) {
         // the glossy photon kernels keep max_depth suspended frames a thread in LDS: refused here, by name
         if (c->lds_per_block == 0)
             HIPCHK(c, hipDeviceGetAttribute(&c->lds_per_block, hipDeviceAttributeMaxSharedMemoryPerBlock, c->device));
         const size_t need = photon_lds_bytes(sdepth, max_depth, true);
         if (need > (size_t)c->lds_per_block)
-            return fail(c, BRE_ERR_INVALID_ARG, "bre_trace_photons: maxdepth %d with plastic / metal / matte-sigma "
+            return fail(c, BRE_ERR_INVALID_ARG, "bre_trace_photons: maxdepth %d with %s "
                         "materials needs %lld bytes of LDS per block for the photon kernels' suspended frames; the "
-                        "device has %d", max_depth, (long long)need, c->lds_per_block);
+                        "device has %d", max_depth,
+                        c->held.lobed ? "rough glass / uber / translucent / substrate" : "plastic / metal / matte-sigma",
+                        (long long)need, c->lds_per_block);
     }
     BeamArrays &slots = c->ph_s, &in = c->in;
     if (cap > 0) {
         HIPCHK(c, slots.ensure(N * (size_t)cap));
         HIPCHK(c, launch_photons(ds, sdepth, n_photons, seq0, max_depth, beam_radius, counts, nullptr, slots.out(), 2, cap,
-                                 media, c->held.glossy, c->stream));
+                                 media, tier, c->stream));
     } else {
         HIPCHK(c, launch_photons(ds, sdepth, n_photons, seq0, max_depth, beam_radius, counts, nullptr, BeamOut{}, 0, 0,
-                                 media, c->held.glossy, c->stream));
+                                 media, tier, c->stream));
     }
     HIPCHK(c, launch_count_scan(c->ph_tmp.ptr, c->ph_tmp.cap, counts, offsets, n_photons, c->stream,
                                 c->slot_passes != 0));
@@ -92,7 +95,7 @@ bre_status bre_trace_photons(bre_ctx *c, const bre_scene *scene, int64_t n_photo
             HIPCHK(c, launch_photon_slots(n_photons, cap, counts, offsets, slots.view(), in.out(), c->stream));
         // every photon (two-trace form), or only those with more beams than slots
         HIPCHK(c, launch_photons(ds, sdepth, n_photons, seq0, max_depth, beam_radius, counts, offsets, in.out(), 1, cap,
-                                 media, c->held.glossy, c->stream));
+                                 media, tier, c->stream));
     }
     float photon_ms = 0.f;
     if (c->timing) {
@@ -162,11 +165,12 @@ bre_status bre_camera_pass(bre_ctx *c, const bre_scene *scene, int32_t width, in
     // run inside another context's gather at 80 VGPRs, keep the code and the resources they had
     bool wide = c->held.glossy;
     for (const bre_light &l : c->held.lights) wide = wide || l.type == BRE_LIGHT_DISTANT;
+    const int tier = c->held.lobed ? 2 : (wide ? 1 : 0);
     HIPCHK(c, launch_camera(c->dev.record.as<DevScene>(), c->dev.head.stack_depth, c->cam_dev.as<DevCamera>(),
                             c->cam_perms.as<uint16_t>(),
                             width, height, iteration, max_depth, render_surfaces, render_media, cs, d_surface,
                             cam_flags, c->shard_rank, c->shard_count,
-                            c->shard_mode != 0 ? 0 : c->shard_block, c->film_classes, planes, media, wide, c->stream));
+                            c->shard_mode != 0 ? 0 : c->shard_block, c->film_classes, planes, media, tier, c->stream));
     // exclusive scan of the slots' valid flags into cam_offs: total = offs[S-1] + valid[S-1]
     HIPCHK(c, launch_camera_scan(c->cam_tmp.ptr, c->cam_tmp.cap, cs, nslots, planes, offs, c->stream,
                                  c->slot_passes != 0));

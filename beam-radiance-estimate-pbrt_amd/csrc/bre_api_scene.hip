@@ -106,6 +106,68 @@ uint64_t hash_geometry(const bre_scene *s, const KeyPart part[4]) {
     return h | 1ull;  // never 0 (= no scene)
 }
 
+// A rough glass, uber, translucent or substrate record (types 8 .. 11): the fields its type reads are finite, its
+// alphas are > 0 after the material's own fallbacks and mapping (glass.cpp:66-69, uber.cpp:72-83,
+// translucent.cpp:66-68, substrate.cpp:57-60), and every field it does not read is 0; its colours are clamped.
+std::string check_lobed_material(bre_material_ex &m) {
+    static const char *const kName[4] = {"rough glass", "uber", "translucent", "substrate"};
+    const std::string name = kName[m.type - BRE_MATERIAL_ROUGH_GLASS];
+    const bool glass = m.type == BRE_MATERIAL_ROUGH_GLASS, uber = m.type == BRE_MATERIAL_UBER;
+    const bool trans = m.type == BRE_MATERIAL_TRANSLUCENT;
+    struct Field {
+        const char *name;
+        float *v;
+        int n;
+        bool read, colour;
+    };
+    const Field fields[] = {
+        {trans ? "reflect" : "Kr", m.kr, 3, glass || uber || trans, true},
+        {trans ? "transmit" : "Kt", m.kt, 3, glass || uber || trans, true},
+        {"eta", &m.eta, 1, glass || uber, false},          {"Kd", m.kd, 3, !glass, true},
+        {"Ks", m.ks, 3, !glass, true},                     {"opacity", m.opacity, 3, uber, true},
+        {"k", m.ck, 3, false, false},                      {"roughness", &m.roughness, 1, uber || trans, false},
+        {"uroughness", &m.uroughness, 1, !trans, false},   {"vroughness", &m.vroughness, 1, !trans, false},
+        {"sigma", &m.sigma, 1, false, false},
+    };
+    for (const Field &f : fields)
+        for (int j = 0; j < f.n; ++j) {
+            if (f.read && !std::isfinite(f.v[j])) return "a non-finite " + std::string(f.name) + " (" + name + ")";
+            if (!f.read && !(f.v[j] == 0))  // a NaN too
+                return std::string(std::isfinite(f.v[j]) ? "a non-zero " : "a non-finite ") + f.name + ", which a " + name +
+                       " does not read" +
+                       (f.v == m.opacity ? " (opacity shares the storage of the metal's eta)" : "");
+        }
+    if (m.remap != 0 && m.remap != 1) return "a remap that is not 0 or 1 (" + name + ")";
+    if ((glass || uber) && !(m.eta > 0)) {
+        char buf[96];
+        snprintf(buf, sizeof(buf), "eta %g (must be finite and > 0; %s)", m.eta, name.c_str());
+        return buf;
+    }
+    if (glass && m.uroughness == 0 && m.vroughness == 0)
+        return "uroughness and vroughness both 0 (rough glass): that is BRE_MATERIAL_GLASS";
+    float u, v;
+    if (uber) {
+        u = m.uroughness != 0 ? m.uroughness : m.roughness;
+        v = m.vroughness != 0 ? m.vroughness : u;
+    } else if (trans) {
+        u = v = m.roughness;
+    } else {
+        u = m.uroughness;
+        v = m.vroughness;
+    }
+    if (m.remap) {
+        u = roughness_to_alpha(u);
+        v = roughness_to_alpha(v);
+    }
+    if (!(u > 0) || !(v > 0))
+        return "an alpha that is not > 0 (" + name + ": the roughnesses after " +
+               (m.remap ? "RoughnessToAlpha" : "the fallbacks, remaproughness false") + ")";
+    for (const Field &f : fields)
+        if (f.read && f.colour)
+            for (int j = 0; j < 3; ++j) f.v[j] = f.v[j] < 0.f ? 0.f : (f.v[j] > 1.f ? 1.f : f.v[j]);
+    return "";
+}
+
 // One record of the table as the context keeps it: checked, colours clamped, unused fields left as given (equal
 // tables compare equal).  `wide`: types past BRE_MATERIAL_INTERFACE are known.  Returns "", or what the material
 // has that is wrong (the narrow cases in bre_set_materials's words).
@@ -136,6 +198,7 @@ std::string check_material(bre_material_ex &m, bool wide, bool media, bool *is_i
         clamp3(m.kt);
         return "";
     }
+    if (wide && m.type >= BRE_MATERIAL_ROUGH_GLASS && m.type <= BRE_MATERIAL_SUBSTRATE) return check_lobed_material(m);
     if (!wide || m.type < BRE_MATERIAL_MATTE || m.type > BRE_MATERIAL_METAL) {
         snprintf(buf, sizeof(buf), "unknown type %d%s", m.type,
                  m.type == BRE_MATERIAL_INTERFACE ? " (BRE_MATERIAL_INTERFACE needs bre_set_media first)" : "");
@@ -172,6 +235,7 @@ bre_status set_material_table(bre_ctx *c, const char *fn, const bre_material_ex 
         c->held.tri_mat.clear();
         c->held.has_interface = false;
         c->held.glossy = false;
+        c->held.lobed = false;
         return BRE_OK;
     }
     if (n_triangles < 0 || n_triangles > BRE_MAX_SCENE_TRIANGLES)
@@ -181,13 +245,14 @@ bre_status set_material_table(bre_ctx *c, const char *fn, const bre_material_ex 
         return fail(c, BRE_ERR_INVALID_ARG, "%s: null material table or triangle_material map", fn);
     std::vector<bre_material_ex> mats(materials, materials + n_materials);
     std::vector<char> is_interface((size_t)n_materials, 0);
-    bool glossy = false;
+    bool glossy = false, lobed = false;
     for (int k = 0; k < n_materials; ++k) {
         bool iface = false;
         const std::string what = check_material(mats[(size_t)k], wide, !c->held.media.empty(), &iface);
         if (!what.empty()) return fail(c, BRE_ERR_INVALID_ARG, "%s: material %d has %s", fn, k, what.c_str());
         is_interface[(size_t)k] = iface;
         glossy = glossy || mats[(size_t)k].type >= BRE_MATERIAL_MATTE;
+        lobed = lobed || mats[(size_t)k].type >= BRE_MATERIAL_ROUGH_GLASS;
     }
     for (int64_t i = 0; i < n_triangles; ++i)
         if (triangle_material[i] < -1 || triangle_material[i] >= n_materials)
@@ -197,6 +262,7 @@ bre_status set_material_table(bre_ctx *c, const char *fn, const bre_material_ex 
     c->held.tri_mat.assign(triangle_material, triangle_material + n_triangles);
     c->held.has_interface = false;
     c->held.glossy = glossy;
+    c->held.lobed = lobed;
     for (int64_t i = 0; i < n_triangles; ++i)
         if (triangle_material[i] >= 0 && is_interface[(size_t)triangle_material[i]]) c->held.has_interface = true;
     return BRE_OK;
@@ -208,7 +274,14 @@ namespace bre {
 
 std::string check_glossy_material(bre_material_ex &m) {
     bool iface;
-    if (m.type < BRE_MATERIAL_MATTE) return "a type outside BRE_MATERIAL_MATTE .. BRE_MATERIAL_METAL";
+    if (m.type < BRE_MATERIAL_MATTE || m.type > BRE_MATERIAL_METAL)
+        return "a type outside BRE_MATERIAL_MATTE .. BRE_MATERIAL_METAL";
+    return check_material(m, true, false, &iface);
+}
+
+std::string check_lobed_or_glossy_material(bre_material_ex &m) {
+    bool iface;
+    if (m.type < BRE_MATERIAL_MATTE) return "a type below BRE_MATERIAL_MATTE";
     return check_material(m, true, false, &iface);
 }
 
@@ -330,6 +403,7 @@ bre_status upload_scene(bre_ctx *c, const bre_scene *scene) {
         HIPCHK(c, upload(c, dv.dlights, hs.dlights, &dv.head.dlights));
         HIPCHK(c, upload(c, dv.mats, hs.mats, &dv.head.mats));
         HIPCHK(c, upload(c, dv.bsdfs, hs.bsdfs, &dv.head.bsdfs));
+        HIPCHK(c, upload(c, dv.lobes, hs.lobes, &dv.head.lobes));
         HIPCHK(c, hipStreamSynchronize(c->stream));  // the host vectors go out of scope
         dv.hash = hash;
         for (int k = 0; k < 4; ++k) {
@@ -356,6 +430,17 @@ bre_status upload_scene(bre_ctx *c, const bre_scene *scene) {
 }  // namespace bre
 
 extern "C" {
+
+bre_status bre_check_material_ex(const bre_material_ex *material, char *message, int32_t capacity) {
+    if (message && capacity > 0) message[0] = 0;
+    if (!material) return BRE_ERR_INVALID_ARG;
+    bre_material_ex m = *material;
+    bool iface = false;
+    const std::string what = check_material(m, true, false, &iface);
+    if (what.empty()) return BRE_OK;
+    if (message && capacity > 0) snprintf(message, (size_t)capacity, "%s", what.c_str());
+    return BRE_ERR_INVALID_ARG;
+}
 
 bre_status bre_set_lights(bre_ctx *c, const bre_light *lights, int32_t n) {
     if (!c) return BRE_ERR_INVALID_ARG;

@@ -315,9 +315,14 @@ __device__ __forceinline__ float power_heuristic(float fpdf, float gpdf) {
 // (scene.cpp:62-75): both step through interface triangles and multiply each segment's Tr in order.
 // GL (bre_set_materials_ex): a plastic, metal or matte vertex goes through the general BSDF (bre_trace.h), whose
 // Pdf is not the cosine's; the early out stays for mirror, glass and interface entries.
-template <bool MED, bool GL>
+// TIER: 0 = GL false, 1 = GL true, 2 = the table holds a rough glass, uber, translucent or substrate entry: every entry
+// from BRE_MATERIAL_MATTE up goes through the BSDF of any number of lobes with bsdfFlags = BSDF_ALL & ~BSDF_SPECULAR
+// (integrator.cpp:112-113) in TransportMode::Radiance: f and Pdf on both sides of the surface, the BSDF-sampling half
+// over the non-specular lobes only, and nothing at all where none matches (matchingComps == 0).
+template <bool MED, int TIER>
 __device__ void estimate_direct(const DevScene &S, HaltonDev &hs, f3 p, f3 perr, const PTri &q, f3 wo, int li,
                                 float usx, float usy, float ulx, float uly, float Ld[3], int tri, int med) {
+    constexpr bool GL = TIER >= 1;
     const bool delta = li < 0;
     const PTri &L = S.t[delta ? 0 : li];
     Ld[0] = Ld[1] = Ld[2] = 0.f;
@@ -325,8 +330,13 @@ __device__ void estimate_direct(const DevScene &S, HaltonDev &hs, f3 p, f3 perr,
     // is 0, so there is no shadow ray and no Tr draw (:132-152), and the BSDF-sampling half's Sample_f has
     // matchingComps == 0 (f = 0, pdf = 0).  Ld = 0 without a draw.
     const DevBsdf *gm = nullptr;
+    const DevLobes *lm = nullptr;
+    (void)lm;
     if (q.mat >= kMatTable) {
-        if constexpr (GL) {
+        if constexpr (TIER == 2) {
+            lm = &S.lobes[q.mat - kMatTable];
+            if (lm->type == 0 || lm->n_nonspec == 0) return;
+        } else if constexpr (GL) {
             if (S.bsdfs[q.mat - kMatTable].type == 0) return;
             gm = &S.bsdfs[q.mat - kMatTable];
         } else {
@@ -374,11 +384,17 @@ __device__ void estimate_direct(const DevScene &S, HaltonDev &hs, f3 p, f3 perr,
     const f3 sp = ps.p;
     if (light_pdf > 0 && !black3(Li)) {
         float f[3];
-        if (GL && gm) bsdf_f(q, *gm, wo, wi, f);
-        else bsdf_f(q, wo, wi, f);
+        if constexpr (TIER == 2) {
+            if (lm) bsdfn_f(q, *lm, wo, wi, kBsdfNonSpecular, kModeRadiance, f);
+            else bsdf_f(q, wo, wi, f);
+        } else {
+            if (GL && gm) bsdf_f(q, *gm, wo, wi, f);
+            else bsdf_f(q, wo, wi, f);
+        }
         const float ad = fabsf(dot3(wi, q.n));
         for (int c = 0; c < 3; ++c) f[c] = f[c] * ad;
-        scat_pdf = (GL && gm) ? bsdf_pdf(q, *gm, wo, wi) : bsdf_pdf(q, wo, wi);
+        if constexpr (TIER == 2) scat_pdf = lm ? bsdfn_pdf(q, *lm, wo, wi, kBsdfNonSpecular) : bsdf_pdf(q, wo, wi);
+        else scat_pdf = (GL && gm) ? bsdf_pdf(q, *gm, wo, wi) : bsdf_pdf(q, wo, wi);
         if (!black3(f)) {
             // VisibilityTester::Tr over Interaction::SpawnRayTo(pShape)
             f3 ro = offset_origin(p, perr, q.n, sub3(sp, p));
@@ -428,8 +444,13 @@ __device__ void estimate_direct(const DevScene &S, HaltonDev &hs, f3 p, f3 perr,
     {
         float f[3];
         int type;
-        if (GL && gm) bsdf_sample(q, *gm, wo, usx, usy, wi, scat_pdf, f, type);
-        else bsdf_sample(q, wo, usx, usy, wi, scat_pdf, f);
+        if constexpr (TIER == 2) {
+            if (lm) bsdfn_sample(q, *lm, wo, usx, usy, kBsdfNonSpecular, kModeRadiance, wi, scat_pdf, f, type);
+            else bsdf_sample(q, wo, usx, usy, wi, scat_pdf, f);
+        } else {
+            if (GL && gm) bsdf_sample(q, *gm, wo, usx, usy, wi, scat_pdf, f, type);
+            else bsdf_sample(q, wo, usx, usy, wi, scat_pdf, f);
+        }
         const float ad = fabsf(dot3(wi, q.n));
         for (int c = 0; c < 3; ++c) f[c] = f[c] * ad;
         if (!black3(f) && scat_pdf > 0) {
@@ -481,16 +502,19 @@ __device__ void estimate_direct(const DevScene &S, HaltonDev &hs, f3 p, f3 perr,
 // instead of its depth.  MED false is the one-medium walk, the code it was before media.
 // GL: the general BSDF for the table's plastic, metal and matte entries, and the distant lights' Sample_Li, at
 // kGlossyWaves waves per SIMD; GL false is the code it was before them, held to 80 VGPRs.
-template <bool MED, bool GL>
-__global__ __launch_bounds__(kCamBlock, GL ? kGlossyWaves : 6) void k_camera(const DevScene *__restrict__ Sp, const DevCamera *__restrict__ Cp,
-                                                     const uint16_t *__restrict__ perms, int iteration, int max_depth,
-                                                     int render_surfaces, int render_media, int64_t nslots,
-                                                     float *__restrict__ so, float *__restrict__ sp_,
-                                                     float *__restrict__ sd, float *__restrict__ st,
-                                                     int32_t *__restrict__ spix, int32_t *__restrict__ valid,
-                                                     float *__restrict__ surface, unsigned int *__restrict__ flags,
-                                                     int shard_rank, int shard_count, int shard_block, int classes,
-                                                     int planes) {
+// TIER: 0 = GL false, 1 = GL true, 2 = the BSDF of any number of lobes (see estimate_direct): the bounce samples it
+// with BSDF_ALL in TransportMode::Radiance and specularBounce follows the sampled lobe's type.  The walk is one body:
+// k_camera<MED, GL> runs tiers 0 and 1 under the names and bounds it had, k_camera_tr<MED> tier 2.
+template <bool MED, int TIER>
+__device__ __forceinline__ void camera_walk(const DevScene *__restrict__ Sp, const DevCamera *__restrict__ Cp,
+                                            const uint16_t *__restrict__ perms, int iteration, int max_depth,
+                                            int render_surfaces, int render_media, int64_t nslots,
+                                            float *__restrict__ so, float *__restrict__ sp_, float *__restrict__ sd,
+                                            float *__restrict__ st, int32_t *__restrict__ spix,
+                                            int32_t *__restrict__ valid, float *__restrict__ surface,
+                                            unsigned int *__restrict__ flags, int shard_rank, int shard_count,
+                                            int shard_block, int classes, int planes) {
+    constexpr bool GL = TIER >= 1;
     const DevScene &S = *Sp;
     const DevCamera &C = *Cp;
     const int64_t slot = (int64_t)blockIdx.x * kCamBlock + threadIdx.x;
@@ -592,10 +616,10 @@ __global__ __launch_bounds__(kCamBlock, GL ? kGlossyWaves : 6) void k_camera(con
             const int lt = S.light_tri[ln];
             if constexpr (GL) {
                 // inlined here: as a call the general BSDF's estimate_direct takes the sampler through memory
-                [[clang::always_inline]] estimate_direct<MED, GL>(S, hs, hit.p, hit.perr, q, normalize3(wo), lt, usx, usy,
+                [[clang::always_inline]] estimate_direct<MED, TIER>(S, hs, hit.p, hit.perr, q, normalize3(wo), lt, usx, usy,
                                                                   ulx, uly, ed, hit.tri, med);
             } else {
-                estimate_direct<MED, GL>(S, hs, hit.p, hit.perr, q, normalize3(wo), lt, usx, usy, ulx, uly, ed, hit.tri, med);
+                estimate_direct<MED, TIER>(S, hs, hit.p, hit.perr, q, normalize3(wo), lt, usx, usy, ulx, uly, ed, hit.tri, med);
             }
             for (int c = 0; c < 3; ++c) Ld[c] = Ld[c] + beta[c] * (ed[c] / light_pdf);
             if (depth < max_depth - 1) {
@@ -605,9 +629,14 @@ __global__ __launch_bounds__(kCamBlock, GL ? kGlossyWaves : 6) void k_camera(con
                 int type = 0;  // the sampled BxDFType's specular bit; a Lambertian lobe has none
                 bool ok;
                 bool general = false;
-                if constexpr (GL) general = q.mat >= kMatTable && S.bsdfs[q.mat - kMatTable].type != 0;
+                if constexpr (TIER == 2) general = q.mat >= kMatTable && S.lobes[q.mat - kMatTable].type != 0;
+                else if constexpr (GL) general = q.mat >= kMatTable && S.bsdfs[q.mat - kMatTable].type != 0;
                 if (general) {
-                    ok = bsdf_sample(q, S.bsdfs[q.mat - kMatTable], wo, ux, uy, wi, pdf, f, type);
+                    if constexpr (TIER == 2)
+                        ok = bsdfn_sample(q, S.lobes[q.mat - kMatTable], wo, ux, uy, kBsdfAll, kModeRadiance, wi, pdf, f,
+                                          type);
+                    else
+                        ok = bsdf_sample(q, S.bsdfs[q.mat - kMatTable], wo, ux, uy, wi, pdf, f, type);
                 } else if (q.mat >= kMatTable) {
                     // mirror / glass: the one specular lobe, TransportMode::Radiance (:514)
                     f3 wil;
@@ -639,6 +668,34 @@ __global__ __launch_bounds__(kCamBlock, GL ? kGlossyWaves : 6) void k_camera(con
     }
 }
 
+template <bool MED, bool GL>
+__global__ __launch_bounds__(kCamBlock, GL ? kGlossyWaves : 6) void k_camera(const DevScene *__restrict__ Sp, const DevCamera *__restrict__ Cp,
+                                                     const uint16_t *__restrict__ perms, int iteration, int max_depth,
+                                                     int render_surfaces, int render_media, int64_t nslots,
+                                                     float *__restrict__ so, float *__restrict__ sp_,
+                                                     float *__restrict__ sd, float *__restrict__ st,
+                                                     int32_t *__restrict__ spix, int32_t *__restrict__ valid,
+                                                     float *__restrict__ surface, unsigned int *__restrict__ flags,
+                                                     int shard_rank, int shard_count, int shard_block, int classes,
+                                                     int planes) {
+    camera_walk<MED, GL ? 1 : 0>(Sp, Cp, perms, iteration, max_depth, render_surfaces, render_media, nslots, so, sp_, sd,
+                                 st, spix, valid, surface, flags, shard_rank, shard_count, shard_block, classes, planes);
+}
+
+template <bool MED>
+__global__ __launch_bounds__(kCamBlock, kGlossyWaves) void k_camera_tr(const DevScene *__restrict__ Sp, const DevCamera *__restrict__ Cp,
+                                                     const uint16_t *__restrict__ perms, int iteration, int max_depth,
+                                                     int render_surfaces, int render_media, int64_t nslots,
+                                                     float *__restrict__ so, float *__restrict__ sp_,
+                                                     float *__restrict__ sd, float *__restrict__ st,
+                                                     int32_t *__restrict__ spix, int32_t *__restrict__ valid,
+                                                     float *__restrict__ surface, unsigned int *__restrict__ flags,
+                                                     int shard_rank, int shard_count, int shard_block, int classes,
+                                                     int planes) {
+    camera_walk<MED, 2>(Sp, Cp, perms, iteration, max_depth, render_surfaces, render_media, nslots, so, sp_, sd, st, spix,
+                        valid, surface, flags, shard_rank, shard_count, shard_block, classes, planes);
+}
+
 __global__ void k_compact(int64_t nslots_total, const int32_t *__restrict__ valid, const int64_t *__restrict__ offs,
                           const float *__restrict__ so, const float *__restrict__ sp_, const float *__restrict__ sd,
                           const float *__restrict__ st, const int32_t *__restrict__ spix, float *__restrict__ o,
@@ -666,7 +723,7 @@ int64_t camera_slots(int width, int height) {
 hipError_t launch_camera(const DevScene *scene, int stack_depth, const DevCamera *cam, const uint16_t *perms, int width,
                          int height, int iteration, int max_depth, int render_surfaces, int render_media,
                          const CamSlots &s, float *surface, unsigned int *flags, int shard_rank, int shard_count,
-                         int shard_block, int classes, int planes, bool media, bool glossy, hipStream_t stream) {
+                         int shard_block, int classes, int planes, bool media, int tier, hipStream_t stream) {
     const int64_t nslots = camera_slots(width, height);
     if (nslots == 0) return hipSuccess;
     const auto go = [&](auto kernel) {
@@ -676,7 +733,8 @@ hipError_t launch_camera(const DevScene *scene, int stack_depth, const DevCamera
                            s.valid, surface, flags, shard_rank, shard_count, shard_block, classes < 1 ? 1 : classes,
                            planes);
     };
-    if (glossy) media ? go(k_camera<true, true>) : go(k_camera<false, true>);
+    if (tier == 2) media ? go(k_camera_tr<true>) : go(k_camera_tr<false>);
+    else if (tier == 1) media ? go(k_camera<true, true>) : go(k_camera<false, true>);
     else media ? go(k_camera<true, false>) : go(k_camera<false, false>);
     return hipGetLastError();
 }

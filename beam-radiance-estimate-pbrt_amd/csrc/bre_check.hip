@@ -113,7 +113,53 @@ __global__ __launch_bounds__(256) void k_check_bsdf(int64_t n, const float *__re
     o[11] = bsdf_pdf(q, m, wo, wi2);
 }
 
+// kind 14: the BSDF of any number of lobes (bre_trace.h) on n records of 11 floats: those of kind 13, then the
+// transport mode (0: Importance) and the flag set (0: BSDF_ALL, 1: BSDF_ALL & ~BSDF_SPECULAR); the same 12 words out
+__global__ __launch_bounds__(256) void k_check_lobes(int64_t n, const float *__restrict__ x,
+                                                     const DevLobes *__restrict__ table, int n_table,
+                                                     float *__restrict__ y) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float *r = x + 11 * i;
+    const int k = (int)r[8];
+    float *o = y + 12 * i;
+    for (int j = 0; j < 12; ++j) o[j] = 0.f;
+    if (k < 0 || k >= n_table) return;
+    const DevLobes &m = table[k];  // read in place: its lobes are indexed at run time
+    const int mode = r[9] != 0.f ? kModeRadiance : kModeImportance;
+    const int flags = r[10] != 0.f ? kBsdfNonSpecular : kBsdfAll;
+    PTri q{};
+    q.ss = mk(1.f, 0.f, 0.f);
+    q.ts = mk(0.f, 1.f, 0.f);
+    q.n = mk(0.f, 0.f, 1.f);
+    const f3 wo = mk(r[0], r[1], r[2]), wi2 = mk(r[5], r[6], r[7]);
+    f3 wi = mk(0.f, 0.f, 0.f);
+    float pdf = 0.f, f[3];
+    int type;
+    if (bsdfn_sample(q, m, wo, r[3], r[4], flags, mode, wi, pdf, f, type)) {
+        o[0] = wi.x;
+        o[1] = wi.y;
+        o[2] = wi.z;
+        o[3] = pdf;
+        o[4] = f[0];
+        o[5] = f[1];
+        o[6] = f[2];
+        o[7] = __int_as_float(type);
+    }
+    bsdfn_f(q, m, wo, wi2, flags, mode, f);
+    o[8] = f[0];
+    o[9] = f[1];
+    o[10] = f[2];
+    o[11] = bsdfn_pdf(q, m, wo, wi2, flags);
+}
+
 }  // namespace
+
+hipError_t launch_check_lobes(int64_t n, const float *x, const DevLobes *table, int n_table, float *y, hipStream_t s) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_check_lobes, dim3((unsigned int)((n + 255) / 256)), dim3(256), 0, s, n, x, table, n_table, y);
+    return hipGetLastError();
+}
 
 hipError_t launch_check_bsdf(int64_t n, const float *x, const DevBsdf *table, int n_table, float *y, hipStream_t s) {
     if (n <= 0) return hipSuccess;

@@ -176,6 +176,7 @@ struct SceneState {
     std::vector<int32_t> tri_mat;    // ... and each triangle's index into it (-1: its own matte kd)
     bool has_interface = false;      // ... one of which leads to a BRE_MATERIAL_INTERFACE entry
     bool glossy = false;             // the table holds a type >= BRE_MATERIAL_MATTE: the passes' glossy kernels
+    bool lobed = false;              // ... a type >= BRE_MATERIAL_ROUGH_GLASS: the kernels with the N-lobe BSDF
     // bre_set_media: the table (grid_density pointing into media_grid), the triangles' (inside, outside) pairs
     // interleaved, the delta lights' media, the camera's; media_key: all of it as bytes, the grids for the pointers
     std::vector<bre_medium> media;
@@ -188,7 +189,7 @@ struct SceneState {
 // What upload_scene keeps on the device, and the host bytes it compares the next call's scene against
 struct SceneDevice {
     // geometry: triangles, BVHAccel nodes + primitive order, scene.lights, the delta lights and the materials
-    DevMem tris, nodes, prims, light_tri, light_func, light_cdf, dlights, mats, bsdfs;
+    DevMem tris, nodes, prims, light_tri, light_func, light_cdf, dlights, mats, bsdfs, lobes;
     DevScene head;                     // its fields of the record below
     uint64_t hash = 0;                 // hash of the uploaded triangles, lights and materials (0: none)
     // the uploaded triangles' bytes, the lights', the materials' and the map's: a hash match is confirmed by memcmp
@@ -326,6 +327,8 @@ const char *scene_state_differs(const SceneState &a, const SceneState &b);
 // a plastic, metal or matte record as bre_set_materials_ex checks and keeps it (colours clamped): "", or what
 // is wrong with it
 std::string check_glossy_material(bre_material_ex &m);
+// ... the same for every type from BRE_MATERIAL_MATTE up (bre_device_check kind 14)
+std::string check_lobed_or_glossy_material(bre_material_ex &m);
 // bre_api_build.hip
 bre_status build(bre_ctx *c, int64_t n, const BeamView &in);
 

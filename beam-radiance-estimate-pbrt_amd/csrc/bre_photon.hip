@@ -63,13 +63,18 @@ struct FrameMed : Frame {
 // GL keeps the suspended frames in the block's dynamic LDS, behind the scene traversal stack, instead of a
 // per-thread array: word w of thread t's frame k at [(k * kFrameWords + w) * kPhotonBlock + t].  A path holds at
 // most max_depth frames (each push adds one to depth), so the launch sizes the region to max_depth frames.
+// TIER: 0 = GL false, 1 = GL true, 2 = the table holds a rough glass, uber, translucent or substrate entry
+// (bre_set_materials_ex, types 8 .. 11): every entry from BRE_MATERIAL_MATTE up scatters through the BSDF of any
+// number of lobes (bsdfn_sample with BSDF_ALL in TransportMode::Importance); frames in LDS as for GL.  The walk is one
+// body: k_photons<MODE, MED, GL> runs tiers 0 and 1 under the names and bounds it had, k_photons_tr<MODE, MED> tier 2.
 constexpr int kFrameWords = 19;  // o, d, tmax, p, perr, tri, depth, beta, med
-template <int MODE, bool MED, bool GL>
-__global__ __launch_bounds__(kPhotonBlock, GL ? kGlossyWaves : 6) void k_photons(const DevScene *__restrict__ Sp, int64_t n, uint64_t seq0,
-                                                          int max_depth, float radius, int32_t *__restrict__ counts,
-                                                          const int64_t *__restrict__ offsets, float *__restrict__ bs,
-                                                          float *__restrict__ be, float *__restrict__ br,
-                                                          float *__restrict__ bp, int over) {
+template <int MODE, bool MED, int TIER>
+__device__ __forceinline__ void photon_walk(const DevScene *__restrict__ Sp, int64_t n, uint64_t seq0, int max_depth,
+                                            float radius, int32_t *__restrict__ counts,
+                                            const int64_t *__restrict__ offsets, float *__restrict__ bs,
+                                            float *__restrict__ be, float *__restrict__ br, float *__restrict__ bp,
+                                            int over) {
+    constexpr bool GL = TIER >= 1;
     const int64_t i = (int64_t)blockIdx.x * kPhotonBlock + threadIdx.x;
     if (i >= n) return;
     if (MODE == 1 && over > 0 && counts[i] <= over) return;
@@ -251,11 +256,16 @@ __global__ __launch_bounds__(kPhotonBlock, GL ? kGlossyWaves : 6) void k_photons
                     f3 wil, wiw;
                     float pdf, fr[3];
                     bool world = false;  // GL: wiw is BSDF::Sample_f's own LocalToWorld(wi)
-                    if constexpr (GL) world = q.mat >= kMatTable && S.bsdfs[q.mat - kMatTable].type != 0;
+                    if constexpr (TIER == 2) world = q.mat >= kMatTable && S.lobes[q.mat - kMatTable].type != 0;
+                    else if constexpr (GL) world = q.mat >= kMatTable && S.bsdfs[q.mat - kMatTable].type != 0;
                     if (world) {
                         int type;
                         pdf = 0.f;
-                        bsdf_sample(q, S.bsdfs[q.mat - kMatTable], wo, ux, uy, wiw, pdf, fr, type);
+                        if constexpr (TIER == 2)
+                            bsdfn_sample(q, S.lobes[q.mat - kMatTable], wo, ux, uy, kBsdfAll, kModeImportance, wiw, pdf,
+                                         fr, type);
+                        else
+                            bsdf_sample(q, S.bsdfs[q.mat - kMatTable], wo, ux, uy, wiw, pdf, fr, type);
                     } else if (q.mat >= kMatTable) {
                         int type;
                         specular_sample(S.mats[q.mat - kMatTable], mk(dot3(wo, q.ss), dot3(wo, q.ts), woz), ux,
@@ -321,6 +331,24 @@ __global__ __launch_bounds__(kPhotonBlock, GL ? kGlossyWaves : 6) void k_photons
     if (MODE != 1) counts[i] = cnt;
 }
 
+template <int MODE, bool MED, bool GL>
+__global__ __launch_bounds__(kPhotonBlock, GL ? kGlossyWaves : 6) void k_photons(const DevScene *__restrict__ Sp, int64_t n, uint64_t seq0,
+                                                          int max_depth, float radius, int32_t *__restrict__ counts,
+                                                          const int64_t *__restrict__ offsets, float *__restrict__ bs,
+                                                          float *__restrict__ be, float *__restrict__ br,
+                                                          float *__restrict__ bp, int over) {
+    photon_walk<MODE, MED, GL ? 1 : 0>(Sp, n, seq0, max_depth, radius, counts, offsets, bs, be, br, bp, over);
+}
+
+template <int MODE, bool MED>
+__global__ __launch_bounds__(kPhotonBlock, kGlossyWaves) void k_photons_tr(const DevScene *__restrict__ Sp, int64_t n, uint64_t seq0,
+                                                          int max_depth, float radius, int32_t *__restrict__ counts,
+                                                          const int64_t *__restrict__ offsets, float *__restrict__ bs,
+                                                          float *__restrict__ be, float *__restrict__ br,
+                                                          float *__restrict__ bp, int over) {
+    photon_walk<MODE, MED, 2>(Sp, n, seq0, max_depth, radius, counts, offsets, bs, be, br, bp, over);
+}
+
 // The single-trace form's copy: photon i's first min(count, cap) beams from its slots to its offsets.
 // Each wave copies the beams of its 64 photons as one run: lane j takes the wave's j-th beam (owner by
 // a search of the wave's prefix sums in LDS), so the writes of consecutive lanes are consecutive and a
@@ -380,15 +408,21 @@ size_t photon_lds_bytes(int stack_depth, int max_depth, bool glossy) {
 
 hipError_t launch_photons(const DevScene *scene, int stack_depth, int64_t n, uint64_t seq0, int max_depth,
                           float radius, int32_t *counts, const int64_t *offsets, const BeamOut &out, int mode,
-                          int over, bool media, bool glossy, hipStream_t s) {
+                          int over, bool media, int tier, hipStream_t s) {
     if (n == 0) return hipSuccess;
-    // the glossy kernels keep their frames in LDS too (the caller has checked the device's room: photon_lds_bytes)
-    const size_t lds = photon_lds_bytes(stack_depth, max_depth, glossy);
+    // tiers 1 and 2 keep their frames in LDS too (the caller has checked the device's room: photon_lds_bytes)
+    const size_t lds = photon_lds_bytes(stack_depth, max_depth, tier >= 1);
     const auto go = [&](auto kernel, int ov) {
         hipLaunchKernelGGL(kernel, dim3(grid_of(n)), dim3(kPhotonBlock), lds, s, scene, n, seq0, max_depth, radius,
                            counts, offsets, out.start, out.end, out.radius, out.power, ov);
     };
-    if (glossy) {
+    if (tier == 2) {
+        if (mode == 1) media ? go(k_photons_tr<1, true>, over) : go(k_photons_tr<1, false>, over);
+        else if (mode == 2) media ? go(k_photons_tr<2, true>, over) : go(k_photons_tr<2, false>, over);
+        else media ? go(k_photons_tr<0, true>, 0) : go(k_photons_tr<0, false>, 0);
+        return hipGetLastError();
+    }
+    if (tier == 1) {
         if (mode == 1) media ? go(k_photons<1, true, true>, over) : go(k_photons<1, false, true>, over);
         else if (mode == 2) media ? go(k_photons<2, true, true>, over) : go(k_photons<2, false, true>, over);
         else media ? go(k_photons<0, true, true>, 0) : go(k_photons<0, false, true>, 0);

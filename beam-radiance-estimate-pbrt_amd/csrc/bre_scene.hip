@@ -100,7 +100,7 @@ static void world_bounding_sphere(const SceneNode &root, f3 *center, float *radi
 // matte.cpp:45-62) on the record's constants (the setter has clamped Kd and Ks and checked the roughnesses)
 DevBsdf make_bsdf(const bre_material_ex &m) {
     DevBsdf b{};
-    if (m.type < BRE_MATERIAL_MATTE) return b;
+    if (m.type < BRE_MATERIAL_MATTE || m.type > BRE_MATERIAL_METAL) return b;
     b.type = m.type;
     b.ax = b.ay = 1.f;
     if (m.type == BRE_MATERIAL_MATTE) {
@@ -144,6 +144,110 @@ DevBsdf make_bsdf(const bre_material_ex &m) {
     return b;
 }
 
+// The same three materials as a list of lobes, and GlassMaterial with roughness (glass.cpp:45-92), UberMaterial
+// (uber.cpp:45-101), TranslucentMaterial (translucent.cpp:45-80) and SubstrateMaterial (substrate.cpp:45-65): the
+// BxDFs in the order added, each colour the product the reference forms (op * Kd, r * ks, ...), in its operations.
+// The setter has clamped the colours and checked the roughnesses.
+DevLobes make_lobes(const bre_material_ex &m) {
+    DevLobes b{};
+    if (m.type < BRE_MATERIAL_MATTE || m.type == 7 || m.type > BRE_MATERIAL_SUBSTRATE) return b;
+    b.type = m.type;
+    const auto add = [&](int kind, int type, const float c[3], float ax, float ay, float etaA, float etaB) -> DevLobe & {
+        DevLobe &L = b.lobe[b.n++];
+        L.kind = kind;
+        L.type = type;
+        for (int k = 0; k < 3; ++k) L.c[k] = c[k];
+        L.ax = ax;
+        L.ay = ay;
+        L.etaA = etaA;
+        L.etaB = etaB;
+        if (!(type & kBsdfSpecular)) ++b.n_nonspec;
+        return L;
+    };
+    const auto mul3 = [](const float a[3], const float x[3], float out[3]) {
+        for (int k = 0; k < 3; ++k) out[k] = a[k] * x[k];
+    };
+    constexpr int R = kBsdfReflection, T = kBsdfTransmission;
+    if (m.type <= BRE_MATERIAL_METAL) {
+        const DevBsdf o = make_bsdf(m);
+        if (o.lobes & kLobeDiffuse)
+            add(o.oren ? kLobeOren : kLobeLambertR, R | kBsdfDiffuse, o.kd, o.oren ? o.A : 1.f, o.oren ? o.B : 1.f, 1.f, 1.f);
+        if (o.lobes & kLobeMicro) {
+            DevLobe &L = add(o.conductor ? kLobeMicroRC : kLobeMicroR, R | kBsdfGlossy, o.ks, o.ax, o.ay, 1.5f, 1.f);
+            for (int k = 0; k < 3; ++k) {
+                L.s[k] = o.ceta[k];
+                L.t[k] = o.ck[k];
+            }
+        }
+        return b;
+    }
+    if (m.type == BRE_MATERIAL_ROUGH_GLASS) {
+        if (black3(m.kr) && black3(m.kt)) return b;
+        float u = m.uroughness, v = m.vroughness;
+        if (m.remap) {
+            u = roughness_to_alpha(u);
+            v = roughness_to_alpha(v);
+        }
+        if (!black3(m.kr)) add(kLobeMicroR, R | kBsdfGlossy, m.kr, u, v, 1.f, m.eta);
+        if (!black3(m.kt)) add(kLobeMicroT, T | kBsdfGlossy, m.kt, u, v, 1.f, m.eta);
+        return b;
+    }
+    if (m.type == BRE_MATERIAL_UBER) {
+        const float e = m.eta;
+        float t[3], c[3];
+        for (int k = 0; k < 3; ++k) t[k] = clampf_ref(-m.opacity[k] + 1.f, 0.f, kMaxFloat);  // (-op + Spectrum(1.f)).Clamp()
+        if (!black3(t)) add(kLobeSpecT, T | kBsdfSpecular, t, 1.f, 1.f, 1.f, 1.f);
+        mul3(m.opacity, m.kd, c);
+        if (!black3(c)) add(kLobeLambertR, R | kBsdfDiffuse, c, 1.f, 1.f, 1.f, 1.f);
+        mul3(m.opacity, m.ks, c);
+        if (!black3(c)) {
+            float u = m.uroughness != 0 ? m.uroughness : m.roughness;
+            float v = m.vroughness != 0 ? m.vroughness : u;
+            if (m.remap) {
+                u = roughness_to_alpha(u);
+                v = roughness_to_alpha(v);
+            }
+            add(kLobeMicroR, R | kBsdfGlossy, c, u, v, 1.f, e);
+        }
+        mul3(m.opacity, m.kr, c);
+        if (!black3(c)) add(kLobeSpecR, R | kBsdfSpecular, c, 1.f, 1.f, 1.f, e);
+        mul3(m.opacity, m.kt, c);
+        if (!black3(c)) add(kLobeSpecT, T | kBsdfSpecular, c, 1.f, 1.f, 1.f, e);
+        return b;
+    }
+    if (m.type == BRE_MATERIAL_TRANSLUCENT) {
+        const float *r = m.kr, *t = m.kt;  // "reflect", "transmit"
+        if (black3(r) && black3(t)) return b;
+        float c[3];
+        if (!black3(m.kd)) {
+            mul3(r, m.kd, c);
+            if (!black3(r)) add(kLobeLambertR, R | kBsdfDiffuse, c, 1.f, 1.f, 1.f, 1.f);
+            mul3(t, m.kd, c);
+            if (!black3(t)) add(kLobeLambertT, T | kBsdfDiffuse, c, 1.f, 1.f, 1.f, 1.f);
+        }
+        if (!black3(m.ks)) {
+            float rough = m.roughness;
+            if (m.remap) rough = roughness_to_alpha(rough);
+            mul3(r, m.ks, c);
+            if (!black3(r)) add(kLobeMicroR, R | kBsdfGlossy, c, rough, rough, 1.f, 1.5f);
+            mul3(t, m.ks, c);
+            if (!black3(t)) add(kLobeMicroT, T | kBsdfGlossy, c, rough, rough, 1.f, 1.5f);
+        }
+        return b;
+    }
+    // substrate
+    if (!black3(m.kd) || !black3(m.ks)) {
+        float u = m.uroughness, v = m.vroughness;
+        if (m.remap) {
+            u = roughness_to_alpha(u);
+            v = roughness_to_alpha(v);
+        }
+        DevLobe &L = add(kLobeBlend, R | kBsdfGlossy, m.kd, u, v, 1.f, 1.f);
+        for (int k = 0; k < 3; ++k) L.s[k] = m.ks[k];
+    }
+    return b;
+}
+
 void prepare_geometry(const bre_scene *s, HostScene *out, const bre_light *lights, int n_lights,
                       const MaterialMap &mm) {
     DevScene &d = out->head;
@@ -152,6 +256,10 @@ void prepare_geometry(const bre_scene *s, HostScene *out, const bre_light *light
     // the plastic / metal / matte ones
     out->mats.resize((size_t)mm.n_mats);
     out->bsdfs.resize((size_t)mm.n_mats);
+    // the lobe lists only where a kernel reads them: a table with a rough glass, uber, translucent or substrate entry
+    bool lobed = false;
+    for (int k = 0; k < mm.n_mats; ++k) lobed = lobed || mm.mats[k].type >= BRE_MATERIAL_ROUGH_GLASS;
+    out->lobes.assign(lobed ? (size_t)mm.n_mats : 0, DevLobes{});
     for (int k = 0; k < mm.n_mats; ++k) {
         const bre_material_ex &m = mm.mats[k];
         bre_material &n = out->mats[(size_t)k];
@@ -162,6 +270,7 @@ void prepare_geometry(const bre_scene *s, HostScene *out, const bre_light *light
         }
         n.eta = m.eta;
         out->bsdfs[(size_t)k] = make_bsdf(m);
+        if (lobed) out->lobes[(size_t)k] = make_lobes(m);
     }
     const bre_triangle *tri = scene_triangles(s);
     out->tris.resize((size_t)s->n_triangles);
@@ -213,7 +322,9 @@ void prepare_geometry(const bre_scene *s, HostScene *out, const bre_light *light
             const bool none = black3(m.kr) && (m.type == BRE_MATERIAL_MIRROR || black3(m.kt));
             T.mat = none ? kMatNone : kMatTable + mm.tri_mat[i];
             if (m.type == BRE_MATERIAL_INTERFACE) T.mat = kMatInterface;  // GetMaterial() == nullptr: no BSDF
-            if (m.type >= BRE_MATERIAL_MATTE) {
+            if (m.type >= BRE_MATERIAL_ROUGH_GLASS) {
+                T.mat = out->lobes[(size_t)mm.tri_mat[i]].n == 0 ? kMatNone : kMatTable + mm.tri_mat[i];
+            } else if (m.type >= BRE_MATERIAL_MATTE) {
                 const DevBsdf &b = out->bsdfs[(size_t)mm.tri_mat[i]];
                 T.mat = b.lobes == 0 ? kMatNone : kMatTable + mm.tri_mat[i];
                 if (b.type == BRE_MATERIAL_MATTE && !b.oren) {

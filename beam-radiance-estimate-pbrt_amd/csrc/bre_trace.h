@@ -188,6 +188,40 @@ struct DevBsdf {
     int conductor;        // the microfacet lobe's Fresnel term is the conductor's
 };
 
+// The BSDF of any number of lobes (a table that holds a rough glass, uber, translucent or substrate entry): every
+// entry from BRE_MATERIAL_MATTE up as its ComputeScatteringFunctions leaves the BSDF (make_lobes), the BxDFs in the
+// order added.  BSDF::eta is read nowhere in photonbeam.cpp and has no place here.  The kernels read a record
+// where it lies in device memory (a lobe is indexed at run time: a copy in registers would go to scratch).
+constexpr int kBsdfAll = 31;                             // BSDF_ALL, reflection.h:128-129
+constexpr int kBsdfNonSpecular = 31 & ~kBsdfSpecular;    // EstimateDirect's BSDF_ALL & ~BSDF_SPECULAR
+constexpr int kMaxLobes = 5;                             // uber.cpp adds at most five
+enum LobeKind : int {
+    kLobeLambertR = 1,  // LambertianReflection(c)
+    kLobeLambertT,      // LambertianTransmission(c)
+    kLobeOren,          // OrenNayar(c), A = ax, B = ay
+    kLobeMicroR,        // MicrofacetReflection(c, TR(ax, ay), FresnelDielectric(etaA, etaB))
+    kLobeMicroRC,       // MicrofacetReflection(c, TR(ax, ay), FresnelConductor(1, s, t))
+    kLobeMicroT,        // MicrofacetTransmission(c, TR(ax, ay), etaA, etaB, mode)
+    kLobeSpecR,         // SpecularReflection(c, FresnelDielectric(etaA, etaB))
+    kLobeSpecT,         // SpecularTransmission(c, etaA, etaB, mode)
+    kLobeBlend          // FresnelBlend(Rd = c, Rs = s, TR(ax, ay))
+};
+struct DevLobe {
+    int kind;         // LobeKind
+    int type;         // its BxDFType bits
+    float c[3];       // R or T: the product (op * Kd, r * ks, ...) formed on the host in the reference's operations
+    float s[3], t[3]; // kLobeBlend: Rs; kLobeMicroRC: the conductor's eta and k
+    float ax, ay;     // the distribution's alphas (RoughnessToAlpha applied on the host); kLobeOren: A, B
+    float etaA, etaB;
+};
+struct DevLobes {
+    int type;         // BRE_MATERIAL_MATTE .. _METAL, _ROUGH_GLASS .. _SUBSTRATE; 0: a mirror, glass or interface
+    int n;            // BxDFs added
+    int n_nonspec;    // NumComponents(BSDF_ALL & ~BSDF_SPECULAR)
+    int pad;
+    DevLobe lobe[kMaxLobes];
+};
+
 // One node of the scene's bounding volume hierarchy: the reference's BVHAccel LinearBVHNode
 // (src/accelerators/bvh.cpp, 32 B, depth-first order: an interior node's first child follows it).
 struct SceneNode {
@@ -253,6 +287,7 @@ struct DevScene {
     const int32_t *light_med;  // one per entry of dlights
     int n_media, cam_med;
     const DevBsdf *bsdfs;  // beside mats, one per table entry (bre_set_materials_ex); last: the layout before it stays
+    const DevLobes *lobes; // beside bsdfs, one per table entry; read only by the kernels of a table with a type >= 8
 };
 
 // Host side of the scene: everything prepare_geometry derives, in host memory; the context uploads
@@ -267,6 +302,7 @@ struct HostScene {
     std::vector<float> light_func, light_cdf;
     std::vector<bre_material> mats;
     std::vector<DevBsdf> bsdfs;
+    std::vector<DevLobes> lobes;
     int depth = 0;  // deepest node of the BVH (root = 1)
 };
 
@@ -288,6 +324,9 @@ DLight prepare_light(const bre_light &l);
 // a table entry as its material leaves the BSDF (plastic.cpp:45-70, metal.cpp:59-80, matte.cpp:45-62); type 0 for
 // a mirror, glass or interface
 DevBsdf make_bsdf(const bre_material_ex &m);
+// a table entry as its material leaves the BSDF, any number of lobes: the above for types 4 .. 6, and glass.cpp:45-92,
+// uber.cpp:45-101, translucent.cpp:45-80, substrate.cpp:45-65 for types 8 .. 11; type 0 below BRE_MATERIAL_MATTE
+DevLobes make_lobes(const bre_material_ex &m);
 // a medium as its constructor leaves it: sigma_t = sigma_a + sigma_s per channel; for a grid, channel 0 of it,
 // 1 / max_density and `d_density`, the device copy of the grid (the grid arguments are not read otherwise)
 DevMedium make_medium(int type, const float sigma_a[3], const float sigma_s[3], float g, const int32_t grid_n[3],
@@ -1059,6 +1098,274 @@ BRE_TD bool bsdf_sample(const PTri &q, const DevBsdf &m, f3 wo_w, float u0, floa
     return true;
 }
 
+// ---- the BSDF of any number of lobes, with BxDFType flags and a TransportMode (DevLobes) ----
+// Refract, reflection.h:96-108 (n a Normal3f); false on total internal reflection
+BRE_TD bool refract(f3 wi, f3 n, float eta, f3 &wt) {
+    const float cos_i = dot3(n, wi);
+    const float sin2_i = smax(0.f, 1 - cos_i * cos_i);
+    const float sin2_t = eta * eta * sin2_i;
+    if (sin2_t >= 1) return false;
+    const float cos_t = sqrtf(1 - sin2_t);
+    const float k = eta * cos_i - cos_t;
+    wt = mk(eta * -wi.x + k * n.x, eta * -wi.y + k * n.y, eta * -wi.z + k * n.z);
+    return true;
+}
+BRE_TD float pow5(float v) { return (v * v) * (v * v) * v; }
+
+// BxDF::f of one lobe, wo and wi in the shading frame: LambertianReflection / Transmission (reflection.cpp:178-190),
+// OrenNayar (:197-219), MicrofacetReflection (:226-236), MicrofacetTransmission (:244-266), FresnelBlend (:285-298
+// with SchlickFresnel, reflection.h:488-491); 0 for the specular lobes (reflection.h:313-315, 338-340)
+BRE_TD void loben_f(const DevLobe &L, f3 wo, f3 wi, int mode, float f[3]) {
+    f[0] = f[1] = f[2] = 0.f;
+    const int kind = L.kind;
+    if (kind == kLobeLambertR || kind == kLobeLambertT) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) f[c] = L.c[c] * kInvPi;
+        return;
+    }
+    if (kind == kLobeOren) {
+        const float sin_i = sin_theta(wi), sin_o = sin_theta(wo);
+        float max_cos = 0;
+        if ((double)sin_i > 1e-4 && (double)sin_o > 1e-4) {
+            const float spi = sin_phi(wi), cpi = cos_phi(wi);
+            const float spo = sin_phi(wo), cpo = cos_phi(wo);
+            const float d_cos = cpi * cpo + spi * spo;
+            max_cos = smax(0.f, d_cos);
+        }
+        float sin_alpha, tan_beta;
+        if (fabsf(wi.z) > fabsf(wo.z)) {
+            sin_alpha = sin_o;
+            tan_beta = sin_i / fabsf(wi.z);
+        } else {
+            sin_alpha = sin_i;
+            tan_beta = sin_o / fabsf(wo.z);
+        }
+        const float s = L.ax + L.ay * max_cos * sin_alpha * tan_beta;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) f[c] = L.c[c] * kInvPi * s;
+        return;
+    }
+    if (kind == kLobeMicroR || kind == kLobeMicroRC) {
+        const float cos_o = fabsf(wo.z), cos_i = fabsf(wi.z);
+        f3 wh = add3(wi, wo);
+        if (cos_i == 0 || cos_o == 0) return;
+        if (wh.x == 0 && wh.y == 0 && wh.z == 0) return;
+        wh = normalize3(wh);
+        const float ci = dot3(wi, wh);
+        const float D = tr_D(L.ax, L.ay, wh), G = tr_G(L.ax, L.ay, wo, wi);
+        const float den = 4 * cos_i * cos_o;
+        if (kind == kLobeMicroRC) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) f[c] = L.c[c] * D * G * fr_conductor(fabsf(ci), L.s[c], L.t[c]) / den;
+        } else {
+            const float F = fr_dielectric(ci, L.etaA, L.etaB);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) f[c] = L.c[c] * D * G * F / den;
+        }
+        return;
+    }
+    if (kind == kLobeMicroT) {
+        if (wo.z * wi.z > 0) return;  // transmission only
+        const float cos_o = wo.z, cos_i = wi.z;
+        if (cos_i == 0 || cos_o == 0) return;
+        const float eta = wo.z > 0 ? (L.etaB / L.etaA) : (L.etaA / L.etaB);
+        f3 wh = normalize3(add3(wo, scale3(wi, eta)));
+        if (wh.z < 0) wh = neg3(wh);
+        const float F = fr_dielectric(dot3(wo, wh), L.etaA, L.etaB);
+        const float sd = dot3(wo, wh) + eta * dot3(wi, wh);
+        const float factor = (mode == kModeRadiance) ? (1 / eta) : 1.f;
+        const float v = fabsf(tr_D(L.ax, L.ay, wh) * tr_G(L.ax, L.ay, wo, wi) * eta * eta * fabsf(dot3(wi, wh)) *
+                              fabsf(dot3(wo, wh)) * factor * factor / (cos_i * cos_o * sd * sd));
+#pragma unroll
+        for (int c = 0; c < 3; ++c) f[c] = (1.f - F) * L.c[c] * v;
+        return;
+    }
+    if (kind == kLobeBlend) {
+        const float a = 1 - pow5(1 - .5f * fabsf(wi.z)), b = 1 - pow5(1 - .5f * fabsf(wo.z));
+        f3 wh = add3(wi, wo);
+        if (wh.x == 0 && wh.y == 0 && wh.z == 0) return;
+        wh = normalize3(wh);
+        const float sc = tr_D(L.ax, L.ay, wh) / (4 * fabsf(dot3(wi, wh)) * smax(fabsf(wi.z), fabsf(wo.z)));
+        const float p5 = pow5(1 - dot3(wi, wh));
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float diffuse = (28.f / (23.f * kPi)) * L.c[c] * (1.f - L.s[c]) * a * b;
+            const float specular = sc * (L.s[c] + p5 * (1.f - L.s[c]));
+            f[c] = diffuse + specular;
+        }
+    }
+}
+// BxDF::Pdf (reflection.cpp:387-389), LambertianTransmission's (:400-403), MicrofacetReflection's (:419-423),
+// MicrofacetTransmission's (:436-448), FresnelBlend's (:470-475); 0 for the specular lobes
+BRE_TD float loben_pdf(const DevLobe &L, f3 wo, f3 wi) {
+    const int kind = L.kind;
+    const bool same = wo.z * wi.z > 0;
+    if (kind == kLobeLambertR || kind == kLobeOren) return same ? fabsf(wi.z) * kInvPi : 0.f;
+    if (kind == kLobeLambertT) return !same ? fabsf(wi.z) * kInvPi : 0.f;
+    if (kind == kLobeMicroR || kind == kLobeMicroRC) {
+        if (!same) return 0.f;
+        const f3 wh = normalize3(add3(wo, wi));
+        return tr_pdf(L.ax, L.ay, wo, wh) / (4 * dot3(wo, wh));
+    }
+    if (kind == kLobeMicroT) {
+        if (same) return 0.f;
+        const float eta = wo.z > 0 ? (L.etaB / L.etaA) : (L.etaA / L.etaB);
+        const f3 wh = normalize3(add3(wo, scale3(wi, eta)));
+        const float sd = dot3(wo, wh) + eta * dot3(wi, wh);
+        const float dwh_dwi = fabsf((eta * eta * dot3(wi, wh)) / (sd * sd));
+        return tr_pdf(L.ax, L.ay, wo, wh) * dwh_dwi;
+    }
+    if (kind == kLobeBlend) {
+        if (!same) return 0.f;
+        const f3 wh = normalize3(add3(wo, wi));
+        const float pdf_wh = tr_pdf(L.ax, L.ay, wo, wh);
+        return .5f * (fabsf(wi.z) * kInvPi + pdf_wh / (4 * dot3(wo, wh)));
+    }
+    return 0.f;
+}
+// The lobe's Sample_f (reflection.cpp:136-166, 378-385, 391-398, 405-417, 425-434, 450-468); pdf arrives as 0 and
+// stays 0 where the lobe returns early, f then being what the caller put there; wo.z != 0
+BRE_TD void loben_sample(const DevLobe &L, f3 wo, float u0, float u1, int mode, f3 &wi, float &pdf, float f[3]) {
+    const int kind = L.kind;
+    if (kind == kLobeSpecR) {
+        wi = mk(-wo.x, -wo.y, wo.z);
+        pdf = 1.f;
+        const float F = fr_dielectric(wi.z, L.etaA, L.etaB);
+        const float ac = fabsf(wi.z);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) f[c] = F * L.c[c] / ac;
+        return;
+    }
+    if (kind == kLobeSpecT) {
+        const bool entering = wo.z > 0;
+        const float eta_i = entering ? L.etaA : L.etaB, eta_t = entering ? L.etaB : L.etaA;
+        // Faceforward(Normal3f(0, 0, 1), wo)
+        const f3 n = (wo.z < 0.f) ? mk(-0.f, -0.f, -1.f) : mk(0.f, 0.f, 1.f);
+        if (!refract(wo, n, eta_i / eta_t, wi)) return;
+        pdf = 1.f;
+        const float F = fr_dielectric(wi.z, L.etaA, L.etaB);
+        const float ac = fabsf(wi.z);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            float ft = L.c[c] * (1.f - F);
+            if (mode == kModeRadiance) ft *= (eta_i * eta_i) / (eta_t * eta_t);
+            f[c] = ft / ac;
+        }
+        return;
+    }
+    if (kind == kLobeLambertR || kind == kLobeOren || kind == kLobeLambertT) {
+        wi = cosine_hemisphere(u0, u1);
+        if (kind == kLobeLambertT ? wo.z > 0 : wo.z < 0) wi.z *= -1;
+    } else if (kind == kLobeMicroT) {
+        const f3 wh = tr_sample_wh(L.ax, L.ay, wo, u0, u1);
+        const float eta = wo.z > 0 ? (L.etaA / L.etaB) : (L.etaB / L.etaA);
+        if (!refract(wo, wh, eta, wi)) return;
+    } else {
+        if (kind == kLobeBlend) {
+            if (u0 < .5f) {
+                wi = cosine_hemisphere(smin(2 * u0, kOneMinusEps), u1);
+                if (wo.z < 0) wi.z *= -1;
+                pdf = loben_pdf(L, wo, wi);
+                loben_f(L, wo, wi, mode, f);
+                return;
+            }
+            u0 = smin(2 * (u0 - .5f), kOneMinusEps);
+        }
+        const f3 wh = tr_sample_wh(L.ax, L.ay, wo, u0, u1);
+        wi = add3(neg3(wo), scale3(wh, 2 * dot3(wo, wh)));  // Reflect, reflection.h:92-94
+        if (!(wo.z * wi.z > 0)) return;
+        if (kind != kLobeBlend) {  // MicrofacetReflection: the pdf of the sampled wh, not of Normalize(wo + wi)
+            pdf = tr_pdf(L.ax, L.ay, wo, wh) / (4 * dot3(wo, wh));
+            loben_f(L, wo, wi, mode, f);
+            return;
+        }
+    }
+    pdf = loben_pdf(L, wo, wi);
+    loben_f(L, wo, wi, mode, f);
+}
+
+BRE_TD bool lobe_matches(const DevLobe &L, int flags) { return (L.type & flags) == L.type; }  // BxDF::MatchesFlags
+// BSDF::f, reflection.cpp:670-683: the matching lobes on the side of the geometric normal that wi lies on
+BRE_TD void bsdfn_f(const PTri &q, const DevLobes &m, f3 wo_w, f3 wi_w, int flags, int mode, float f[3]) {
+    f[0] = f[1] = f[2] = 0.f;
+    const f3 wi = to_local(q, wi_w), wo = to_local(q, wo_w);
+    if (wo.z == 0) return;
+    const bool reflect = dot3(wi_w, q.n) * dot3(wo_w, q.n) > 0;
+    for (int i = 0; i < m.n; ++i) {
+        const DevLobe &L = m.lobe[i];
+        if (!lobe_matches(L, flags) || !(L.type & (reflect ? kBsdfReflection : kBsdfTransmission))) continue;
+        float fl[3];
+        loben_f(L, wo, wi, mode, fl);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) f[c] = f[c] + fl[c];
+    }
+}
+// BSDF::Pdf, reflection.cpp:770-785
+BRE_TD float bsdfn_pdf(const PTri &q, const DevLobes &m, f3 wo_w, f3 wi_w, int flags) {
+    if (m.n == 0) return 0.f;
+    const f3 wo = to_local(q, wo_w), wi = to_local(q, wi_w);
+    if (wo.z == 0) return 0.f;
+    float pdf = 0.f;
+    int n = 0;
+    for (int i = 0; i < m.n; ++i) {
+        if (!lobe_matches(m.lobe[i], flags)) continue;
+        ++n;
+        pdf += loben_pdf(m.lobe[i], wo, wi);
+    }
+    return n > 0 ? pdf / (float)n : 0.f;
+}
+// BSDF::Sample_f, reflection.cpp:703-768: NumComponents(flags), the component by floor(u[0] * n) over the matching
+// lobes, u[0] remapped, the lobe's Sample_f; unless that lobe is specular, the other matching lobes' Pdf added and f
+// taken again over all of them (:749-764).  Returns false where Sample_f returns 0 before f is known (no matching
+// lobe, wo.z == 0 with pdf untouched, pdf == 0); type is then 0.
+BRE_TD bool bsdfn_sample(const PTri &q, const DevLobes &m, f3 wo_w, float u0, float u1, int flags, int mode, f3 &wi_w,
+                         float &pdf, float f[3], int &type) {
+    f[0] = f[1] = f[2] = 0.f;
+    type = 0;
+    int n = 0;
+    for (int i = 0; i < m.n; ++i) n += lobe_matches(m.lobe[i], flags) ? 1 : 0;
+    if (n == 0) {
+        pdf = 0.f;
+        return false;
+    }
+    const int fl = (int)floorf(u0 * (float)n);
+    const int comp = fl < n - 1 ? fl : n - 1;
+    int at = 0;
+    for (int i = 0, count = comp; i < m.n; ++i)
+        if (lobe_matches(m.lobe[i], flags) && count-- == 0) {
+            at = i;
+            break;
+        }
+    const DevLobe &L = m.lobe[at];
+    const float ur = smin(u0 * (float)n - (float)comp, kOneMinusEps);
+    const f3 wo = to_local(q, wo_w);
+    if (wo.z == 0) return false;
+    pdf = 0.f;
+    f3 wi = mk(0.f, 0.f, 0.f);
+    loben_sample(L, wo, ur, u1, mode, wi, pdf, f);
+    if (pdf == 0) return false;  // f is whatever the lobe left: the callers read it only behind pdf != 0
+    type = L.type;
+    wi_w = to_world(q, wi);
+    const bool mix = !(L.type & kBsdfSpecular) && n > 1;
+    if (mix)
+        for (int i = 0; i < m.n; ++i)
+            if (i != at && lobe_matches(m.lobe[i], flags)) pdf += loben_pdf(m.lobe[i], wo, wi);
+    if (n > 1) pdf /= (float)n;
+    if (mix) {
+        const bool reflect = dot3(wi_w, q.n) * dot3(wo_w, q.n) > 0;
+        f[0] = f[1] = f[2] = 0.f;
+        for (int i = 0; i < m.n; ++i) {
+            const DevLobe &K = m.lobe[i];
+            if (!lobe_matches(K, flags) || !(K.type & (reflect ? kBsdfReflection : kBsdfTransmission))) continue;
+            float fl2[3];
+            loben_f(K, wo, wi, mode, fl2);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) f[c] = f[c] + fl2[c];
+        }
+    }
+    return true;
+}
+
 // ---- camera pass (bre_camera.hip) ----
 constexpr int kHaltonDims = 1000;  // HaltonSampler's PrimeTableSize = AwesomeSampler's limit (photonbeam.cpp:460)
 
@@ -1083,12 +1390,12 @@ struct CamSlots {
 void prepare_camera(const bre_scene *s, int width, int height, DevCamera *c, std::vector<uint16_t> *perms);
 int64_t camera_slots(int width, int height);
 // `planes`: the slot planes of `s` (max_depth, plus the segment budget with media and an interface triangle);
-// `media`: the context holds media (the kernel that carries a medium per ray); `glossy`: its table holds a
-// plastic, metal or matte entry (the kernel with the general BSDF)
+// `media`: the context holds media (the kernel that carries a medium per ray); `tier`: as for launch_photons (1 also
+// where the context holds a distant light)
 hipError_t launch_camera(const DevScene *scene, int stack_depth, const DevCamera *cam, const uint16_t *perms, int width,
                          int height, int iteration, int max_depth, int render_surfaces, int render_media,
                          const CamSlots &s, float *surface, unsigned int *flags, int shard_rank, int shard_count,
-                         int shard_block, int classes, int planes, bool media, bool glossy, hipStream_t stream);
+                         int shard_block, int classes, int planes, bool media, int tier, hipStream_t stream);
 constexpr unsigned int kCamFlagBudget = 1u;  // k_camera's flag word: a path overran its segment budget
 size_t camera_scan_temp_bytes(int64_t n);
 hipError_t launch_camera_scan(void *tmp, size_t tmp_bytes, const CamSlots &s, int64_t nslots, int max_depth,
@@ -1100,6 +1407,8 @@ hipError_t launch_camera_compact(const CamSlots &s, int64_t nslots, int max_dept
 hipError_t launch_check_specular(int64_t n, const float *x, float *y, hipStream_t s);
 // kind 13 (bre_check.hip): bsdf_sample, bsdf_f and bsdf_pdf on n records of 9 floats against `table`, 12 words out each
 hipError_t launch_check_bsdf(int64_t n, const float *x, const DevBsdf *table, int n_table, float *y, hipStream_t s);
+// kind 14 (bre_check.hip): bsdfn_sample, bsdfn_f and bsdfn_pdf on n records of 11 floats against `table`, 12 words out
+hipError_t launch_check_lobes(int64_t n, const float *x, const DevLobes *table, int n_table, float *y, hipStream_t s);
 
 // dynamic LDS of a photon / camera launch: the scene traversal stack of every thread of a block
 inline size_t scene_stack_bytes(int stack_depth, int block) {
@@ -1114,11 +1423,12 @@ constexpr int kGlossyWaves = 2;
 size_t photon_lds_bytes(int stack_depth, int max_depth, bool glossy);
 // mode 0: count beams per photon; 1: write them at offsets (over > 0: only photons with more than `over`
 // beams); 2: write the first `over` beams to per-photon slots and count them all (single-trace form)
-// `media`: the context holds media (the kernels that carry a medium per ray); `glossy`: its table holds a plastic,
-// metal or matte entry (the kernels with the general BSDF)
+// `media`: the context holds media (the kernels that carry a medium per ray); `tier`: 1 where its table holds a
+// plastic, metal or matte entry (the kernels with the two-lobe BSDF), 2 where it holds a rough glass, uber,
+// translucent or substrate entry (the kernels with the BSDF of any number of lobes), else 0
 hipError_t launch_photons(const DevScene *scene, int stack_depth, int64_t n, uint64_t seq0, int max_depth,
                           float radius, int32_t *counts, const int64_t *offsets, const BeamOut &out, int mode,
-                          int over, bool media, bool glossy, hipStream_t s);
+                          int over, bool media, int tier, hipStream_t s);
 // the single-trace form's copy of each photon's slots to its offsets
 hipError_t launch_photon_slots(int64_t n, int cap, const int32_t *counts, const int64_t *offsets,
                                const BeamView &slots, const BeamOut &out, hipStream_t s);

@@ -20,19 +20,20 @@ static bre_status finish_parse(bre_pbrt *p, bool ok) {
 
 extern "C" {
 
-static_assert(BRE_PBRT_MEDIA == kParseMedia && BRE_PBRT_LIGHTS == kParseLights, "the ABI's flags are the parser's");
+static_assert(BRE_PBRT_MEDIA == kParseMedia && BRE_PBRT_LIGHTS == kParseLights && BRE_PBRT_MATERIALS == kParseMaterials,
+              "the ABI's flags are the parser's");
 
 bre_status bre_pbrt_parse_file_ex(const char *path, int32_t flags, bre_pbrt **out) {
     if (!out) return BRE_ERR_INVALID_ARG;
     *out = new bre_pbrt();
-    if (!path || (flags & ~(BRE_PBRT_MEDIA | BRE_PBRT_LIGHTS))) return BRE_ERR_INVALID_ARG;
+    if (!path || (flags & ~(BRE_PBRT_MEDIA | BRE_PBRT_LIGHTS | BRE_PBRT_MATERIALS))) return BRE_ERR_INVALID_ARG;
     return finish_parse(*out, ParsePbrtFile(path, &(*out)->scene, flags));
 }
 
 bre_status bre_pbrt_parse_string_ex(const char *text, int32_t flags, bre_pbrt **out) {
     if (!out) return BRE_ERR_INVALID_ARG;
     *out = new bre_pbrt();
-    if (!text || (flags & ~(BRE_PBRT_MEDIA | BRE_PBRT_LIGHTS))) return BRE_ERR_INVALID_ARG;
+    if (!text || (flags & ~(BRE_PBRT_MEDIA | BRE_PBRT_LIGHTS | BRE_PBRT_MATERIALS))) return BRE_ERR_INVALID_ARG;
     return finish_parse(*out, ParsePbrtString(text, &(*out)->scene, flags));
 }
 

@@ -16,7 +16,7 @@
 #include "../../include/bre_pbrt.h"
 
 static const char *kUsage =
-    "usage: bre_pbrt [--quick] [--media] [--lights] [--outfile file.pfm] [--device n | --devices a,b,...] scene.pbrt\n";
+    "usage: bre_pbrt [--quick] [--media] [--lights] [--materials] [--outfile file.pfm] [--device n | --devices a,b,...] scene.pbrt\n";
 
 // "0,1,2,3" -> ordinals; empty when the text is not a comma-separated list of non-negative integers
 static std::vector<int32_t> ParseDevices(const char *text) {
@@ -39,6 +39,7 @@ int main(int argc, char **argv) {
         if (!strcmp(argv[i], "--quick")) quick = 1;
         else if (!strcmp(argv[i], "--media")) flags |= BRE_PBRT_MEDIA;
         else if (!strcmp(argv[i], "--lights")) flags |= BRE_PBRT_LIGHTS;
+        else if (!strcmp(argv[i], "--materials")) flags |= BRE_PBRT_MATERIALS;
         else if (!strcmp(argv[i], "--outfile") && i + 1 < argc) outfile = argv[++i];
         else if (!strcmp(argv[i], "--device") && i + 1 < argc) device = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--devices") && i + 1 < argc) {

@@ -489,6 +489,10 @@ struct Material {
     float ceta[3] = {0.f, 0.f, 0.f}, ck[3] = {0.f, 0.f, 0.f};
     float roughness = 0.1f, uroughness = 0.f, vroughness = 0.f;
     bool remap = true;
+    // kParseMaterials: "roughglass" (a "glass" with "uroughness" or "vroughness" != 0: kr, kt, eta, u / vroughness),
+    // "uber" (pkd, ks, kr, kt, eta, roughness, u / vroughness with 0 = not given, opacity), "translucent" (pkd, ks,
+    // "reflect" in kr and "transmit" in kt, roughness), "substrate" (pkd, ks, u / vroughness)
+    float opacity[3] = {1.f, 1.f, 1.f};
 };
 
 struct GraphicsState {
@@ -518,7 +522,8 @@ struct ShapeRec {
 class Parser {
   public:
     Parser(PbrtScene *out, int flags)
-        : out_(out), mediaOk_((flags & kParseMedia) != 0), lightsOk_((flags & kParseLights) != 0) {}
+        : out_(out), mediaOk_((flags & kParseMedia) != 0), lightsOk_((flags & kParseLights) != 0),
+          materialsOk_((flags & kParseMaterials) != 0) {}
 
     bool Run(Lexer &lx, int depth);
     bool Finish();
@@ -546,6 +551,7 @@ class Parser {
     PbrtScene *out_;
     bool mediaOk_;  // kParseMedia
     bool lightsOk_;  // kParseLights: LightSource "distant" and "point", two-sided area lights
+    bool materialsOk_;  // kParseMaterials: rough glass, direct Material "glass", "uber", "translucent", "substrate"
     Xform ctm_ = Xform::Identity();
     int ctmKind_ = 0;  // 0 identity, 1 exactly one LookAt, 2 anything else
     float lookAt_[9] = {0, 0, 0, 0, 0, 1, 0, 1, 0};
@@ -746,6 +752,89 @@ void Parser::MakeMaterial(Lexer &lx, int line, const std::string &type, const Pa
         m->none = true;
         return;
     }
+    if (materialsOk_ && (type == "glass" || type == "uber" || type == "translucent" || type == "substrate")) {
+        // CreateGlassMaterial (glass.cpp:94-110), CreateUberMaterial (uber.cpp:103-127), CreateTranslucentMaterial
+        // (translucent.cpp:82-98), CreateSubstrateMaterial (substrate.cpp:67-81): their defaults
+        bool ok = true;
+        const auto spectrum = [&](const char *name, float *v, float d) {
+            v[0] = v[1] = v[2] = d;
+            if (ps.Has(name) && !ps.FindOneSpectrum(name, v)) {
+                Error(lx, line, "%s \"%s\" must be an rgb or xyz value (textures are not supported)", type.c_str(), name);
+                ok = false;
+            }
+        };
+        const auto number = [&](const char *name, float d) {
+            if (ps.Has(name) && !ps.FindFloats(name)) {
+                Error(lx, line, "%s \"%s\" must be a float (textures are not supported)", type.c_str(), name);
+                ok = false;
+            }
+            return ps.FindOneFloat(name, d);
+        };
+        const auto eta = [&]() {
+            const float e = ps.Has("eta") ? number("eta", 1.5f) : number("index", 1.5f);
+            if (!(e > 0.f) || !std::isfinite(e)) {
+                Error(lx, line, "%s \"eta\" must be finite and > 0", type.c_str());
+                ok = false;
+            }
+            return e;
+        };
+        if (type == "glass") {
+            spectrum("Kr", m->kr, 1.f);
+            spectrum("Kt", m->kt, 1.f);
+            m->eta = eta();
+            m->uroughness = number("uroughness", 0.f);
+            m->vroughness = number("vroughness", 0.f);
+            if (m->uroughness != 0.f || m->vroughness != 0.f) m->type = "roughglass";
+        } else if (type == "uber") {
+            spectrum("Kd", m->pkd, 0.25f);
+            spectrum("Ks", m->ks, 0.25f);
+            spectrum("Kr", m->kr, 0.f);
+            spectrum("Kt", m->kt, 0.f);
+            m->roughness = number("roughness", 0.1f);
+            m->uroughness = number("uroughness", 0.f);  // 0 = not given: uber.cpp:72-79
+            m->vroughness = number("vroughness", 0.f);
+            m->eta = eta();
+            spectrum("opacity", m->opacity, 1.f);
+        } else if (type == "translucent") {
+            spectrum("Kd", m->pkd, 0.25f);
+            spectrum("Ks", m->ks, 0.25f);
+            spectrum("reflect", m->kr, 0.5f);
+            spectrum("transmit", m->kt, 0.5f);
+            m->roughness = number("roughness", 0.1f);
+        } else {
+            spectrum("Kd", m->pkd, 0.5f);
+            spectrum("Ks", m->ks, 0.5f);
+            m->uroughness = number("uroughness", 0.1f);
+            m->vroughness = number("vroughness", 0.1f);
+        }
+        m->remap = ps.FindOneBool("remaproughness", true);
+        if (ok && m->type != "glass") {
+            // the alphas a material's own fallbacks leave: finite, and > 0 where RoughnessToAlpha does not clamp them
+            float u = m->uroughness, v = m->vroughness;
+            if (type == "uber") {
+                u = m->uroughness != 0.f ? m->uroughness : m->roughness;
+                v = m->vroughness != 0.f ? m->vroughness : u;
+            } else if (type == "translucent") {
+                u = v = m->roughness;
+            }
+            if (!std::isfinite(u) || !std::isfinite(v) || (!m->remap && (!(u > 0.f) || !(v > 0.f)))) {
+                Error(lx, line, "%s: the roughnesses must be finite, and > 0 with \"remaproughness\" false", type.c_str());
+                ok = false;
+            }
+        }
+        if (ps.Has("bumpmap")) {
+            Error(lx, line, "%s \"bumpmap\" is not supported by the GPU scene model", type.c_str());
+            ok = false;
+        }
+        ps.FindOneString("type", "");
+        if (ok) {
+            ReportUnused(lx, line, ps);
+            return;
+        }
+        Error(lx, line, "using \"matte\" in place of this \"%s\"", type.c_str());
+        *m = Material();
+        return;
+    }
     if (type == "mirror" || (type == "glass" && named)) {
         // CreateMirrorMaterial (mirror.cpp:58-64), CreateGlassMaterial (glass.cpp:94-109)
         const bool glass = type == "glass";
@@ -876,7 +965,9 @@ void Parser::MakeMaterial(Lexer &lx, int line, const std::string &type, const Pa
 // sigma 0, which stays the triangle's own kd): entries are shared by equal materials
 int Parser::SpecularIndex(Lexer &lx, int line, const Material &m) {
     const bool rough_matte = m.type == "matte" && m.sigma != 0.f;
-    if (m.type != "mirror" && m.type != "glass" && m.type != "plastic" && m.type != "metal" && !rough_matte && !m.none)
+    const bool lobed = m.type == "roughglass" || m.type == "uber" || m.type == "translucent" || m.type == "substrate";
+    if (m.type != "mirror" && m.type != "glass" && m.type != "plastic" && m.type != "metal" && !rough_matte && !m.none &&
+        !lobed)
         return -1;
     bre_material_ex b;
     memset(&b, 0, sizeof(b));
@@ -886,6 +977,27 @@ int Parser::SpecularIndex(Lexer &lx, int line, const Material &m) {
         b.type = BRE_MATERIAL_MATTE;
         memcpy(b.kd, m.kd, sizeof(b.kd));
         b.sigma = m.sigma;
+    } else if (lobed) {
+        // each type's record holds the fields it reads and zeros elsewhere (include/bre_scene.h)
+        const bool glass = m.type == "roughglass", uber = m.type == "uber", trans = m.type == "translucent";
+        b.type = glass ? BRE_MATERIAL_ROUGH_GLASS : uber ? BRE_MATERIAL_UBER : trans ? BRE_MATERIAL_TRANSLUCENT
+                                                                                      : BRE_MATERIAL_SUBSTRATE;
+        if (!glass) {
+            memcpy(b.kd, m.pkd, sizeof(b.kd));
+            memcpy(b.ks, m.ks, sizeof(b.ks));
+        }
+        if (glass || uber || trans) {
+            memcpy(b.kr, m.kr, sizeof(b.kr));
+            memcpy(b.kt, m.kt, sizeof(b.kt));
+        }
+        if (glass || uber) b.eta = m.eta;
+        if (uber || trans) b.roughness = m.roughness;
+        if (!trans) {
+            b.uroughness = m.uroughness;
+            b.vroughness = m.vroughness;
+        }
+        if (uber) memcpy(b.opacity, m.opacity, sizeof(b.opacity));
+        b.remap = m.remap ? 1 : 0;
     } else if (m.type == "plastic") {
         b.type = BRE_MATERIAL_PLASTIC;
         memcpy(b.kd, m.pkd, sizeof(b.kd));

@@ -28,6 +28,8 @@
 //     bre_material_ex in PbrtScene::materials, referred to by the triangles declared under it
 //     (PbrtScene::triangleMaterial).  "bumpmap" and texture-valued parameters are reported and the statement
 //     falls back to matte.  The direct statement Material "glass" is reported as unsupported.
+//   * With kParseMaterials: "glass" with "uroughness" / "vroughness" (rough glass) and as a direct statement,
+//     "uber", "translucent" and "substrate", direct or named (see kParseMaterials below).
 //   * AreaLightSource "diffuse" ("L" x "scale"; one-sided, with kParseLights also "bool twosided"): every
 //     triangle of an emitting mesh is its own light, as pbrtShape makes one DiffuseAreaLight per shape (api.cpp).
 //   * media: "homogeneous" or "heterogeneous" (GridDensityMedium).  By default the scene has ONE medium
@@ -125,6 +127,12 @@ constexpr int kParseMedia = 1;  // BRE_PBRT_MEDIA (include/bre_pbrt.h)
 // become bre_lights and "bool twosided" "true" on an AreaLightSource "diffuse" gives BRE_EMIT_TWO_SIDED triangles,
 // instead of the three refusals of the default parse
 constexpr int kParseLights = 2;  // BRE_PBRT_LIGHTS
+// kParseMaterials: Material "glass" with a roughness (rough glass), "glass" as a direct statement, "uber",
+// "translucent" and "substrate" become bre_material_ex records of types 8 .. 11 (2 for a smooth glass), direct or
+// named, with the defaults of the reference's Create...Material functions; without it the parse reports them as
+// before.  Texture-valued parameters and "bumpmap" are reported and the statement falls back to matte, as for the
+// other materials.
+constexpr int kParseMaterials = 4;  // BRE_PBRT_MATERIALS
 struct SceneMedia {
     std::vector<bre_medium> media;             // grid_density points into `density`
     std::vector<std::vector<float>> density;   // per table entry: a heterogeneous medium's data

@@ -24,6 +24,7 @@ CLI_PATH = os.path.join(HERE, "host", "bre_pbrt")
 
 PBRT_MEDIA = 1  # BRE_PBRT_MEDIA
 PBRT_LIGHTS = 2  # BRE_PBRT_LIGHTS: LightSource "distant" and "point", two-sided area lights
+PBRT_MATERIALS = 4  # BRE_PBRT_MATERIALS: rough glass, direct Material "glass", "uber", "translucent", "substrate"
 EXPORTS = ["bre_pbrt_parse_file", "bre_pbrt_parse_string", "bre_pbrt_parse_file_ex", "bre_pbrt_parse_string_ex",
            "bre_pbrt_get_media", "bre_pbrt_free", "bre_pbrt_messages",
            "bre_pbrt_get_scene", "bre_pbrt_get_lights", "bre_pbrt_get_materials", "bre_pbrt_get_materials_ex", "bre_pbrt_make_spot_light", "bre_pbrt_get_render_params", "bre_pbrt_get_film", "bre_pbrt_render",
@@ -169,27 +170,31 @@ class PbrtScene:
             pass
 
 
-def _parse(fn, arg: bytes, quick: bool, media: bool, lights: bool = False) -> PbrtScene:
+def _parse(fn, arg: bytes, quick: bool, media: bool, lights: bool = False, materials: bool = False) -> PbrtScene:
     lib = load_host_library()
     h = ctypes.c_void_p()
-    if media or lights:
-        flags = (PBRT_MEDIA if media else 0) | (PBRT_LIGHTS if lights else 0)
+    if media or lights or materials:
+        flags = (PBRT_MEDIA if media else 0) | (PBRT_LIGHTS if lights else 0) | (PBRT_MATERIALS if materials else 0)
         st = getattr(lib, fn + "_ex")(arg, flags, ctypes.byref(h))
     else:
         st = getattr(lib, fn)(arg, ctypes.byref(h))
     return PbrtScene(h, st == 0, quick)
 
 
-def parse_file(path: str, quick: bool = False, media: bool = False, lights: bool = False) -> PbrtScene:
+def parse_file(path: str, quick: bool = False, media: bool = False, lights: bool = False,
+               materials: bool = False) -> PbrtScene:
     """`media`: BRE_PBRT_MEDIA -- media bounded by surfaces are accepted (.media, .tri_inside, .tri_outside,
     .camera_medium, .light_medium on the result) instead of refused.
     `lights`: BRE_PBRT_LIGHTS -- LightSource "distant" and "point" and "bool twosided" "true" on an
-    AreaLightSource "diffuse" are accepted instead of refused."""
-    return _parse("bre_pbrt_parse_file", os.fsencode(path), quick, media, lights)
+    AreaLightSource "diffuse" are accepted instead of refused.
+    `materials`: BRE_PBRT_MATERIALS -- Material "glass" with a roughness or as a direct statement, "uber",
+    "translucent" and "substrate" become entries of .materials_ex instead of being reported."""
+    return _parse("bre_pbrt_parse_file", os.fsencode(path), quick, media, lights, materials)
 
 
-def parse_string(text: str, quick: bool = False, media: bool = False, lights: bool = False) -> PbrtScene:
-    return _parse("bre_pbrt_parse_string", text.encode(), quick, media, lights)
+def parse_string(text: str, quick: bool = False, media: bool = False, lights: bool = False,
+                 materials: bool = False) -> PbrtScene:
+    return _parse("bre_pbrt_parse_string", text.encode(), quick, media, lights, materials)
 
 
 def make_spot_light(frm, to, I, coneangle: float = 30.0, conedelta: float = 5.0, order: int = 0, ctm=None,

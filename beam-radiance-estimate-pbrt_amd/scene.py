@@ -143,6 +143,15 @@ class MaterialEx(ctypes.Structure):
     def to_bytes(self) -> bytes:
         return ctypes.string_at(ctypes.addressof(self), ctypes.sizeof(self))
 
+    @property
+    def opacity(self):
+        """An uber's "opacity": the words of `ceta`, which an uber never reads (the record's anonymous union)."""
+        return self.ceta
+
+    @opacity.setter
+    def opacity(self, v):
+        self.ceta = v
+
 
 def widen(m) -> "MaterialEx":
     """A Material as the MaterialEx bre_set_materials makes of it; a MaterialEx as it is."""
@@ -175,6 +184,49 @@ def metal(eta, k, roughness: float = 0.01, uroughness: float = 0.0, vroughness: 
     m = MaterialEx()
     m.type, m.ceta, m.ck = MATERIAL_METAL, _rgb(eta), _rgb(k)
     m.roughness, m.uroughness, m.vroughness, m.remap = float(roughness), float(uroughness), float(vroughness), int(bool(remap))
+    return m
+
+
+MATERIAL_ROUGH_GLASS, MATERIAL_UBER, MATERIAL_TRANSLUCENT, MATERIAL_SUBSTRATE = 8, 9, 10, 11
+
+
+def rough_glass(kr=1.0, kt=1.0, eta: float = 1.5, uroughness: float = 0.0, vroughness: float = 0.0,
+                remap: bool = True) -> MaterialEx:
+    """Material "glass" with "uroughness" or "vroughness" != 0 (glass.cpp:94-110): "Kr", "Kt" (default 1), "eta"
+    (1.5), the two roughnesses (default 0; both 0 is glass(), and refused as a rough glass), "remaproughness"."""
+    m = MaterialEx()
+    m.type, m.kr, m.kt, m.eta = MATERIAL_ROUGH_GLASS, _rgb(kr), _rgb(kt), float(eta)
+    m.uroughness, m.vroughness, m.remap = float(uroughness), float(vroughness), int(bool(remap))
+    return m
+
+
+def uber(kd=0.25, ks=0.25, kr=0.0, kt=0.0, roughness: float = 0.1, uroughness: float = 0.0, vroughness: float = 0.0,
+         eta: float = 1.5, opacity=1.0, remap: bool = True) -> MaterialEx:
+    """Material "uber" (uber.cpp:103-127): "Kd", "Ks" (default 0.25), "Kr", "Kt" (0), "roughness" (0.1),
+    "uroughness" / "vroughness" (0: not given; u falls back to `roughness`, v to u), "eta" (1.5), "opacity" (1),
+    "remaproughness"."""
+    m = MaterialEx()
+    m.type, m.kd, m.ks, m.kr, m.kt = MATERIAL_UBER, _rgb(kd), _rgb(ks), _rgb(kr), _rgb(kt)
+    m.roughness, m.uroughness, m.vroughness = float(roughness), float(uroughness), float(vroughness)
+    m.eta, m.opacity, m.remap = float(eta), _rgb(opacity), int(bool(remap))
+    return m
+
+
+def translucent(kd=0.25, ks=0.25, reflect=0.5, transmit=0.5, roughness: float = 0.1, remap: bool = True) -> MaterialEx:
+    """Material "translucent" (translucent.cpp:82-98): "Kd", "Ks" (default 0.25), "reflect", "transmit" (0.5; kept
+    in kr and kt), "roughness" (0.1), "remaproughness"."""
+    m = MaterialEx()
+    m.type, m.kd, m.ks, m.kr, m.kt = MATERIAL_TRANSLUCENT, _rgb(kd), _rgb(ks), _rgb(reflect), _rgb(transmit)
+    m.roughness, m.remap = float(roughness), int(bool(remap))
+    return m
+
+
+def substrate(kd=0.5, ks=0.5, uroughness: float = 0.1, vroughness: float = 0.1, remap: bool = True) -> MaterialEx:
+    """Material "substrate" (substrate.cpp:67-81): "Kd", "Ks" (default 0.5), "uroughness", "vroughness" (0.1),
+    "remaproughness"."""
+    m = MaterialEx()
+    m.type, m.kd, m.ks = MATERIAL_SUBSTRATE, _rgb(kd), _rgb(ks)
+    m.uroughness, m.vroughness, m.remap = float(uroughness), float(vroughness), int(bool(remap))
     return m
 
 

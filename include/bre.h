@@ -320,9 +320,22 @@ bre_status bre_set_materials(bre_ctx *ctx, const bre_material *materials, int32_
    BRE_ERR_INVALID_ARG, beside the cases of bre_set_materials: an unknown type; a non-finite parameter of the
    record's type; a plastic roughness, or a metal u / v roughness after the fallback to `roughness`, that is
    not > 0 (a negative u / vroughness included); a metal ceta channel of 0; a remap other than 0 / 1; non-zero
-   reserved words.  Needs no device. */
+   reserved words.
+   BRE_MATERIAL_ROUGH_GLASS, _UBER, _TRANSLUCENT and _SUBSTRATE (bre_scene.h) are records of the same table; a
+   context whose table holds one runs the passes' kernels with the BSDF of any number of lobes.  Their colours
+   (uber's opacity included) are clamped to [0, 1]; a material left without a lobe absorbs.  Refused for them,
+   besides the above: eta not finite or not > 0 (rough glass, uber); an alpha that is not > 0 after the material's
+   own fallbacks and mapping (with remap 1 a roughness of 0 is legal, RoughnessToAlpha clamps at 1e-3; with remap
+   0 it is not); a rough glass with both roughnesses 0 (that is BRE_MATERIAL_GLASS);
+   a non-zero field that the type does not read (bre_scene.h lists what each reads), `opacity` / `ceta` on a
+   record that is not an uber included.  Type 7 is unassigned.  Needs no device. */
 bre_status bre_set_materials_ex(bre_ctx *ctx, const bre_material_ex *materials, int32_t n_materials,
                                 const int32_t *triangle_material, int64_t n_triangles);
+/* One record as bre_set_materials_ex would check it on a context without media, with no context and no device:
+   BRE_OK, or BRE_ERR_INVALID_ARG with what the material has that is wrong in `message` (up to `capacity` bytes, the
+   text that follows "material k has " in the setter's error; message may be NULL).  For front ends that want to
+   report a record before a context exists. */
+bre_status bre_check_material_ex(const bre_material_ex *material, char *message, int32_t capacity);
 
 /* ---- media bounded by surfaces (bre_medium, bre_scene.h; pbrt's MediumInterface) ----
    Copies the table media[0 .. n_media) with its density grids, the per-triangle pairs
@@ -505,6 +518,12 @@ bre_status bre_resolve_image(int64_t npix, const float *ld_rgb, int iteration, f
              sampled wi (xyz), pdf, f (rgb) and the sampled BxDFType as int32 (all zero where Sample_f returns
              0 or the material has no BxDF), then f(wo, wi2) (rgb) and Pdf(wo, wi2).  Partial records and an
              index outside aux are refused with BRE_ERR_INVALID_ARG.
+     kind 14: the BSDF of any number of lobes (bsdfn_sample, bsdfn_f, bsdfn_pdf, bre_trace.h: BSDF::Sample_f, f
+             and Pdf with BxDFType flags and a TransportMode) that the passes use for a table with a rough glass,
+             uber, translucent or substrate entry.  Kind 13 with two more floats per record: aux as there, with
+             types 4 .. 6 and 8 .. 11; x holds n / 11 records of 11 floats: the 9 of kind 13, then the transport
+             mode (0: Importance, 1: Radiance) and the flag set (0: BSDF_ALL, 1: BSDF_ALL & ~BSDF_SPECULAR), used
+             by all three functions.  The same 12 words out.
    so the tests can hold them against the reference's own primitive tests (src/tests/fp_tests.cpp,
    find_interval.cpp), against the compiler's correctly rounded sqrt and division, and (kinds 10, 11)
    against a host restatement and validator of the hierarchy (tests/refpy_lbvh.py). */

@@ -42,10 +42,14 @@ bre_status bre_pbrt_parse_string(const char *text, bre_pbrt **out);
    BRE_PBRT_LIGHTS: LightSource "distant" and LightSource "point" become bre_lights (bre_pbrt_get_lights) and
    "bool twosided" "true" on an AreaLightSource "diffuse" makes BRE_EMIT_TWO_SIDED triangles.  A distant light is
    in vacuum whatever MediumInterface is current (its entry of light_medium is -1); a scene whose one medium fills
-   all space cannot hold one: bound the medium with surfaces and add BRE_PBRT_MEDIA.  The flags combine.
+   all space cannot hold one: bound the medium with surfaces and add BRE_PBRT_MEDIA.
+   BRE_PBRT_MATERIALS: Material "glass" with "uroughness" / "vroughness" (rough glass), "glass" as a direct
+   statement, "uber", "translucent" and "substrate", direct or named, become bre_material_ex records of types 8 .. 11
+   (bre_pbrt_get_materials_ex) with the defaults of pbrt's Create...Material functions.  The flags combine.
    flags 0 is bre_pbrt_parse_file / _string, which keep refusing such scenes. */
 #define BRE_PBRT_MEDIA 1
 #define BRE_PBRT_LIGHTS 2
+#define BRE_PBRT_MATERIALS 4
 bre_status bre_pbrt_parse_file_ex(const char *path, int32_t flags, bre_pbrt **out);
 bre_status bre_pbrt_parse_string_ex(const char *text, int32_t flags, bre_pbrt **out);
 void bre_pbrt_free(bre_pbrt *p);

@@ -51,6 +51,12 @@
  *                       with "sigma"), set with bre_set_materials_ex as the same table in its wide form.  Both
  *                       passes go through the general BSDF (BSDF::f, Pdf and Sample_f, reflection.cpp:670-785)
  *                       over a Lambertian or Oren-Nayar lobe and a Trowbridge-Reitz microfacet lobe.
+ *   - rough glass, uber, translucent and substrate (bre_material_ex types 8 .. 11; GlassMaterial with roughness,
+ *                       UberMaterial, TranslucentMaterial, SubstrateMaterial), in the same table.  Their BSDFs hold
+ *                       up to five lobes, reflecting and transmitting, specular and not: both passes sample them
+ *                       with BSDF_ALL, the photon pass in TransportMode::Importance and the camera pass in Radiance,
+ *                       and EstimateDirect evaluates them with BSDF_ALL & ~BSDF_SPECULAR on both sides of the
+ *                       surface (src/core/integrator.cpp:112-113).
  *   - media bounded by surfaces (bre_medium below; pbrt's MediumInterface): a context holds a table of
  *                       media, a per-triangle (inside, outside) pair, the camera's medium and each delta
  *                       light's (bre_set_media, bre.h).  Every ray carries its medium; a triangle whose
@@ -69,6 +75,7 @@
 #ifndef BRE_SCENE_H
 #define BRE_SCENE_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -182,23 +189,56 @@ typedef struct bre_material {
 #define BRE_MATERIAL_MATTE 4   /* kd, sigma */
 #define BRE_MATERIAL_PLASTIC 5 /* kd, ks, roughness, remap */
 #define BRE_MATERIAL_METAL 6   /* ceta, ck, roughness / uroughness / vroughness, remap */
+/* Type 7 is unassigned and refused as unknown.
+   Transmissive and layered materials, through the BSDF of any number of lobes with BxDFType flags and a transport
+   mode (BSDF::f, Pdf, Sample_f with their reflect / transmit split, reflection.cpp:670-785):
+   - rough glass (GlassMaterial with "uroughness" or "vroughness" != 0, src/materials/glass.cpp:45-92): a
+     MicrofacetReflection under FresnelDielectric(1, eta) and a MicrofacetTransmission between 1 and eta.  Both
+     roughnesses 0 is BRE_MATERIAL_GLASS and refused here; with remap, one of them may be 0 (RoughnessToAlpha
+     clamps at 1e-3).
+   - uber (UberMaterial, src/materials/uber.cpp:45-101): SpecularTransmission(1 - opacity, 1, 1),
+     LambertianReflection(op Kd), MicrofacetReflection(op Ks), SpecularReflection(op Kr), SpecularTransmission(op Kt,
+     1, eta), each only where its colour is not black.  uroughness 0 = not given: `roughness`; vroughness 0 = not
+     given: the u value (uber.cpp:72-79).  `opacity` shares the storage of `ceta`, which uber never reads.
+   - translucent (TranslucentMaterial, src/materials/translucent.cpp:45-80): "reflect" in kr, "transmit" in kt;
+     Lambertian reflection and transmission of Kd, microfacet reflection and transmission of Ks between 1 and 1.5.
+   - substrate (SubstrateMaterial, src/materials/substrate.cpp:45-65): one FresnelBlend(Kd, Ks).
+   Every field a type does not read must be 0 in a record of these four types. */
+#define BRE_MATERIAL_ROUGH_GLASS 8  /* kr, kt, eta, uroughness, vroughness, remap */
+#define BRE_MATERIAL_UBER 9         /* kd, ks, kr, kt, eta, roughness, uroughness, vroughness, remap, opacity */
+#define BRE_MATERIAL_TRANSLUCENT 10 /* kd, ks, kr ("reflect"), kt ("transmit"), roughness, remap */
+#define BRE_MATERIAL_SUBSTRATE 11   /* kd, ks, uroughness, vroughness, remap */
 
 typedef struct bre_material_ex {
-    int32_t type;     /* BRE_MATERIAL_MIRROR .. BRE_MATERIAL_METAL */
-    float kr[3];      /* as in bre_material */
-    float kt[3];
-    float eta;        /* mirror / glass: finite and > 0; ignored by the other types */
-    float kd[3];      /* matte, plastic: "Kd", clamped to [0, 1]; black = no diffuse lobe */
-    float ks[3];      /* plastic: "Ks", clamped to [0, 1]; black = no glossy lobe */
-    float ceta[3];    /* metal: "eta" (the conductor's index per channel), finite and != 0 */
+    int32_t type;     /* BRE_MATERIAL_MIRROR .. BRE_MATERIAL_METAL, BRE_MATERIAL_ROUGH_GLASS .. BRE_MATERIAL_SUBSTRATE */
+    float kr[3];      /* as in bre_material; translucent: "reflect" */
+    float kt[3];      /* translucent: "transmit" */
+    float eta;        /* mirror / glass / rough glass / uber: finite and > 0; ignored by types 4 .. 6 */
+    float kd[3];      /* matte, plastic, uber, translucent, substrate: "Kd", clamped to [0, 1] */
+    float ks[3];      /* plastic, uber, translucent, substrate: "Ks", clamped to [0, 1] */
+#if defined(__cplusplus) || (defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L)
+    union {
+        float ceta[3];    /* metal: "eta" (the conductor's index per channel), finite and != 0 */
+        float opacity[3]; /* uber: "opacity", clamped to [0, 1] (pbrt's default is 1, the record's is what it holds) */
+    };
+#else
+    float ceta[3];    /* metal: "eta"; uber: "opacity" */
+#endif
     float ck[3];      /* metal: "k" (its absorption per channel) */
-    float roughness;  /* plastic: "roughness" (> 0); metal: "roughness", used where u / vroughness is 0 */
-    float uroughness; /* metal: "uroughness" (>= 0; 0 = not given: `roughness`) */
-    float vroughness; /* metal: "vroughness" (likewise) */
+    float roughness;  /* plastic, translucent: "roughness" (> 0); metal, uber: used where u / vroughness is 0 */
+    float uroughness; /* metal, uber: "uroughness" (>= 0; 0 = not given); rough glass, substrate: "uroughness" */
+    float vroughness; /* metal, uber: "vroughness" (likewise); rough glass, substrate: "vroughness" */
     float sigma;      /* matte: "sigma" in degrees (clamped to [0, 90]; 0 = Lambertian) */
-    int32_t remap;    /* plastic, metal: "remaproughness" (0 / 1): roughness -> alpha by RoughnessToAlpha */
+    int32_t remap;    /* every type with a roughness: "remaproughness" (0 / 1): roughness -> alpha by RoughnessToAlpha */
     int32_t reserved[3]; /* 0 */
 } bre_material_ex;    /* 112 bytes, no padding */
+#ifdef __cplusplus
+static_assert(sizeof(bre_material_ex) == 112, "bre_material_ex stays 112 bytes");
+static_assert(offsetof(bre_material_ex, ceta) == 56 && offsetof(bre_material_ex, opacity) == 56 &&
+              offsetof(bre_material_ex, ck) == 68 && offsetof(bre_material_ex, roughness) == 80 &&
+              offsetof(bre_material_ex, remap) == 96 && offsetof(bre_material_ex, reserved) == 100,
+              "bre_material_ex keeps every offset; opacity shares ceta's storage");
+#endif
 
 /* Media bounded by surfaces: pbrt's MediumInterface.  Like the lights and materials they are not part of
    bre_scene: a context holds a table of media, each triangle's (inside, outside) pair, the camera's medium
