@@ -46,7 +46,7 @@ EXPORTS = [
     "bre_render_progressive", "bre_shard_segments", "bre_set_beams_sharded", "bre_gather_sharded",
     "bre_device_check", "bre_resolve_classes", "bre_film_add", "bre_set_gather_after", "bre_set_gather_events",
     "bre_render_sharded", "bre_render_progressive_sharded", "bre_set_lights", "bre_set_materials",
-    "bre_set_media", "bre_set_materials_ex", "bre_check_material_ex",
+    "bre_set_media", "bre_set_materials_ex", "bre_check_material_ex", "bre_check_material_table_ex",
 ]
 # bre_image_fn: int on_image(int32 iteration, const float *image_rgb, void *user)
 IMAGE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_int32, ctypes.POINTER(ctypes.c_float), ctypes.c_void_p)
@@ -140,6 +140,9 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     if hasattr(lib, "bre_check_material_ex"):
         lib.bre_check_material_ex.argtypes = [P, ctypes.c_char_p, I32]
         lib.bre_check_material_ex.restype = I32
+    if hasattr(lib, "bre_check_material_table_ex"):
+        lib.bre_check_material_table_ex.argtypes = [P, I32, ctypes.c_char_p, I32]
+        lib.bre_check_material_table_ex.restype = I32
     if hasattr(lib, "bre_set_media"):
         lib.bre_set_media.argtypes = [P, P, I32, P, P, I64, I32, P, I32]
         lib.bre_set_media.restype = I32
@@ -375,6 +378,19 @@ class BeamGather:
         self._check(self.lib.bre_set_materials(self.h, arr if materials else None, len(materials),
                                                tm.ctypes.data if tm.size else None, tm.size))
 
+    @staticmethod
+    def check_material_table(materials) -> str:
+        """bre_check_material_table_ex: the whole table (scene.MaterialEx, or scene.Material widened) as
+        set_materials would check it on a context without media, the rules between records that a scene.mix brings
+        included, with no context and no device.  Returns "" or the setter's text from "material k has " on."""
+        from .scene import MaterialEx, widen
+
+        wide = [widen(m) for m in materials]
+        arr = (MaterialEx * max(len(wide), 1))(*wide)
+        buf = ctypes.create_string_buffer(512)
+        status = load_library().bre_check_material_table_ex(arr, len(wide), buf, len(buf))
+        return "" if status == 0 else (buf.value.decode() or "invalid arguments")
+
     # ---- media ----
     def set_media(self, media=(), tri_inside=(), tri_outside=(), camera_medium: int = -1, light_medium=()):
         """bre_set_media: the media table (scene.Medium: scene.medium_homogeneous, scene.medium_grid), each scene
@@ -531,7 +547,9 @@ class BeamGather:
     def lobes_check(self, materials, records):
         """bre_device_check kind 14: the BSDF of any number of lobes on records [n, 11]: those of bsdf_check, then the
         transport mode (0 Importance / 1 Radiance) and the flag set (0 BSDF_ALL / 1 BSDF_ALL & ~BSDF_SPECULAR);
-        `materials` may also hold rough glass, uber, translucent and substrate records.  Returns bsdf_check's dict."""
+        `materials` may also hold rough glass, uber, translucent and substrate records, and mixes (scene.mix) with
+        the entries they name, mirrors and smooth glasses among them (scene.widen): such a table is checked as
+        set_materials checks it and a record may name any entry of type >= 4.  Returns bsdf_check's dict."""
         from .scene import MaterialEx
 
         mats = list(materials)

@@ -185,6 +185,44 @@ bre_status bre_device_check(bre_ctx *c, int32_t kind, int64_t n, const float *x,
         const int n_mats = n_aux / kWords;
         std::vector<bre_material_ex> mats((size_t)n_mats);
         std::memcpy(mats.data(), aux, (size_t)n_aux * 4);
+        bool mixed = false;
+        for (int k = 0; k < n_mats; ++k) mixed = mixed || mats[(size_t)k].type == BRE_MATERIAL_MIX;
+        if (mixed) {
+            // a table that holds a mix: checked as bre_set_materials_ex checks it (mirror and glass children and the
+            // rules between records included) and evaluated through the wide lists of a mixed context
+            int bad = 0;
+            const std::string what = check_material_table(mats, &bad);
+            if (!what.empty())
+                return fail(c, BRE_ERR_INVALID_ARG, "bre_device_check: kind 14: material %d has %s", bad, what.c_str());
+            std::vector<DevLobesMx> wide;
+            make_lobes_mx(mats.data(), n_mats, &wide);
+            for (int64_t i = 0; i < n / kRec; ++i) {
+                const float *r = x + kRec * i;
+                if (!(r[8] >= 0 && r[8] < (float)n_mats) || r[8] != std::floor(r[8]))
+                    return fail(c, BRE_ERR_INVALID_ARG, "bre_device_check: kind 14: record %lld names material %g of %d",
+                                (long long)i, (double)r[8], n_mats);
+                if (mats[(size_t)r[8]].type < BRE_MATERIAL_MATTE)
+                    return fail(c, BRE_ERR_INVALID_ARG, "bre_device_check: kind 14: record %lld names material %d, a "
+                                "mirror or glass: it is evaluated only as a mix's child", (long long)i, (int)r[8]);
+                if ((r[9] != 0.f && r[9] != 1.f) || (r[10] != 0.f && r[10] != 1.f))
+                    return fail(c, BRE_ERR_INVALID_ARG, "bre_device_check: kind 14: record %lld has a mode or a flag "
+                                "set that is not 0 or 1", (long long)i);
+            }
+            if (n == 0) return BRE_OK;
+            BRE_TRY(set_device(c));
+            float *dx = nullptr, *dy = nullptr;
+            DevLobesMx *dt = nullptr;
+            const size_t outs = (size_t)(n / kRec) * 12;
+            HIPCHK(c, c->chk_x.get((size_t)n, &dx));
+            HIPCHK(c, c->chk_y.get(outs, &dy));
+            HIPCHK(c, c->chk_aux.get((size_t)n_mats, &dt));
+            HIPCHK(c, hipMemcpyAsync(dx, x, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, hipMemcpyAsync(dt, wide.data(), wide.size() * sizeof(DevLobesMx), hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, launch_check_lobes_mx(n / kRec, dx, dt, n_mats, dy, c->stream));
+            HIPCHK(c, hipMemcpyAsync(y, dy, outs * 4, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            return BRE_OK;
+        }
         std::vector<DevLobes> table((size_t)n_mats);
         for (int k = 0; k < n_mats; ++k) {
             const std::string what = check_lobed_or_glossy_material(mats[(size_t)k]);

@@ -63,7 +63,7 @@ bre_status bre_trace_photons(bre_ctx *c, const bre_scene *scene, int64_t n_photo
     int cap = c->photon_single ? (int)std::min<int64_t>(64, ((int64_t)5 << 29) / (40 * std::max<int64_t>(n_photons, 1))) : 0;
     if (cap < 4) cap = 0;
     if (c->photon_single >= 2) cap = c->photon_single;  // tests: a forced slot count (overflow paths)
-    const int tier = c->held.lobed ? 2 : (c->held.glossy ? 1 : 0);
+    const int tier = c->held.mixed ? 3 : (c->held.lobed ? 2 : (c->held.glossy ? 1 : 0));
     if (c->held.glossy) {
         // the glossy photon kernels keep max_depth suspended frames a thread in LDS: refused here, by name
         if (c->lds_per_block == 0)
@@ -73,7 +73,8 @@ bre_status bre_trace_photons(bre_ctx *c, const bre_scene *scene, int64_t n_photo
             return fail(c, BRE_ERR_INVALID_ARG, "bre_trace_photons: maxdepth %d with %s "
                         "materials needs %lld bytes of LDS per block for the photon kernels' suspended frames; the "
                         "device has %d", max_depth,
-                        c->held.lobed ? "rough glass / uber / translucent / substrate" : "plastic / metal / matte-sigma",
+                        c->held.mixed ? "mix" : c->held.lobed ? "rough glass / uber / translucent / substrate"
+                                                               : "plastic / metal / matte-sigma",
                         (long long)need, c->lds_per_block);
     }
     BeamArrays &slots = c->ph_s, &in = c->in;
@@ -165,7 +166,7 @@ bre_status bre_camera_pass(bre_ctx *c, const bre_scene *scene, int32_t width, in
     // run inside another context's gather at 80 VGPRs, keep the code and the resources they had
     bool wide = c->held.glossy;
     for (const bre_light &l : c->held.lights) wide = wide || l.type == BRE_LIGHT_DISTANT;
-    const int tier = c->held.lobed ? 2 : (wide ? 1 : 0);
+    const int tier = c->held.mixed ? 3 : (c->held.lobed ? 2 : (wide ? 1 : 0));
     HIPCHK(c, launch_camera(c->dev.record.as<DevScene>(), c->dev.head.stack_depth, c->cam_dev.as<DevCamera>(),
                             c->cam_perms.as<uint16_t>(),
                             width, height, iteration, max_depth, render_surfaces, render_media, cs, d_surface,

@@ -168,6 +168,38 @@ std::string check_lobed_material(bre_material_ex &m) {
     return "";
 }
 
+// A mix record (type 12): it reads `amount` (the words of kd) and its two children (the words of reserved[0..1]) and
+// nothing else; amount is clamped.
+std::string check_mix_material(bre_material_ex &m) {
+    struct Field {
+        const char *name;
+        const float *v;
+        int n;
+    };
+    const Field unread[] = {{"Kr", m.kr, 3},           {"Kt", m.kt, 3},
+                            {"eta", &m.eta, 1},        {"Ks", m.ks, 3},
+                            {"metal eta", m.ceta, 3},  {"k", m.ck, 3},
+                            {"roughness", &m.roughness, 1},   {"uroughness", &m.uroughness, 1},
+                            {"vroughness", &m.vroughness, 1}, {"sigma", &m.sigma, 1}};
+    for (int j = 0; j < 3; ++j)
+        if (!std::isfinite(m.amount[j])) return "a non-finite amount (mix)";
+    for (int j = 0; j < 2; ++j)
+        if (m.mix_child[j] < 0) {
+            char buf[96];
+            snprintf(buf, sizeof(buf), "a negative child index %d (mix: mix_child[%d])", m.mix_child[j], j);
+            return buf;
+        }
+    if (m.reserved[2] != 0) return "a non-zero reserved[2] (mix: only reserved[0..1] hold its children)";
+    for (const Field &f : unread)
+        for (int j = 0; j < f.n; ++j)
+            if (!(f.v[j] == 0))  // a NaN too
+                return std::string(std::isfinite(f.v[j]) ? "a non-zero " : "a non-finite ") + f.name +
+                       ", which a mix does not read";
+    if (m.remap != 0) return "a non-zero remap, which a mix does not read";
+    for (int j = 0; j < 3; ++j) m.amount[j] = m.amount[j] < 0.f ? 0.f : (m.amount[j] > 1.f ? 1.f : m.amount[j]);
+    return "";
+}
+
 // One record of the table as the context keeps it: checked, colours clamped, unused fields left as given (equal
 // tables compare equal).  `wide`: types past BRE_MATERIAL_INTERFACE are known.  Returns "", or what the material
 // has that is wrong (the narrow cases in bre_set_materials's words).
@@ -178,6 +210,7 @@ std::string check_material(bre_material_ex &m, bool wide, bool media, bool *is_i
         for (int j = 0; j < 3; ++j) v[j] = v[j] < 0.f ? 0.f : (v[j] > 1.f ? 1.f : v[j]);
     };
     char buf[160];
+    if (wide && m.type == BRE_MATERIAL_MIX) return check_mix_material(m);
     if (m.reserved[0] || m.reserved[1] || m.reserved[2]) return "non-zero reserved words";
     if (m.type == BRE_MATERIAL_INTERFACE && media) {
         // no BSDF: every parameter is ignored (kept as zeros, so that equal tables compare equal)
@@ -226,6 +259,50 @@ std::string check_material(bre_material_ex &m, bool wide, bool media, bool *is_i
     return "";
 }
 
+// The rules between the records of a checked table, which a mix brings: its children come earlier (the parser's
+// declaration order; no cycles) and have a BSDF, it nests at most BRE_MAX_MIX_DEPTH deep and expands to at most
+// BRE_MAX_BXDFS BxDFs (BSDF::Add CHECK_LTs against MaxBxDFs, reflection.h:166).  Returns "" or what material *bad has.
+std::string check_mix_table(const std::vector<bre_material_ex> &mats, int *bad) {
+    const size_t n = mats.size();
+    std::vector<int> depth(n, 0), count(n, 0);
+    char buf[200];
+    for (size_t k = 0; k < n; ++k) {
+        const bre_material_ex &m = mats[k];
+        *bad = (int)k;
+        if (m.type != BRE_MATERIAL_MIX) {
+            if (m.type == BRE_MATERIAL_MIRROR) count[k] = black3(m.kr) ? 0 : 1;
+            else if (m.type == BRE_MATERIAL_GLASS) count[k] = black3(m.kr) && black3(m.kt) ? 0 : 1;
+            else count[k] = make_lobes(m).n;  // 0 for an interface
+            continue;
+        }
+        for (int j = 0; j < 2; ++j) {
+            const int ch = m.mix_child[j];
+            if (ch >= (int)k) {
+                snprintf(buf, sizeof(buf), "child %d (mix_child[%d]) that does not come before it: a mix's children are "
+                         "earlier entries of the table", ch, j);
+                return buf;
+            }
+            if (mats[(size_t)ch].type == BRE_MATERIAL_INTERFACE) {
+                snprintf(buf, sizeof(buf), "child %d (mix_child[%d]) that is a BRE_MATERIAL_INTERFACE, which has no BSDF "
+                         "to scale", ch, j);
+                return buf;
+            }
+            depth[k] = std::max(depth[k], depth[(size_t)ch] + 1);
+            count[k] += count[(size_t)ch];
+        }
+        if (depth[k] > BRE_MAX_MIX_DEPTH) {
+            snprintf(buf, sizeof(buf), "a nest %d mixes deep (at most BRE_MAX_MIX_DEPTH = %d)", depth[k], BRE_MAX_MIX_DEPTH);
+            return buf;
+        }
+        if (count[k] > BRE_MAX_BXDFS) {
+            snprintf(buf, sizeof(buf), "%d BxDFs after expansion (at most BRE_MAX_BXDFS = %d, the reference's "
+                     "BSDF::MaxBxDFs)", count[k], BRE_MAX_BXDFS);
+            return buf;
+        }
+    }
+    return "";
+}
+
 bre_status set_material_table(bre_ctx *c, const char *fn, const bre_material_ex *materials, int32_t n_materials,
                               const int32_t *triangle_material, int64_t n_triangles, bool wide) {
     if (n_materials < 0 || n_materials > BRE_MAX_MATERIALS)
@@ -236,6 +313,7 @@ bre_status set_material_table(bre_ctx *c, const char *fn, const bre_material_ex 
         c->held.has_interface = false;
         c->held.glossy = false;
         c->held.lobed = false;
+        c->held.mixed = false;
         return BRE_OK;
     }
     if (n_triangles < 0 || n_triangles > BRE_MAX_SCENE_TRIANGLES)
@@ -245,7 +323,7 @@ bre_status set_material_table(bre_ctx *c, const char *fn, const bre_material_ex 
         return fail(c, BRE_ERR_INVALID_ARG, "%s: null material table or triangle_material map", fn);
     std::vector<bre_material_ex> mats(materials, materials + n_materials);
     std::vector<char> is_interface((size_t)n_materials, 0);
-    bool glossy = false, lobed = false;
+    bool glossy = false, lobed = false, mixed = false;
     for (int k = 0; k < n_materials; ++k) {
         bool iface = false;
         const std::string what = check_material(mats[(size_t)k], wide, !c->held.media.empty(), &iface);
@@ -253,6 +331,12 @@ bre_status set_material_table(bre_ctx *c, const char *fn, const bre_material_ex 
         is_interface[(size_t)k] = iface;
         glossy = glossy || mats[(size_t)k].type >= BRE_MATERIAL_MATTE;
         lobed = lobed || mats[(size_t)k].type >= BRE_MATERIAL_ROUGH_GLASS;
+        mixed = mixed || mats[(size_t)k].type == BRE_MATERIAL_MIX;
+    }
+    if (mixed) {
+        int bad = 0;
+        const std::string what = check_mix_table(mats, &bad);
+        if (!what.empty()) return fail(c, BRE_ERR_INVALID_ARG, "%s: material %d has %s", fn, bad, what.c_str());
     }
     for (int64_t i = 0; i < n_triangles; ++i)
         if (triangle_material[i] < -1 || triangle_material[i] >= n_materials)
@@ -263,6 +347,7 @@ bre_status set_material_table(bre_ctx *c, const char *fn, const bre_material_ex 
     c->held.has_interface = false;
     c->held.glossy = glossy;
     c->held.lobed = lobed;
+    c->held.mixed = mixed;
     for (int64_t i = 0; i < n_triangles; ++i)
         if (triangle_material[i] >= 0 && is_interface[(size_t)triangle_material[i]]) c->held.has_interface = true;
     return BRE_OK;
@@ -277,6 +362,18 @@ std::string check_glossy_material(bre_material_ex &m) {
     if (m.type < BRE_MATERIAL_MATTE || m.type > BRE_MATERIAL_METAL)
         return "a type outside BRE_MATERIAL_MATTE .. BRE_MATERIAL_METAL";
     return check_material(m, true, false, &iface);
+}
+
+std::string check_material_table(std::vector<bre_material_ex> &mats, int *bad) {
+    bool mixed = false;
+    for (size_t k = 0; k < mats.size(); ++k) {
+        bool iface;
+        *bad = (int)k;
+        const std::string what = check_material(mats[k], true, false, &iface);
+        if (!what.empty()) return what;
+        mixed = mixed || mats[k].type == BRE_MATERIAL_MIX;
+    }
+    return mixed ? check_mix_table(mats, bad) : std::string();
 }
 
 std::string check_lobed_or_glossy_material(bre_material_ex &m) {
@@ -404,6 +501,8 @@ bre_status upload_scene(bre_ctx *c, const bre_scene *scene) {
         HIPCHK(c, upload(c, dv.mats, hs.mats, &dv.head.mats));
         HIPCHK(c, upload(c, dv.bsdfs, hs.bsdfs, &dv.head.bsdfs));
         HIPCHK(c, upload(c, dv.lobes, hs.lobes, &dv.head.lobes));
+        dv.head.lobes_mx = nullptr;  // only a table that holds a mix has the wide lists
+        if (!hs.lobes_mx.empty()) HIPCHK(c, upload(c, dv.lobes_mx, hs.lobes_mx, &dv.head.lobes_mx));
         HIPCHK(c, hipStreamSynchronize(c->stream));  // the host vectors go out of scope
         dv.hash = hash;
         for (int k = 0; k < 4; ++k) {
@@ -439,6 +538,18 @@ bre_status bre_check_material_ex(const bre_material_ex *material, char *message,
     const std::string what = check_material(m, true, false, &iface);
     if (what.empty()) return BRE_OK;
     if (message && capacity > 0) snprintf(message, (size_t)capacity, "%s", what.c_str());
+    return BRE_ERR_INVALID_ARG;
+}
+
+bre_status bre_check_material_table_ex(const bre_material_ex *materials, int32_t n_materials, char *message,
+                                       int32_t capacity) {
+    if (message && capacity > 0) message[0] = 0;
+    if (!materials || n_materials < 0 || n_materials > BRE_MAX_MATERIALS) return BRE_ERR_INVALID_ARG;
+    std::vector<bre_material_ex> mats(materials, materials + n_materials);
+    int bad = 0;
+    const std::string what = check_material_table(mats, &bad);
+    if (what.empty()) return BRE_OK;
+    if (message && capacity > 0) snprintf(message, (size_t)capacity, "material %d has %s", bad, what.c_str());
     return BRE_ERR_INVALID_ARG;
 }
 

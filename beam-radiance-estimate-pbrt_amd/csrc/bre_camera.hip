@@ -19,6 +19,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <type_traits>
 #include <vector>
 
 #include "bre_device.h"
@@ -318,7 +319,8 @@ __device__ __forceinline__ float power_heuristic(float fpdf, float gpdf) {
 // TIER: 0 = GL false, 1 = GL true, 2 = the table holds a rough glass, uber, translucent or substrate entry: every entry
 // from BRE_MATERIAL_MATTE up goes through the BSDF of any number of lobes with bsdfFlags = BSDF_ALL & ~BSDF_SPECULAR
 // (integrator.cpp:112-113) in TransportMode::Radiance: f and Pdf on both sides of the surface, the BSDF-sampling half
-// over the non-specular lobes only, and nothing at all where none matches (matchingComps == 0).
+// over the non-specular lobes only, and nothing at all where none matches (matchingComps == 0).  TIER 3 (the table
+// holds a mix): the same over the wide lists S.lobes_mx.
 template <bool MED, int TIER>
 __device__ void estimate_direct(const DevScene &S, HaltonDev &hs, f3 p, f3 perr, const PTri &q, f3 wo, int li,
                                 float usx, float usy, float ulx, float uly, float Ld[3], int tri, int med) {
@@ -330,10 +332,13 @@ __device__ void estimate_direct(const DevScene &S, HaltonDev &hs, f3 p, f3 perr,
     // is 0, so there is no shadow ray and no Tr draw (:132-152), and the BSDF-sampling half's Sample_f has
     // matchingComps == 0 (f = 0, pdf = 0).  Ld = 0 without a draw.
     const DevBsdf *gm = nullptr;
-    const DevLobes *lm = nullptr;
+    const typename std::conditional<TIER == 3, DevLobesMx, DevLobes>::type *lm = nullptr;
     (void)lm;
     if (q.mat >= kMatTable) {
-        if constexpr (TIER == 2) {
+        if constexpr (TIER == 3) {
+            lm = &S.lobes_mx[q.mat - kMatTable];
+            if (lm->type == 0 || lm->n_nonspec == 0) return;
+        } else if constexpr (TIER == 2) {
             lm = &S.lobes[q.mat - kMatTable];
             if (lm->type == 0 || lm->n_nonspec == 0) return;
         } else if constexpr (GL) {
@@ -384,7 +389,7 @@ __device__ void estimate_direct(const DevScene &S, HaltonDev &hs, f3 p, f3 perr,
     const f3 sp = ps.p;
     if (light_pdf > 0 && !black3(Li)) {
         float f[3];
-        if constexpr (TIER == 2) {
+        if constexpr (TIER >= 2) {
             if (lm) bsdfn_f(q, *lm, wo, wi, kBsdfNonSpecular, kModeRadiance, f);
             else bsdf_f(q, wo, wi, f);
         } else {
@@ -393,7 +398,7 @@ __device__ void estimate_direct(const DevScene &S, HaltonDev &hs, f3 p, f3 perr,
         }
         const float ad = fabsf(dot3(wi, q.n));
         for (int c = 0; c < 3; ++c) f[c] = f[c] * ad;
-        if constexpr (TIER == 2) scat_pdf = lm ? bsdfn_pdf(q, *lm, wo, wi, kBsdfNonSpecular) : bsdf_pdf(q, wo, wi);
+        if constexpr (TIER >= 2) scat_pdf = lm ? bsdfn_pdf(q, *lm, wo, wi, kBsdfNonSpecular) : bsdf_pdf(q, wo, wi);
         else scat_pdf = (GL && gm) ? bsdf_pdf(q, *gm, wo, wi) : bsdf_pdf(q, wo, wi);
         if (!black3(f)) {
             // VisibilityTester::Tr over Interaction::SpawnRayTo(pShape)
@@ -444,7 +449,7 @@ __device__ void estimate_direct(const DevScene &S, HaltonDev &hs, f3 p, f3 perr,
     {
         float f[3];
         int type;
-        if constexpr (TIER == 2) {
+        if constexpr (TIER >= 2) {
             if (lm) bsdfn_sample(q, *lm, wo, usx, usy, kBsdfNonSpecular, kModeRadiance, wi, scat_pdf, f, type);
             else bsdf_sample(q, wo, usx, usy, wi, scat_pdf, f);
         } else {
@@ -504,7 +509,8 @@ __device__ void estimate_direct(const DevScene &S, HaltonDev &hs, f3 p, f3 perr,
 // kGlossyWaves waves per SIMD; GL false is the code it was before them, held to 80 VGPRs.
 // TIER: 0 = GL false, 1 = GL true, 2 = the BSDF of any number of lobes (see estimate_direct): the bounce samples it
 // with BSDF_ALL in TransportMode::Radiance and specularBounce follows the sampled lobe's type.  The walk is one body:
-// k_camera<MED, GL> runs tiers 0 and 1 under the names and bounds it had, k_camera_tr<MED> tier 2.
+// k_camera<MED, GL> runs tiers 0 and 1 under the names and bounds it had, k_camera_tr<MED> tier 2, k_camera_mx<MED>
+// tier 3 (tier 2 over the wide lists of a table that holds a mix).
 template <bool MED, int TIER>
 __device__ __forceinline__ void camera_walk(const DevScene *__restrict__ Sp, const DevCamera *__restrict__ Cp,
                                             const uint16_t *__restrict__ perms, int iteration, int max_depth,
@@ -629,10 +635,14 @@ __device__ __forceinline__ void camera_walk(const DevScene *__restrict__ Sp, con
                 int type = 0;  // the sampled BxDFType's specular bit; a Lambertian lobe has none
                 bool ok;
                 bool general = false;
-                if constexpr (TIER == 2) general = q.mat >= kMatTable && S.lobes[q.mat - kMatTable].type != 0;
+                if constexpr (TIER == 3) general = q.mat >= kMatTable && S.lobes_mx[q.mat - kMatTable].type != 0;
+                else if constexpr (TIER == 2) general = q.mat >= kMatTable && S.lobes[q.mat - kMatTable].type != 0;
                 else if constexpr (GL) general = q.mat >= kMatTable && S.bsdfs[q.mat - kMatTable].type != 0;
                 if (general) {
-                    if constexpr (TIER == 2)
+                    if constexpr (TIER == 3)
+                        ok = bsdfn_sample(q, S.lobes_mx[q.mat - kMatTable], wo, ux, uy, kBsdfAll, kModeRadiance, wi, pdf,
+                                          f, type);
+                    else if constexpr (TIER == 2)
                         ok = bsdfn_sample(q, S.lobes[q.mat - kMatTable], wo, ux, uy, kBsdfAll, kModeRadiance, wi, pdf, f,
                                           type);
                     else
@@ -696,6 +706,20 @@ __global__ __launch_bounds__(kCamBlock, kGlossyWaves) void k_camera_tr(const Dev
                         valid, surface, flags, shard_rank, shard_count, shard_block, classes, planes);
 }
 
+template <bool MED>
+__global__ __launch_bounds__(kCamBlock, kMixWaves) void k_camera_mx(const DevScene *__restrict__ Sp, const DevCamera *__restrict__ Cp,
+                                                     const uint16_t *__restrict__ perms, int iteration, int max_depth,
+                                                     int render_surfaces, int render_media, int64_t nslots,
+                                                     float *__restrict__ so, float *__restrict__ sp_,
+                                                     float *__restrict__ sd, float *__restrict__ st,
+                                                     int32_t *__restrict__ spix, int32_t *__restrict__ valid,
+                                                     float *__restrict__ surface, unsigned int *__restrict__ flags,
+                                                     int shard_rank, int shard_count, int shard_block, int classes,
+                                                     int planes) {
+    camera_walk<MED, 3>(Sp, Cp, perms, iteration, max_depth, render_surfaces, render_media, nslots, so, sp_, sd, st, spix,
+                        valid, surface, flags, shard_rank, shard_count, shard_block, classes, planes);
+}
+
 __global__ void k_compact(int64_t nslots_total, const int32_t *__restrict__ valid, const int64_t *__restrict__ offs,
                           const float *__restrict__ so, const float *__restrict__ sp_, const float *__restrict__ sd,
                           const float *__restrict__ st, const int32_t *__restrict__ spix, float *__restrict__ o,
@@ -733,7 +757,8 @@ hipError_t launch_camera(const DevScene *scene, int stack_depth, const DevCamera
                            s.valid, surface, flags, shard_rank, shard_count, shard_block, classes < 1 ? 1 : classes,
                            planes);
     };
-    if (tier == 2) media ? go(k_camera_tr<true>) : go(k_camera_tr<false>);
+    if (tier == 3) media ? go(k_camera_mx<true>) : go(k_camera_mx<false>);
+    else if (tier == 2) media ? go(k_camera_tr<true>) : go(k_camera_tr<false>);
     else if (tier == 1) media ? go(k_camera<true, true>) : go(k_camera<false, true>);
     else media ? go(k_camera<true, false>) : go(k_camera<false, false>);
     return hipGetLastError();

@@ -115,9 +115,9 @@ __global__ __launch_bounds__(256) void k_check_bsdf(int64_t n, const float *__re
 
 // kind 14: the BSDF of any number of lobes (bre_trace.h) on n records of 11 floats: those of kind 13, then the
 // transport mode (0: Importance) and the flag set (0: BSDF_ALL, 1: BSDF_ALL & ~BSDF_SPECULAR); the same 12 words out
-__global__ __launch_bounds__(256) void k_check_lobes(int64_t n, const float *__restrict__ x,
-                                                     const DevLobes *__restrict__ table, int n_table,
-                                                     float *__restrict__ y) {
+template <class REC>
+__device__ __forceinline__ void check_lobes(int64_t n, const float *__restrict__ x, const REC *__restrict__ table,
+                                            int n_table, float *__restrict__ y) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const float *r = x + 11 * i;
@@ -125,7 +125,7 @@ __global__ __launch_bounds__(256) void k_check_lobes(int64_t n, const float *__r
     float *o = y + 12 * i;
     for (int j = 0; j < 12; ++j) o[j] = 0.f;
     if (k < 0 || k >= n_table) return;
-    const DevLobes &m = table[k];  // read in place: its lobes are indexed at run time
+    const REC &m = table[k];  // read in place: its lobes are indexed at run time
     const int mode = r[9] != 0.f ? kModeRadiance : kModeImportance;
     const int flags = r[10] != 0.f ? kBsdfNonSpecular : kBsdfAll;
     PTri q{};
@@ -153,7 +153,26 @@ __global__ __launch_bounds__(256) void k_check_lobes(int64_t n, const float *__r
     o[11] = bsdfn_pdf(q, m, wo, wi2, flags);
 }
 
+__global__ __launch_bounds__(256) void k_check_lobes(int64_t n, const float *__restrict__ x,
+                                                     const DevLobes *__restrict__ table, int n_table,
+                                                     float *__restrict__ y) {
+    check_lobes(n, x, table, n_table, y);
+}
+// ... over the wide lists of a table that holds a mix
+__global__ __launch_bounds__(256) void k_check_lobes_mx(int64_t n, const float *__restrict__ x,
+                                                        const DevLobesMx *__restrict__ table, int n_table,
+                                                        float *__restrict__ y) {
+    check_lobes(n, x, table, n_table, y);
+}
+
 }  // namespace
+
+hipError_t launch_check_lobes_mx(int64_t n, const float *x, const DevLobesMx *table, int n_table, float *y,
+                                 hipStream_t s) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_check_lobes_mx, dim3((unsigned int)((n + 255) / 256)), dim3(256), 0, s, n, x, table, n_table, y);
+    return hipGetLastError();
+}
 
 hipError_t launch_check_lobes(int64_t n, const float *x, const DevLobes *table, int n_table, float *y, hipStream_t s) {
     if (n <= 0) return hipSuccess;

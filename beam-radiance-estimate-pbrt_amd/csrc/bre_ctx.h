@@ -177,6 +177,7 @@ struct SceneState {
     bool has_interface = false;      // ... one of which leads to a BRE_MATERIAL_INTERFACE entry
     bool glossy = false;             // the table holds a type >= BRE_MATERIAL_MATTE: the passes' glossy kernels
     bool lobed = false;              // ... a type >= BRE_MATERIAL_ROUGH_GLASS: the kernels with the N-lobe BSDF
+    bool mixed = false;              // ... a BRE_MATERIAL_MIX: the tier-3 kernels over the wide lobe lists
     // bre_set_media: the table (grid_density pointing into media_grid), the triangles' (inside, outside) pairs
     // interleaved, the delta lights' media, the camera's; media_key: all of it as bytes, the grids for the pointers
     std::vector<bre_medium> media;
@@ -189,7 +190,7 @@ struct SceneState {
 // What upload_scene keeps on the device, and the host bytes it compares the next call's scene against
 struct SceneDevice {
     // geometry: triangles, BVHAccel nodes + primitive order, scene.lights, the delta lights and the materials
-    DevMem tris, nodes, prims, light_tri, light_func, light_cdf, dlights, mats, bsdfs, lobes;
+    DevMem tris, nodes, prims, light_tri, light_func, light_cdf, dlights, mats, bsdfs, lobes, lobes_mx;
     DevScene head;                     // its fields of the record below
     uint64_t hash = 0;                 // hash of the uploaded triangles, lights and materials (0: none)
     // the uploaded triangles' bytes, the lights', the materials' and the map's: a hash match is confirmed by memcmp
@@ -329,6 +330,9 @@ const char *scene_state_differs(const SceneState &a, const SceneState &b);
 std::string check_glossy_material(bre_material_ex &m);
 // ... the same for every type from BRE_MATERIAL_MATTE up (bre_device_check kind 14)
 std::string check_lobed_or_glossy_material(bre_material_ex &m);
+// a whole table as bre_set_materials_ex checks it on a context without media, the rules a mix brings included
+// (records clamped in place); "" or what material *bad has
+std::string check_material_table(std::vector<bre_material_ex> &mats, int *bad);
 // bre_api_build.hip
 bre_status build(bre_ctx *c, int64_t n, const BeamView &in);
 

@@ -67,6 +67,9 @@ struct FrameMed : Frame {
 // (bre_set_materials_ex, types 8 .. 11): every entry from BRE_MATERIAL_MATTE up scatters through the BSDF of any
 // number of lobes (bsdfn_sample with BSDF_ALL in TransportMode::Importance); frames in LDS as for GL.  The walk is one
 // body: k_photons<MODE, MED, GL> runs tiers 0 and 1 under the names and bounds it had, k_photons_tr<MODE, MED> tier 2.
+// TIER 3 (the table holds a BRE_MATERIAL_MIX): tier 2 over the wide lists (S.lobes_mx: up to BRE_MAX_BXDFS lobes, each
+// under its chain of ScaledBxDF scales), in k_photons_mx<MODE, MED>.  A triangle whose own material is a mirror or a
+// smooth glass keeps the one-lobe specular path in every tier.
 constexpr int kFrameWords = 19;  // o, d, tmax, p, perr, tri, depth, beta, med
 template <int MODE, bool MED, int TIER>
 __device__ __forceinline__ void photon_walk(const DevScene *__restrict__ Sp, int64_t n, uint64_t seq0, int max_depth,
@@ -256,12 +259,16 @@ __device__ __forceinline__ void photon_walk(const DevScene *__restrict__ Sp, int
                     f3 wil, wiw;
                     float pdf, fr[3];
                     bool world = false;  // GL: wiw is BSDF::Sample_f's own LocalToWorld(wi)
-                    if constexpr (TIER == 2) world = q.mat >= kMatTable && S.lobes[q.mat - kMatTable].type != 0;
+                    if constexpr (TIER == 3) world = q.mat >= kMatTable && S.lobes_mx[q.mat - kMatTable].type != 0;
+                    else if constexpr (TIER == 2) world = q.mat >= kMatTable && S.lobes[q.mat - kMatTable].type != 0;
                     else if constexpr (GL) world = q.mat >= kMatTable && S.bsdfs[q.mat - kMatTable].type != 0;
                     if (world) {
                         int type;
                         pdf = 0.f;
-                        if constexpr (TIER == 2)
+                        if constexpr (TIER == 3)
+                            bsdfn_sample(q, S.lobes_mx[q.mat - kMatTable], wo, ux, uy, kBsdfAll, kModeImportance, wiw,
+                                         pdf, fr, type);
+                        else if constexpr (TIER == 2)
                             bsdfn_sample(q, S.lobes[q.mat - kMatTable], wo, ux, uy, kBsdfAll, kModeImportance, wiw, pdf,
                                          fr, type);
                         else
@@ -349,6 +356,15 @@ __global__ __launch_bounds__(kPhotonBlock, kGlossyWaves) void k_photons_tr(const
     photon_walk<MODE, MED, 2>(Sp, n, seq0, max_depth, radius, counts, offsets, bs, be, br, bp, over);
 }
 
+template <int MODE, bool MED>
+__global__ __launch_bounds__(kPhotonBlock, kMixWaves) void k_photons_mx(const DevScene *__restrict__ Sp, int64_t n, uint64_t seq0,
+                                                          int max_depth, float radius, int32_t *__restrict__ counts,
+                                                          const int64_t *__restrict__ offsets, float *__restrict__ bs,
+                                                          float *__restrict__ be, float *__restrict__ br,
+                                                          float *__restrict__ bp, int over) {
+    photon_walk<MODE, MED, 3>(Sp, n, seq0, max_depth, radius, counts, offsets, bs, be, br, bp, over);
+}
+
 // The single-trace form's copy: photon i's first min(count, cap) beams from its slots to its offsets.
 // Each wave copies the beams of its 64 photons as one run: lane j takes the wave's j-th beam (owner by
 // a search of the wave's prefix sums in LDS), so the writes of consecutive lanes are consecutive and a
@@ -416,6 +432,12 @@ hipError_t launch_photons(const DevScene *scene, int stack_depth, int64_t n, uin
         hipLaunchKernelGGL(kernel, dim3(grid_of(n)), dim3(kPhotonBlock), lds, s, scene, n, seq0, max_depth, radius,
                            counts, offsets, out.start, out.end, out.radius, out.power, ov);
     };
+    if (tier == 3) {
+        if (mode == 1) media ? go(k_photons_mx<1, true>, over) : go(k_photons_mx<1, false>, over);
+        else if (mode == 2) media ? go(k_photons_mx<2, true>, over) : go(k_photons_mx<2, false>, over);
+        else media ? go(k_photons_mx<0, true>, 0) : go(k_photons_mx<0, false>, 0);
+        return hipGetLastError();
+    }
     if (tier == 2) {
         if (mode == 1) media ? go(k_photons_tr<1, true>, over) : go(k_photons_tr<1, false>, over);
         else if (mode == 2) media ? go(k_photons_tr<2, true>, over) : go(k_photons_tr<2, false>, over);

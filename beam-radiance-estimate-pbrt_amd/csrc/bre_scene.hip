@@ -248,6 +248,68 @@ DevLobes make_lobes(const bre_material_ex &m) {
     return b;
 }
 
+// The BxDFs a table entry brings to a mix that names it (mixmat.cpp:54-55: the child's own
+// ComputeScatteringFunctions, allowMultipleLobes true as both walks pass it): a mirror's SpecularReflection under
+// FresnelNoOp (mirror.cpp:50-56), a smooth glass's FresnelSpecular (glass.cpp:71-73), else the entry's wide list, which
+// for a mix already carries its scales
+static DevLobesMx child_lobes(const bre_material_ex &m, const DevLobesMx &own) {
+    if (m.type != BRE_MATERIAL_MIRROR && m.type != BRE_MATERIAL_GLASS) return own;
+    DevLobesMx b{};
+    DevLobeMx L{};
+    L.ax = L.ay = L.etaA = L.etaB = 1.f;
+    for (int k = 0; k < 3; ++k) L.c[k] = m.kr[k];
+    if (m.type == BRE_MATERIAL_MIRROR) {
+        if (black3(m.kr)) return b;
+        L.kind = kLobeSpecNoOp;
+        L.type = kBsdfReflection | kBsdfSpecular;
+    } else {
+        if (black3(m.kr) && black3(m.kt)) return b;
+        L.kind = kLobeFresnelSpec;
+        L.type = kBsdfReflection | kBsdfTransmission | kBsdfSpecular;
+        for (int k = 0; k < 3; ++k) L.s[k] = m.kt[k];
+        L.etaB = m.eta;
+    }
+    b.lobe[b.n++] = L;
+    return b;
+}
+
+void make_lobes_mx(const bre_material_ex *table, int n, std::vector<DevLobesMx> *out) {
+    out->assign((size_t)n, DevLobesMx{});
+    for (int k = 0; k < n; ++k) {
+        const bre_material_ex &m = table[k];
+        DevLobesMx &w = (*out)[(size_t)k];
+        if (m.type != BRE_MATERIAL_MIX) {
+            const DevLobes b = make_lobes(m);  // type 0 below BRE_MATERIAL_MATTE
+            w.type = b.type;
+            w.n = b.n;
+            w.n_nonspec = b.n_nonspec;
+            for (int i = 0; i < b.n; ++i) static_cast<DevLobe &>(w.lobe[i]) = b.lobe[i];
+            continue;
+        }
+        w.type = BRE_MATERIAL_MIX;
+        // s1 = scale->Evaluate(*si).Clamp() (the setter has clamped it), s2 = (Spectrum(1.f) - s1).Clamp()
+        float s[2][3];
+        for (int c = 0; c < 3; ++c) {
+            s[0][c] = m.amount[c];
+            s[1][c] = clampf_ref(1.f - s[0][c], 0.f, kMaxFloat);
+        }
+        for (int side = 0; side < 2; ++side) {
+            const int ch = m.mix_child[side];
+            if (ch < 0 || ch >= k) continue;  // refused by the setter
+            const DevLobesMx from = child_lobes(table[ch], (*out)[(size_t)ch]);
+            for (int i = 0; i < from.n && w.n < kMaxLobesMx; ++i) {
+                DevLobeMx &L = w.lobe[w.n++];
+                L = from.lobe[i];
+                if (L.nscale < BRE_MAX_MIX_DEPTH) {
+                    for (int c = 0; c < 3; ++c) L.scale[L.nscale][c] = s[side][c];
+                    ++L.nscale;
+                }
+                if (!(L.type & kBsdfSpecular)) ++w.n_nonspec;
+            }
+        }
+    }
+}
+
 void prepare_geometry(const bre_scene *s, HostScene *out, const bre_light *lights, int n_lights,
                       const MaterialMap &mm) {
     DevScene &d = out->head;
@@ -257,8 +319,17 @@ void prepare_geometry(const bre_scene *s, HostScene *out, const bre_light *light
     out->mats.resize((size_t)mm.n_mats);
     out->bsdfs.resize((size_t)mm.n_mats);
     // the lobe lists only where a kernel reads them: a table with a rough glass, uber, translucent or substrate entry
-    bool lobed = false;
-    for (int k = 0; k < mm.n_mats; ++k) lobed = lobed || mm.mats[k].type >= BRE_MATERIAL_ROUGH_GLASS;
+    bool lobed = false, mixed = false;
+    for (int k = 0; k < mm.n_mats; ++k) {
+        lobed = lobed || mm.mats[k].type >= BRE_MATERIAL_ROUGH_GLASS;
+        mixed = mixed || mm.mats[k].type == BRE_MATERIAL_MIX;
+    }
+    // a table that holds a mix: the wide lists instead, which the tier-3 kernels read
+    out->lobes_mx.clear();
+    if (mixed) {
+        make_lobes_mx(mm.mats, mm.n_mats, &out->lobes_mx);
+        lobed = false;
+    }
     out->lobes.assign(lobed ? (size_t)mm.n_mats : 0, DevLobes{});
     for (int k = 0; k < mm.n_mats; ++k) {
         const bre_material_ex &m = mm.mats[k];
@@ -323,7 +394,8 @@ void prepare_geometry(const bre_scene *s, HostScene *out, const bre_light *light
             T.mat = none ? kMatNone : kMatTable + mm.tri_mat[i];
             if (m.type == BRE_MATERIAL_INTERFACE) T.mat = kMatInterface;  // GetMaterial() == nullptr: no BSDF
             if (m.type >= BRE_MATERIAL_ROUGH_GLASS) {
-                T.mat = out->lobes[(size_t)mm.tri_mat[i]].n == 0 ? kMatNone : kMatTable + mm.tri_mat[i];
+                const int nl = mixed ? out->lobes_mx[(size_t)mm.tri_mat[i]].n : out->lobes[(size_t)mm.tri_mat[i]].n;
+                T.mat = nl == 0 ? kMatNone : kMatTable + mm.tri_mat[i];
             } else if (m.type >= BRE_MATERIAL_MATTE) {
                 const DevBsdf &b = out->bsdfs[(size_t)mm.tri_mat[i]];
                 T.mat = b.lobes == 0 ? kMatNone : kMatTable + mm.tri_mat[i];

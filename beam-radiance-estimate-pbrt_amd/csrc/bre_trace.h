@@ -11,6 +11,7 @@
 #include "bre_math.h"
 #include "bre_views.h"
 
+#include <type_traits>
 #include <vector>
 
 namespace bre {
@@ -222,6 +223,27 @@ struct DevLobes {
     DevLobe lobe[kMaxLobes];
 };
 
+// The wide lobe list (a table that holds a BRE_MATERIAL_MIX): every entry from BRE_MATERIAL_MATTE up as above, and a
+// mix as MixMaterial::ComputeScatteringFunctions leaves the BSDF (mixmat.cpp:51-63): the first child's BxDFs in order,
+// then the second's, each a ScaledBxDF once per enclosing mix.  A lobe carries that chain of scales innermost first:
+// ScaledBxDF::f is scale * bxdf->f in float, so a nest is s_outer * (s_inner * f), which is not (s_outer * s_inner) * f
+// in bits: the scales are not multiplied on the host.  A scaled lobe's type and Pdf are its inner lobe's
+// (reflection.h:230-232, reflection.cpp:108-110).  Under a mix a mirror and a smooth glass are lobes among others:
+constexpr int kLobeSpecNoOp = kLobeBlend + 1;     // SpecularReflection(c, FresnelNoOp): mirror.cpp:50-56
+constexpr int kLobeFresnelSpec = kLobeBlend + 2;  // FresnelSpecular(c, s, etaA, etaB, mode): glass.cpp:71-73
+constexpr int kMaxLobesMx = BRE_MAX_BXDFS;
+struct DevLobeMx : DevLobe {
+    int nscale;                             // enclosing mixes: 0 for the own lobe of an entry that is no mix
+    float scale[BRE_MAX_MIX_DEPTH][3];      // innermost first
+};
+struct DevLobesMx {
+    int type;         // BRE_MATERIAL_MATTE .. _METAL, _ROUGH_GLASS .. _MIX; 0: a mirror, glass or interface
+    int n;
+    int n_nonspec;
+    int pad;
+    DevLobeMx lobe[kMaxLobesMx];
+};
+
 // One node of the scene's bounding volume hierarchy: the reference's BVHAccel LinearBVHNode
 // (src/accelerators/bvh.cpp, 32 B, depth-first order: an interior node's first child follows it).
 struct SceneNode {
@@ -288,6 +310,8 @@ struct DevScene {
     int n_media, cam_med;
     const DevBsdf *bsdfs;  // beside mats, one per table entry (bre_set_materials_ex); last: the layout before it stays
     const DevLobes *lobes; // beside bsdfs, one per table entry; read only by the kernels of a table with a type >= 8
+    const DevLobesMx *lobes_mx; // one per table entry, only where the table holds a BRE_MATERIAL_MIX (else null): read
+                                // by the tier-3 kernels instead of lobes
 };
 
 // Host side of the scene: everything prepare_geometry derives, in host memory; the context uploads
@@ -303,6 +327,7 @@ struct HostScene {
     std::vector<bre_material> mats;
     std::vector<DevBsdf> bsdfs;
     std::vector<DevLobes> lobes;
+    std::vector<DevLobesMx> lobes_mx;
     int depth = 0;  // deepest node of the BVH (root = 1)
 };
 
@@ -327,6 +352,9 @@ DevBsdf make_bsdf(const bre_material_ex &m);
 // a table entry as its material leaves the BSDF, any number of lobes: the above for types 4 .. 6, and glass.cpp:45-92,
 // uber.cpp:45-101, translucent.cpp:45-80, substrate.cpp:45-65 for types 8 .. 11; type 0 below BRE_MATERIAL_MATTE
 DevLobes make_lobes(const bre_material_ex &m);
+// the wide lists of a checked table that holds a mix (children before their mix, the expansions within kMaxLobesMx):
+// entry k as make_lobes leaves it with no scale, a mix as mixmat.cpp:51-63 leaves it, type 0 for the others
+void make_lobes_mx(const bre_material_ex *table, int n, std::vector<DevLobesMx> *out);
 // a medium as its constructor leaves it: sigma_t = sigma_a + sigma_s per channel; for a grid, channel 0 of it,
 // 1 / max_density and `d_density`, the device copy of the grid (the grid arguments are not read otherwise)
 DevMedium make_medium(int type, const float sigma_a[3], const float sigma_s[3], float g, const int32_t grid_n[3],
@@ -1285,23 +1313,80 @@ BRE_TD void loben_sample(const DevLobe &L, f3 wo, float u0, float u1, int mode, 
 }
 
 BRE_TD bool lobe_matches(const DevLobe &L, int flags) { return (L.type & flags) == L.type; }  // BxDF::MatchesFlags
+
+// ---- the lobes of a wide list (DevLobeMx): the two specular lobes a mix brings, and ScaledBxDF around any lobe ----
+// ScaledBxDF's scale * f (reflection.cpp:97-106) once per enclosing mix, innermost first; nothing for a DevLobe
+BRE_TD void lobe_scale(const DevLobe &, float[3]) {}
+BRE_TD void lobe_scale(const DevLobeMx &L, float f[3]) {
+    for (int k = 0; k < L.nscale; ++k)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) f[c] = L.scale[k][c] * f[c];
+}
+// BxDF::f and Pdf through the scales: loben_f leaves 0 for the two new kinds as for every specular lobe, and
+// ScaledBxDF::Pdf is the inner Pdf
+BRE_TD void lobex_f(const DevLobe &L, f3 wo, f3 wi, int mode, float f[3]) { loben_f(L, wo, wi, mode, f); }
+BRE_TD void lobex_f(const DevLobeMx &L, f3 wo, f3 wi, int mode, float f[3]) {
+    loben_f(L, wo, wi, mode, f);
+    lobe_scale(L, f);
+}
+// Sample_f; `type` arrives as the lobe's own and is changed only by FresnelSpecular (reflection.cpp:486-487, 506-507)
+BRE_TD void lobex_sample(const DevLobeMx &L, f3 wo, float u0, float u1, int mode, f3 &wi, float &pdf, float f[3],
+                         int &type) {
+    if (L.kind == kLobeSpecNoOp) {  // SpecularReflection::Sample_f under FresnelNoOp, reflection.cpp:136-143
+        wi = mk(-wo.x, -wo.y, wo.z);
+        pdf = 1.f;
+        const float ac = fabsf(wi.z);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) f[c] = (1.f * L.c[c]) / ac;
+    } else if (L.kind == kLobeFresnelSpec) {  // FresnelSpecular::Sample_f, reflection.cpp:477-511 (R = c, T = s)
+        const float F = fr_dielectric(wo.z, L.etaA, L.etaB);
+        if (u0 < F) {
+            wi = mk(-wo.x, -wo.y, wo.z);
+            type = kBsdfSpecular | kBsdfReflection;
+            pdf = F;
+            const float ac = fabsf(wi.z);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) f[c] = (F * L.c[c]) / ac;
+        } else {
+            const bool entering = wo.z > 0;
+            const float eta_i = entering ? L.etaA : L.etaB, eta_t = entering ? L.etaB : L.etaA;
+            const f3 n = (wo.z < 0.f) ? mk(-0.f, -0.f, -1.f) : mk(0.f, 0.f, 1.f);
+            if (!refract(wo, n, eta_i / eta_t, wi)) return;  // pdf stays 0
+            type = kBsdfSpecular | kBsdfTransmission;
+            pdf = 1 - F;
+            const float ac = fabsf(wi.z);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                float ft = L.s[c] * (1 - F);
+                if (mode == kModeRadiance) ft *= (eta_i * eta_i) / (eta_t * eta_t);
+                f[c] = ft / ac;
+            }
+        }
+    } else {
+        loben_sample(L, wo, u0, u1, mode, wi, pdf, f);
+    }
+    lobe_scale(L, f);
+}
 // BSDF::f, reflection.cpp:670-683: the matching lobes on the side of the geometric normal that wi lies on
-BRE_TD void bsdfn_f(const PTri &q, const DevLobes &m, f3 wo_w, f3 wi_w, int flags, int mode, float f[3]) {
+// (REC: DevLobes, or DevLobesMx with its scales and its two more kinds; the walk is the same)
+template <class REC>
+BRE_TD void bsdfn_f(const PTri &q, const REC &m, f3 wo_w, f3 wi_w, int flags, int mode, float f[3]) {
     f[0] = f[1] = f[2] = 0.f;
     const f3 wi = to_local(q, wi_w), wo = to_local(q, wo_w);
     if (wo.z == 0) return;
     const bool reflect = dot3(wi_w, q.n) * dot3(wo_w, q.n) > 0;
     for (int i = 0; i < m.n; ++i) {
-        const DevLobe &L = m.lobe[i];
+        const auto &L = m.lobe[i];
         if (!lobe_matches(L, flags) || !(L.type & (reflect ? kBsdfReflection : kBsdfTransmission))) continue;
         float fl[3];
-        loben_f(L, wo, wi, mode, fl);
+        lobex_f(L, wo, wi, mode, fl);
 #pragma unroll
         for (int c = 0; c < 3; ++c) f[c] = f[c] + fl[c];
     }
 }
 // BSDF::Pdf, reflection.cpp:770-785
-BRE_TD float bsdfn_pdf(const PTri &q, const DevLobes &m, f3 wo_w, f3 wi_w, int flags) {
+template <class REC>
+BRE_TD float bsdfn_pdf(const PTri &q, const REC &m, f3 wo_w, f3 wi_w, int flags) {
     if (m.n == 0) return 0.f;
     const f3 wo = to_local(q, wo_w), wi = to_local(q, wi_w);
     if (wo.z == 0) return 0.f;
@@ -1318,7 +1403,8 @@ BRE_TD float bsdfn_pdf(const PTri &q, const DevLobes &m, f3 wo_w, f3 wi_w, int f
 // lobes, u[0] remapped, the lobe's Sample_f; unless that lobe is specular, the other matching lobes' Pdf added and f
 // taken again over all of them (:749-764).  Returns false where Sample_f returns 0 before f is known (no matching
 // lobe, wo.z == 0 with pdf untouched, pdf == 0); type is then 0.
-BRE_TD bool bsdfn_sample(const PTri &q, const DevLobes &m, f3 wo_w, float u0, float u1, int flags, int mode, f3 &wi_w,
+template <class REC>
+BRE_TD bool bsdfn_sample(const PTri &q, const REC &m, f3 wo_w, float u0, float u1, int flags, int mode, f3 &wi_w,
                          float &pdf, float f[3], int &type) {
     f[0] = f[1] = f[2] = 0.f;
     type = 0;
@@ -1336,15 +1422,22 @@ BRE_TD bool bsdfn_sample(const PTri &q, const DevLobes &m, f3 wo_w, float u0, fl
             at = i;
             break;
         }
-    const DevLobe &L = m.lobe[at];
+    const auto &L = m.lobe[at];
     const float ur = smin(u0 * (float)n - (float)comp, kOneMinusEps);
     const f3 wo = to_local(q, wo_w);
     if (wo.z == 0) return false;
     pdf = 0.f;
     f3 wi = mk(0.f, 0.f, 0.f);
-    loben_sample(L, wo, ur, u1, mode, wi, pdf, f);
-    if (pdf == 0) return false;  // f is whatever the lobe left: the callers read it only behind pdf != 0
-    type = L.type;
+    if constexpr (std::is_same<REC, DevLobes>::value) {  // the statements tier 2 had, in their order
+        loben_sample(L, wo, ur, u1, mode, wi, pdf, f);
+        if (pdf == 0) return false;  // f is whatever the lobe left: the callers read it only behind pdf != 0
+        type = L.type;
+    } else {
+        int sampled = L.type;  // *sampledType = bxdf->type before the lobe's Sample_f (:737), which may change it
+        lobex_sample(L, wo, ur, u1, mode, wi, pdf, f, sampled);
+        if (pdf == 0) return false;
+        type = sampled;
+    }
     wi_w = to_world(q, wi);
     const bool mix = !(L.type & kBsdfSpecular) && n > 1;
     if (mix)
@@ -1355,10 +1448,10 @@ BRE_TD bool bsdfn_sample(const PTri &q, const DevLobes &m, f3 wo_w, float u0, fl
         const bool reflect = dot3(wi_w, q.n) * dot3(wo_w, q.n) > 0;
         f[0] = f[1] = f[2] = 0.f;
         for (int i = 0; i < m.n; ++i) {
-            const DevLobe &K = m.lobe[i];
+            const auto &K = m.lobe[i];
             if (!lobe_matches(K, flags) || !(K.type & (reflect ? kBsdfReflection : kBsdfTransmission))) continue;
             float fl2[3];
-            loben_f(K, wo, wi, mode, fl2);
+            lobex_f(K, wo, wi, mode, fl2);
 #pragma unroll
             for (int c = 0; c < 3; ++c) f[c] = f[c] + fl2[c];
         }
@@ -1409,6 +1502,9 @@ hipError_t launch_check_specular(int64_t n, const float *x, float *y, hipStream_
 hipError_t launch_check_bsdf(int64_t n, const float *x, const DevBsdf *table, int n_table, float *y, hipStream_t s);
 // kind 14 (bre_check.hip): bsdfn_sample, bsdfn_f and bsdfn_pdf on n records of 11 floats against `table`, 12 words out
 hipError_t launch_check_lobes(int64_t n, const float *x, const DevLobes *table, int n_table, float *y, hipStream_t s);
+// kind 14 over a table that holds a mix: the same records against the wide lists
+hipError_t launch_check_lobes_mx(int64_t n, const float *x, const DevLobesMx *table, int n_table, float *y,
+                                 hipStream_t s);
 
 // dynamic LDS of a photon / camera launch: the scene traversal stack of every thread of a block
 inline size_t scene_stack_bytes(int stack_depth, int block) {
@@ -1417,6 +1513,8 @@ inline size_t scene_stack_bytes(int stack_depth, int block) {
 
 // waves per SIMD the glossy (GL) instantiations of k_photons and k_camera are bounded to; the others keep 6
 constexpr int kGlossyWaves = 2;
+// ... and the tier-3 kernels (k_photons_mx, k_camera_mx): the walk of tier 2 with a scale chain per lobe
+constexpr int kMixWaves = 2;
 
 // photon pass launchers (bre_photon.hip)
 // dynamic LDS of a photon launch: the traversal stack and, for the glossy kernels, max_depth suspended frames a thread
@@ -1425,7 +1523,8 @@ size_t photon_lds_bytes(int stack_depth, int max_depth, bool glossy);
 // beams); 2: write the first `over` beams to per-photon slots and count them all (single-trace form)
 // `media`: the context holds media (the kernels that carry a medium per ray); `tier`: 1 where its table holds a
 // plastic, metal or matte entry (the kernels with the two-lobe BSDF), 2 where it holds a rough glass, uber,
-// translucent or substrate entry (the kernels with the BSDF of any number of lobes), else 0
+// translucent or substrate entry (the kernels with the BSDF of any number of lobes), 3 where it holds a mix (the same
+// over the wide lists, DevScene::lobes_mx), else 0
 hipError_t launch_photons(const DevScene *scene, int stack_depth, int64_t n, uint64_t seq0, int max_depth,
                           float radius, int32_t *counts, const int64_t *offsets, const BeamOut &out, int mode,
                           int over, bool media, int tier, hipStream_t s);

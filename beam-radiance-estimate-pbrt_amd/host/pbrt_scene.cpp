@@ -1,6 +1,8 @@
 // pbrt_scene.cpp — see pbrt_scene.h.
 #include "pbrt_scene.h"
 
+#include "bre.h"
+
 #include <array>
 #include <cmath>
 #include <cstdarg>
@@ -8,6 +10,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <memory>
 #include <sstream>
 #include <utility>
 
@@ -493,6 +496,10 @@ struct Material {
     // "uber" (pkd, ks, kr, kt, eta, roughness, u / vroughness with 0 = not given, opacity), "translucent" (pkd, ks,
     // "reflect" in kr and "transmit" in kt, roughness), "substrate" (pkd, ks, u / vroughness)
     float opacity[3] = {1.f, 1.f, 1.f};
+    // kParseMaterials: "mix" (api.cpp:430-446, CreateMixMaterial mixmat.cpp:66-72): its two materials as they were
+    // when the statement was read, and "amount" (default 0.5)
+    std::shared_ptr<Material> child[2];
+    float amount[3] = {0.5f, 0.5f, 0.5f};
 };
 
 struct GraphicsState {
@@ -539,7 +546,8 @@ class Parser {
     void MakeMedium(Lexer &lx, int line, const std::string &name, const ParamSet &ps);
     // `named`: from MakeNamedMaterial (the direct statement Material "glass" stays unsupported)
     void MakeMaterial(Lexer &lx, int line, const std::string &type, const ParamSet &ps, Material *m, bool named);
-    int SpecularIndex(Lexer &lx, int line, const Material &m);
+    // `entry`: a Lambertian matte gets a table entry too (a mix's child is named by table index)
+    int SpecularIndex(Lexer &lx, int line, const Material &m, bool entry = false);
     void Camera(Lexer &lx, int line, const std::string &name, const ParamSet &ps);
     void Concat(const Xform &t) {
         ctm_ = ctm_ * t;
@@ -752,9 +760,37 @@ void Parser::MakeMaterial(Lexer &lx, int line, const std::string &type, const Pa
         m->none = true;
         return;
     }
-    if (materialsOk_ && (type == "glass" || type == "uber" || type == "translucent" || type == "substrate")) {
+    if (materialsOk_ && type == "mix") {
+        // api.cpp:430-446: an undeclared child is a matte made from this statement's own parameters
+        if (ps.Has("amount") && ps.FindFloats("amount")) {
+            m->amount[0] = m->amount[1] = m->amount[2] = ps.FindOneFloat("amount", 0.5f);
+        } else if (ps.Has("amount") && !ps.FindOneSpectrum("amount", m->amount)) {
+            Error(lx, line, "mix \"amount\" must be an rgb or xyz value (textures are not supported); using 0.5");
+            m->amount[0] = m->amount[1] = m->amount[2] = 0.5f;
+        }
+        const std::string names[2] = {ps.FindOneString("namedmaterial1", ""), ps.FindOneString("namedmaterial2", "")};
+        ps.FindOneString("type", "");
+        for (int k = 0; k < 2; ++k) {
+            m->child[k] = std::make_shared<Material>();
+            const auto it = namedMaterials_.find(names[k]);
+            if (it != namedMaterials_.end()) {
+                *m->child[k] = it->second;
+            } else {
+                Error(lx, line, "Named material \"%s\" undefined.  Using \"matte\"", names[k].c_str());
+                MakeMaterial(lx, line, "matte", ps, m->child[k].get(), named);
+            }
+        }
+        ReportUnused(lx, line, ps);
+        return;
+    }
+    // SubsurfaceMaterial and KdSubsurfaceMaterial add the BSDF GlassMaterial adds (subsurface.cpp:46-98,
+    // kdsubsurface.cpp:45-98 against glass.cpp:45-92) and a BSSRDF, which photonbeam.cpp never reads: under
+    // kParseMaterials they are their dielectric boundary, a glass or rough glass with their own defaults
+    const bool sub = type == "subsurface" || type == "kdsubsurface";
+    if (materialsOk_ && (type == "glass" || type == "uber" || type == "translucent" || type == "substrate" || sub)) {
         // CreateGlassMaterial (glass.cpp:94-110), CreateUberMaterial (uber.cpp:103-127), CreateTranslucentMaterial
-        // (translucent.cpp:82-98), CreateSubstrateMaterial (substrate.cpp:67-81): their defaults
+        // (translucent.cpp:82-98), CreateSubstrateMaterial (substrate.cpp:67-81), CreateSubsurfaceMaterial
+        // (subsurface.cpp:100-136), CreateKdSubsurfaceMaterial (kdsubsurface.cpp:100-123): their defaults
         bool ok = true;
         const auto spectrum = [&](const char *name, float *v, float d) {
             v[0] = v[1] = v[2] = d;
@@ -771,20 +807,29 @@ void Parser::MakeMaterial(Lexer &lx, int line, const std::string &type, const Pa
             return ps.FindOneFloat(name, d);
         };
         const auto eta = [&]() {
-            const float e = ps.Has("eta") ? number("eta", 1.5f) : number("index", 1.5f);
+            // (the subsurface materials read "eta" alone, default 1.33)
+            const float e = sub ? number("eta", 1.33f) : ps.Has("eta") ? number("eta", 1.5f) : number("index", 1.5f);
             if (!(e > 0.f) || !std::isfinite(e)) {
                 Error(lx, line, "%s \"eta\" must be finite and > 0", type.c_str());
                 ok = false;
             }
             return e;
         };
-        if (type == "glass") {
+        if (type == "glass" || sub) {
             spectrum("Kr", m->kr, 1.f);
             spectrum("Kt", m->kt, 1.f);
             m->eta = eta();
             m->uroughness = number("uroughness", 0.f);
             m->vroughness = number("vroughness", 0.f);
-            if (m->uroughness != 0.f || m->vroughness != 0.f) m->type = "roughglass";
+            m->type = (m->uroughness != 0.f || m->vroughness != 0.f) ? "roughglass" : "glass";
+            if (sub) {
+                // what only the BSSRDF reads: accepted and ignored (a texture is still reported)
+                float unused[3];
+                for (const char *name : {"sigma_a", "sigma_s", "Kd", "mfp"}) spectrum(name, unused, 0.f);
+                number("scale", 1.f);
+                number("g", 0.f);
+                ps.FindOneString("name", "");
+            }
         } else if (type == "uber") {
             spectrum("Kd", m->pkd, 0.25f);
             spectrum("Ks", m->ks, 0.25f);
@@ -828,6 +873,10 @@ void Parser::MakeMaterial(Lexer &lx, int line, const std::string &type, const Pa
         }
         ps.FindOneString("type", "");
         if (ok) {
+            if (sub)
+                Warning(lx, line, "Material \"%s\": the photon-beam integrator never reads the BSSRDF; the surface renders "
+                        "as its dielectric boundary (a %s of eta %g)", type.c_str(),
+                        m->type == "glass" ? "glass" : "rough glass", (double)m->eta);
             ReportUnused(lx, line, ps);
             return;
         }
@@ -963,8 +1012,54 @@ void Parser::MakeMaterial(Lexer &lx, int line, const std::string &type, const Pa
 
 // The table entry of a mirror, glass, plastic or metal material or of a matte with sigma (-1 for a matte with
 // sigma 0, which stays the triangle's own kd): entries are shared by equal materials
-int Parser::SpecularIndex(Lexer &lx, int line, const Material &m) {
-    const bool rough_matte = m.type == "matte" && m.sigma != 0.f;
+int Parser::SpecularIndex(Lexer &lx, int line, const Material &m, bool entry) {
+    const bool rough_matte = m.type == "matte" && (m.sigma != 0.f || entry);
+    if (m.type == "mix" && m.child[0] && m.child[1]) {
+        // the children go into the table before the mix; a table the library refuses (a child without a BSDF, a nest
+        // too deep, too many BxDFs) is reported in its words and the statement falls back to matte
+        bre_material_ex b;
+        memset(&b, 0, sizeof(b));
+        b.type = BRE_MATERIAL_MIX;
+        memcpy(b.amount, m.amount, sizeof(b.amount));
+        std::vector<bre_material_ex> &table = out_->materials;
+        const size_t before = table.size();
+        bool ok = true;
+        for (int k = 0; k < 2 && ok; ++k) {
+            b.mix_child[k] = SpecularIndex(lx, line, *m.child[k], true);
+            ok = b.mix_child[k] >= 0;
+        }
+        if (ok) {
+            for (size_t k = 0; k < table.size(); ++k)
+                if (memcmp(&table[k], &b, sizeof(b)) == 0) return (int)k;
+            ok = (int)table.size() < BRE_MAX_MATERIALS;
+            if (!ok) Error(lx, line, "more than BRE_MAX_MATERIALS (%d) table materials; using \"matte\"", BRE_MAX_MATERIALS);
+        }
+        if (ok) {
+            table.push_back(b);
+            char msg[256];
+            // the device-free check knows no media: an interface child is refused here, and any other interface entry
+            // of the table stands in as a matte (the setter checks it with the context's media)
+            std::vector<bre_material_ex> probe(table);
+            bool iface = false;
+            for (int k = 0; k < 2; ++k) iface = iface || table[(size_t)b.mix_child[k]].type == BRE_MATERIAL_INTERFACE;
+            for (bre_material_ex &e : probe)
+                if (e.type == BRE_MATERIAL_INTERFACE) {
+                    e.type = BRE_MATERIAL_MATTE;
+                    e.kd[0] = e.kd[1] = e.kd[2] = 0.5f;
+                }
+            if (iface) {
+                snprintf(msg, sizeof(msg), "material %d has a child that is a BRE_MATERIAL_INTERFACE, which has no BSDF to "
+                         "scale", (int)table.size() - 1);
+                ok = false;
+            } else {
+                ok = bre_check_material_table_ex(probe.data(), (int32_t)probe.size(), msg, (int32_t)sizeof(msg)) == BRE_OK;
+            }
+            if (ok) return (int)table.size() - 1;
+            Error(lx, line, "mix: %s; using \"matte\"", msg);
+        }
+        table.resize(before);  // entries added for this statement alone
+        return -1;
+    }
     const bool lobed = m.type == "roughglass" || m.type == "uber" || m.type == "translucent" || m.type == "substrate";
     if (m.type != "mirror" && m.type != "glass" && m.type != "plastic" && m.type != "metal" && !rough_matte && !m.none &&
         !lobed)

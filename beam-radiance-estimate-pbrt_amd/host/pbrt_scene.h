@@ -131,7 +131,10 @@ constexpr int kParseLights = 2;  // BRE_PBRT_LIGHTS
 // "translucent" and "substrate" become bre_material_ex records of types 8 .. 11 (2 for a smooth glass), direct or
 // named, with the defaults of the reference's Create...Material functions; without it the parse reports them as
 // before.  Texture-valued parameters and "bumpmap" are reported and the statement falls back to matte, as for the
-// other materials.
+// other materials.  Material "mix" (api.cpp:430-446) becomes a record of type 12 after the entries of its two named
+// materials (an undeclared one is a matte of the statement's own parameters; a table the library refuses is reported in
+// its words and the statement falls back to matte); "subsurface" and "kdsubsurface" become the glass or rough glass of
+// their dielectric boundary (Kr = Kt = 1, eta 1.33) with a warning: photonbeam.cpp never reads the BSSRDF.
 constexpr int kParseMaterials = 4;  // BRE_PBRT_MATERIALS
 struct SceneMedia {
     std::vector<bre_medium> media;             // grid_density points into `density`

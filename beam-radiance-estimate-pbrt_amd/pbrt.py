@@ -24,7 +24,8 @@ CLI_PATH = os.path.join(HERE, "host", "bre_pbrt")
 
 PBRT_MEDIA = 1  # BRE_PBRT_MEDIA
 PBRT_LIGHTS = 2  # BRE_PBRT_LIGHTS: LightSource "distant" and "point", two-sided area lights
-PBRT_MATERIALS = 4  # BRE_PBRT_MATERIALS: rough glass, direct Material "glass", "uber", "translucent", "substrate"
+PBRT_MATERIALS = 4  # BRE_PBRT_MATERIALS: rough glass, direct Material "glass", "uber", "translucent", "substrate", "mix",
+#                     "subsurface" / "kdsubsurface" (their dielectric boundary)
 EXPORTS = ["bre_pbrt_parse_file", "bre_pbrt_parse_string", "bre_pbrt_parse_file_ex", "bre_pbrt_parse_string_ex",
            "bre_pbrt_get_media", "bre_pbrt_free", "bre_pbrt_messages",
            "bre_pbrt_get_scene", "bre_pbrt_get_lights", "bre_pbrt_get_materials", "bre_pbrt_get_materials_ex", "bre_pbrt_make_spot_light", "bre_pbrt_get_render_params", "bre_pbrt_get_film", "bre_pbrt_render",

@@ -152,6 +152,24 @@ class MaterialEx(ctypes.Structure):
     def opacity(self, v):
         self.ceta = v
 
+    @property
+    def amount(self):
+        """A mix's "amount": the words of `kd`, which a mix never reads (the record's anonymous union)."""
+        return self.kd
+
+    @amount.setter
+    def amount(self, v):
+        self.kd = v
+
+    @property
+    def mix_child(self):
+        """A mix's two children, table indices: a view of reserved[0..1] (writable by index)."""
+        return (ctypes.c_int32 * 2).from_address(ctypes.addressof(self) + type(self).reserved.offset)
+
+    @mix_child.setter
+    def mix_child(self, v):
+        self.reserved[0], self.reserved[1] = int(v[0]), int(v[1])
+
 
 def widen(m) -> "MaterialEx":
     """A Material as the MaterialEx bre_set_materials makes of it; a MaterialEx as it is."""
@@ -227,6 +245,19 @@ def substrate(kd=0.5, ks=0.5, uroughness: float = 0.1, vroughness: float = 0.1, 
     m = MaterialEx()
     m.type, m.kd, m.ks = MATERIAL_SUBSTRATE, _rgb(kd), _rgb(ks)
     m.uroughness, m.vroughness, m.remap = float(uroughness), float(vroughness), int(bool(remap))
+    return m
+
+
+MATERIAL_MIX = 12
+MAX_MIX_DEPTH, MAX_BXDFS = 4, 8
+
+
+def mix(child1: int, child2: int, amount=0.5) -> MaterialEx:
+    """Material "mix" (mixmat.cpp:66-72): the table indices of "namedmaterial1" and "namedmaterial2", both earlier
+    entries of the table the record goes into, and "amount" (rgb or scalar, default 0.5): the first child's BxDFs
+    scaled by amount, then the second's by 1 - amount."""
+    m = MaterialEx()
+    m.type, m.amount, m.mix_child = MATERIAL_MIX, _rgb(amount), (int(child1), int(child2))
     return m
 
 

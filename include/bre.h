@@ -336,6 +336,12 @@ bre_status bre_set_materials_ex(bre_ctx *ctx, const bre_material_ex *materials, 
    text that follows "material k has " in the setter's error; message may be NULL).  For front ends that want to
    report a record before a context exists. */
 bre_status bre_check_material_ex(const bre_material_ex *material, char *message, int32_t capacity);
+/* A whole table as bre_set_materials_ex would check it on a context without media, with no context and no device:
+   every record as above, then the rules between records that a BRE_MATERIAL_MIX brings (its children earlier in the
+   table and not BRE_MATERIAL_INTERFACE, at most BRE_MAX_MIX_DEPTH mixes deep, at most BRE_MAX_BXDFS BxDFs after
+   expansion).  `message` receives the setter's text from "material k has " on. */
+bre_status bre_check_material_table_ex(const bre_material_ex *materials, int32_t n_materials, char *message,
+                                       int32_t capacity);
 
 /* ---- media bounded by surfaces (bre_medium, bre_scene.h; pbrt's MediumInterface) ----
    Copies the table media[0 .. n_media) with its density grids, the per-triangle pairs
@@ -523,7 +529,10 @@ bre_status bre_resolve_image(int64_t npix, const float *ld_rgb, int iteration, f
              uber, translucent or substrate entry.  Kind 13 with two more floats per record: aux as there, with
              types 4 .. 6 and 8 .. 11; x holds n / 11 records of 11 floats: the 9 of kind 13, then the transport
              mode (0: Importance, 1: Radiance) and the flag set (0: BSDF_ALL, 1: BSDF_ALL & ~BSDF_SPECULAR), used
-             by all three functions.  The same 12 words out.
+             by all three functions.  The same 12 words out.  aux may hold BRE_MATERIAL_MIX records and, as their
+             children, mirror and glass records: the table is then checked as bre_set_materials_ex checks it, the rules
+             between records included, and evaluated through the wide lobe lists of a mixed context; a record may name
+             any entry of type >= 4 (a mirror or a smooth glass is evaluated only as a mix's child).
    so the tests can hold them against the reference's own primitive tests (src/tests/fp_tests.cpp,
    find_interval.cpp), against the compiler's correctly rounded sqrt and division, and (kinds 10, 11)
    against a host restatement and validator of the hierarchy (tests/refpy_lbvh.py). */

@@ -45,7 +45,10 @@ bre_status bre_pbrt_parse_string(const char *text, bre_pbrt **out);
    all space cannot hold one: bound the medium with surfaces and add BRE_PBRT_MEDIA.
    BRE_PBRT_MATERIALS: Material "glass" with "uroughness" / "vroughness" (rough glass), "glass" as a direct
    statement, "uber", "translucent" and "substrate", direct or named, become bre_material_ex records of types 8 .. 11
-   (bre_pbrt_get_materials_ex) with the defaults of pbrt's Create...Material functions.  The flags combine.
+   (bre_pbrt_get_materials_ex) with the defaults of pbrt's Create...Material functions.  Material "mix" ("string
+   namedmaterial1", "string namedmaterial2", "rgb|float amount") becomes a record of type 12 behind its two children's
+   entries, and "subsurface" / "kdsubsurface" the glass or rough glass of their dielectric boundary, with one warning
+   (the integrator never reads the BSSRDF).  The flags combine.
    flags 0 is bre_pbrt_parse_file / _string, which keep refusing such scenes. */
 #define BRE_PBRT_MEDIA 1
 #define BRE_PBRT_LIGHTS 2

@@ -57,6 +57,12 @@
  *                       with BSDF_ALL, the photon pass in TransportMode::Importance and the camera pass in Radiance,
  *                       and EstimateDirect evaluates them with BSDF_ALL & ~BSDF_SPECULAR on both sides of the
  *                       surface (src/core/integrator.cpp:112-113).
+ *   - mix             (bre_material_ex type 12; MixMaterial, src/materials/mixmat.cpp), in the same table: two earlier
+ *                       entries of it on one surface.  Its BSDF holds the first child's BxDFs, then the second's, each
+ *                       a ScaledBxDF (reflection.cpp:97-110) under `amount` and max(1 - amount, 0), up to
+ *                       BRE_MAX_BXDFS of them; a child may itself be a mix, BRE_MAX_MIX_DEPTH deep.  A mirror or a
+ *                       smooth glass under a mix is one specular lobe among the others (SpecularReflection under
+ *                       FresnelNoOp, FresnelSpecular).
  *   - media bounded by surfaces (bre_medium below; pbrt's MediumInterface): a context holds a table of
  *                       media, a per-triangle (inside, outside) pair, the camera's medium and each delta
  *                       light's (bre_set_media, bre.h).  Every ray carries its medium; a triangle whose
@@ -208,13 +214,31 @@ typedef struct bre_material {
 #define BRE_MATERIAL_UBER 9         /* kd, ks, kr, kt, eta, roughness, uroughness, vroughness, remap, opacity */
 #define BRE_MATERIAL_TRANSLUCENT 10 /* kd, ks, kr ("reflect"), kt ("transmit"), roughness, remap */
 #define BRE_MATERIAL_SUBSTRATE 11   /* kd, ks, uroughness, vroughness, remap */
+/* - mix (MixMaterial, src/materials/mixmat.cpp:46-64): the BxDFs of table entry mix_child[0] ("namedmaterial1"), each
+     a ScaledBxDF under s1 = `amount`, then those of entry mix_child[1] ("namedmaterial2") under
+     s2 = max(1 - s1, 0) per channel.  A ScaledBxDF is added even where its scale is black: it counts in
+     NumComponents and takes its share of the samples.  Both children come earlier in the table (no cycles) and are
+     not BRE_MATERIAL_INTERFACE (no BSDF to scale); a child may be a mix, at most BRE_MAX_MIX_DEPTH mixes deep, and the
+     expanded BSDF holds at most BRE_MAX_BXDFS BxDFs (BSDF::MaxBxDFs, reflection.h:202; the reference aborts past it).
+     `amount` shares the storage of `kd` and `mix_child` that of reserved[0..1], neither of which a mix reads; every
+     other field is 0 in a mix record.  bre_set_materials (the narrow form) does not know it. */
+#define BRE_MATERIAL_MIX 12         /* amount, mix_child */
+#define BRE_MAX_MIX_DEPTH 4 /* a mix sits at most this many mixes deep (itself included) */
+#define BRE_MAX_BXDFS 8     /* BxDFs of an expanded mix */
 
 typedef struct bre_material_ex {
-    int32_t type;     /* BRE_MATERIAL_MIRROR .. BRE_MATERIAL_METAL, BRE_MATERIAL_ROUGH_GLASS .. BRE_MATERIAL_SUBSTRATE */
+    int32_t type;     /* BRE_MATERIAL_MIRROR .. BRE_MATERIAL_METAL, BRE_MATERIAL_ROUGH_GLASS .. BRE_MATERIAL_MIX */
     float kr[3];      /* as in bre_material; translucent: "reflect" */
     float kt[3];      /* translucent: "transmit" */
     float eta;        /* mirror / glass / rough glass / uber: finite and > 0; ignored by types 4 .. 6 */
-    float kd[3];      /* matte, plastic, uber, translucent, substrate: "Kd", clamped to [0, 1] */
+#if defined(__cplusplus) || (defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L)
+    union {
+        float kd[3];      /* matte, plastic, uber, translucent, substrate: "Kd", clamped to [0, 1] */
+        float amount[3];  /* mix: "amount", clamped to [0, 1] (pbrt's default is 0.5) */
+    };
+#else
+    float kd[3];      /* "Kd"; mix: "amount" */
+#endif
     float ks[3];      /* plastic, uber, translucent, substrate: "Ks", clamped to [0, 1] */
 #if defined(__cplusplus) || (defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L)
     union {
@@ -230,7 +254,14 @@ typedef struct bre_material_ex {
     float vroughness; /* metal, uber: "vroughness" (likewise); rough glass, substrate: "vroughness" */
     float sigma;      /* matte: "sigma" in degrees (clamped to [0, 90]; 0 = Lambertian) */
     int32_t remap;    /* every type with a roughness: "remaproughness" (0 / 1): roughness -> alpha by RoughnessToAlpha */
-    int32_t reserved[3]; /* 0 */
+#if defined(__cplusplus) || (defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L)
+    union {
+        int32_t reserved[3];  /* 0 (a mix: reserved[2] is 0) */
+        int32_t mix_child[2]; /* mix: the table indices of "namedmaterial1" and "namedmaterial2", both below its own */
+    };
+#else
+    int32_t reserved[3]; /* 0; mix: [0] and [1] are the table indices of its two children */
+#endif
 } bre_material_ex;    /* 112 bytes, no padding */
 #ifdef __cplusplus
 static_assert(sizeof(bre_material_ex) == 112, "bre_material_ex stays 112 bytes");
@@ -238,6 +269,10 @@ static_assert(offsetof(bre_material_ex, ceta) == 56 && offsetof(bre_material_ex,
               offsetof(bre_material_ex, ck) == 68 && offsetof(bre_material_ex, roughness) == 80 &&
               offsetof(bre_material_ex, remap) == 96 && offsetof(bre_material_ex, reserved) == 100,
               "bre_material_ex keeps every offset; opacity shares ceta's storage");
+static_assert(offsetof(bre_material_ex, kd) == 32 && offsetof(bre_material_ex, amount) == 32,
+              "amount shares kd's storage");
+static_assert(offsetof(bre_material_ex, mix_child) == 100 && sizeof(((bre_material_ex *)0)->mix_child) == 8,
+              "mix_child shares reserved[0..1]");
 #endif
 
 /* Media bounded by surfaces: pbrt's MediumInterface.  Like the lights and materials they are not part of
