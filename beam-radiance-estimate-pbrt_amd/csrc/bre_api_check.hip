@@ -121,10 +121,45 @@ extern "C" {
 bre_status bre_device_check(bre_ctx *c, int32_t kind, int64_t n, const float *x, int32_t n_aux, const float *aux,
                             float *y) {
     if (!c) return BRE_ERR_INVALID_ARG;
-    if (kind < 0 || kind > 14) return fail(c, BRE_ERR_INVALID_ARG, "bre_device_check: kind %d not in [0, 14]", kind);
+    if (kind < 0 || kind > 15) return fail(c, BRE_ERR_INVALID_ARG, "bre_device_check: kind %d not in [0, 15]", kind);
     if (kind == 10) return check_hierarchy(c, n, x, n_aux, aux, y);
     if (kind == 11) return check_read_tree(c, n, y);
     if (n < 0 || (n > 0 && (!x || !y))) return fail(c, BRE_ERR_INVALID_ARG, "bre_device_check: bad arrays");
+    if (kind == 15) {
+        // the packet records of the context's last tile launch (PacketRec, bre_packet.h) against the bundle and
+        // margin formed again from that launch's segments: x = n / 10 segments in the GATHERED order, 10 floats
+        // each (o, p, d, tmax); y[0] = the record words that differ, y[1] = the packets compared
+        if (n % 10 || n == 0) return fail(c, BRE_ERR_INVALID_ARG, "bre_device_check: kind 15 needs whole segments of 10 floats");
+        const int64_t ns = n / 10;
+        if (c->pktrec_nseg != ns || !c->pktrec.ptr)
+            return fail(c, BRE_ERR_STATE, "bre_device_check: kind 15: the context's last tile launch gathered %lld "
+                        "segments, not %lld", (long long)c->pktrec_nseg, (long long)ns);
+        BRE_TRY(set_device(c));
+        std::vector<float> soa((size_t)n);
+        float *ho = soa.data(), *hp = ho + 3 * ns, *hd = hp + 3 * ns, *ht = hd + 3 * ns;
+        for (int64_t i = 0; i < ns; ++i) {
+            for (int k = 0; k < 3; ++k) {
+                ho[3 * i + k] = x[10 * i + k];
+                hp[3 * i + k] = x[10 * i + 3 + k];
+                hd[3 * i + k] = x[10 * i + 6 + k];
+            }
+            ht[i] = x[10 * i + 9];
+        }
+        float *dx = nullptr;
+        unsigned int *dy = nullptr;
+        HIPCHK(c, c->chk_x.get((size_t)n, &dx));
+        HIPCHK(c, c->chk_y.get((size_t)1, &dy));
+        HIPCHK(c, hipMemcpyAsync(dx, soa.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemsetAsync(dy, 0, 4, c->stream));
+        const SegView sv{dx, dx + 3 * ns, dx + 6 * ns, dx + 9 * ns, nullptr};
+        HIPCHK(c, launch_packet_check(ns, sv, c->pktrec.as<PacketRec>(), dy, c->stream));
+        unsigned int bad = 0;
+        HIPCHK(c, hipMemcpyAsync(&bad, dy, 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        y[0] = (float)bad;
+        y[1] = (float)packet_count(ns);
+        return BRE_OK;
+    }
     if (kind == 12) {
         // the specular lobe of the photon and camera passes on records of 6 floats (layout: include/bre.h)
         if (n % 6) return fail(c, BRE_ERR_INVALID_ARG, "bre_device_check: kind 12 needs whole records of 6 floats");

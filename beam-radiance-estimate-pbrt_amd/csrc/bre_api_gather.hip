@@ -204,12 +204,9 @@ bre_status gather_device(bre_ctx *c, int64_t nseg, const SegView &seg, float R, 
     const bool rshard = c->shard_mode == 2 && c->shard_count > 1;
     const int S_eff = rshard ? (c->split + c->shard_count - 1) / c->shard_count : c->split;
     const size_t per_seg = (size_t)S_eff * (12 + (want_cnt ? 8 : 0));
-    int64_t chunk = c->partial_cap / (int64_t)per_seg / 64 * 64;
     // the exact stage addresses a launch's SegRec records with 32-bit byte offsets (BRE_BUF_LOADS):
-    // at most 2^26 segments (64 B each) per launch
-    if (chunk > ((int64_t)1 << 26)) chunk = (int64_t)1 << 26;
-    if (chunk < 64) chunk = 64;
-    if (chunk > nseg) chunk = nseg;
+    // at most 2^26 segments (64 B each) per launch (launch_chunk, bre_packet.h)
+    const int64_t chunk = launch_chunk(nseg, c->partial_cap, per_seg);
     int32_t *roots = nullptr;
     HIPCHK(c, c->roots.get(kMaxSplit + 1, &roots));
     HIPCHK(c, c->partial.get(3 * (size_t)chunk * (size_t)S_eff, &a.partial));
@@ -235,6 +232,7 @@ bre_status gather_device(bre_ctx *c, int64_t nseg, const SegView &seg, float R, 
         a.split = S_eff;
     }
     HIPCHK(c, c->segrec.get((size_t)((chunk + 63) / 64 * 64), &a.segrec));  // whole packets
+    HIPCHK(c, c->pktrec.get((size_t)packet_count(chunk), &a.pktrec));        // one record per packet of a launch
     if (want_cnt) HIPCHK(c, c->pcnt.get(2 * (size_t)chunk * (size_t)S_eff, &a.pcnt));
     if (c->tile_axis && a.leaf_size > 0) {
         const int64_t ntiles = (c->nvalid + a.leaf_size - 1) / a.leaf_size;
@@ -258,6 +256,7 @@ bre_status gather_device(bre_ctx *c, int64_t nseg, const SegView &seg, float R, 
         else
             ac.out = out.slice(off);
         HIPCHK(c, launch_gather_tile(ac, c->counters, c->stream));
+        c->pktrec_nseg = ac.nseg;  // what the packet records hold now (bre_device_check kind 15)
     }
     c->tile_ev_valid = true;
     if (c->timing) HIPCHK(c, hipEventRecord(c->ev[3], c->stream));

@@ -225,6 +225,7 @@ struct bre_ctx {
     int kernel = 0, leaf_size = 1, sqrt_mode = 0, split = 256, leaf2 = 64, chunk_len = 400, chunk_leaf = 1;
     int shard_rank = 0, shard_count = 1, shard_block = 1, shard_mode = 0, film_classes = 1;
     int stack_cap = 0, occupancy = 6, sort_key = 4, block_map = 3, tscan = -1;         // 101, 102, 105, 107, 108
+    int64_t pktrec_nseg = 0;  // segments of the last tile launch: its packets' records are in `pktrec`
     int64_t partial_cap = (int64_t)4 << 30;                                            // 109, in bytes
     int beam_key = 2, margin = 1, tile_axis = 1, split_records = 0, film_compose = 1;  // 110 .. 114
     int photon_single = 1, pass_priority = 1, kernel_readback = BRE_KERNEL_READBACK;   // 116 .. 118
@@ -246,7 +247,7 @@ struct bre_ctx {
     // gather
     bre::SegArrays g;  // staging of the host-pointer API; g.pix only with a seg_pixel array
     bre::DevMem g_accum, g_seg_rgb, g_counts;  // each only when the caller passes that output
-    bre::DevMem counters_buf, roots, roots_sh, roots_tmp, partial, pcnt, segrec, tileax, segbox, nodes4;
+    bre::DevMem counters_buf, roots, roots_sh, roots_tmp, partial, pcnt, segrec, pktrec, tileax, segbox, nodes4;
     // kernel 5: capsule-chunk index, rebuilt per gather (bre_chunk.hip)
     bre::DevMem ch_bounds, ch_counts, ch_offsets, ch_range, ch_scan_tmp, ch_box, ch_cent, ch_slo, ch_shi, ch_par,
         ch_recs, ch_cpar, ch_nodes;

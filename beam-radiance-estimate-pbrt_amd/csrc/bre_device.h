@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "bre_packet.h"
 #include "bre_views.h"
 
 namespace bre {
@@ -189,6 +190,7 @@ struct GatherArgs {
     float *partial;        // [split][nseg][3]
     int32_t *pcnt;         // [split][nseg][2] per-subtree counts (counters / contribution counting)
     SegRec *segrec;        // [nseg] tile kernel: per-segment records (written by k_seg_prep)
+    PacketRec *pktrec = nullptr;  // [packet_count(nseg)] tile kernel: per-packet records (written by k_packet_prep)
     bool prefilter;
     int occupancy;         // tile kernel register budget: min waves per SIMD (1, 6, 7 or 8)
     int stack_cap;         // traversal stack entries to use (0 = all); tests force an overflow
@@ -318,6 +320,10 @@ struct PacketPick {
 };
 hipError_t launch_packet_pick(const PacketPick &k, hipStream_t st);
 
+// bre_device_check kind 15 (bre_gather.hip): a wave per packet forms the packet's bundle and margin again and
+// compares the stored record word for word; bad[0] += the words that differ
+hipError_t launch_packet_check(int64_t nseg, const SegView &seg, const PacketRec *pktrec, unsigned int *bad,
+                               hipStream_t s);
 // device self-check of the shared scalar primitives (bre_check.hip, bre_device_check)
 hipError_t launch_device_check(int kind, int64_t n, const float *x, int n_aux, const float *aux, float *y,
                                hipStream_t s);

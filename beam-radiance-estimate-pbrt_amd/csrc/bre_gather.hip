@@ -611,8 +611,11 @@ __global__ __launch_bounds__(kTileBlock, MINW) void k_gather_tile(
     int32_t *__restrict__ pcnt_arg, const BeamRec *__restrict__ recs, const float4 *__restrict__ pw, BeamSet bset_arg,
     const Node *__restrict__ nodes, const Node4 *__restrict__ nodes4, int64_t nvalid, int leaf_size_arg,
     const int32_t *__restrict__ roots, int S, DevCounters *ctr, int stack_cap, int prefilter_arg, int map_arg, int tscan,
-    int margin_arg, const TileAxis *__restrict__ tax) {
+    int margin_arg, const TileAxis *__restrict__ tax, const PacketRec *__restrict__ pkr, float inv_maxd_arg) {
     constexpr bool FIXED = CFG::kFixed;
+    // PREP: the packet's bundle comes from its record (PacketRec).  The seven-wave specialised instantiation
+    // only: the six-wave one is kept for comparisons (internal option 124) with the text and the registers it had.
+    constexpr bool PREP = FIXED && MINW == 7;
     static_assert(!(FIXED && COUNT), "the counting instantiation is generic");
     // (constant expressions when FIXED: the branches on them below are decided at compile time)
     const int prefilter = FIXED ? CFG::kPrefilter : prefilter_arg;
@@ -656,21 +659,25 @@ __global__ __launch_bounds__(kTileBlock, MINW) void k_gather_tile(
     Lane L;
     bool valid;
     if constexpr (FIXED) {
-        // the lane's values as k_seg_prep stored them from the same load_lane (SegRec planes 0 to 2: the
+        // the lane's values as k_seg_prep stored them from the same load_lane (SegRec planes 0 and 2: the
         // same bits without the wave's three divisions, its square root and the raw o / p / tmax arrays);
-        // 1 / d is not loaded here: the walk reads it from plane 3 at every visit
+        // 1 / d is not loaded here: the walk reads it from plane 3 at every visit.  p, d and |A| feed the
+        // packet bundle and the lane margin only: not loaded where those come from the packet's record.
         zero_lane(L);
         valid = s < nseg;
         if (valid) {
             const float4 *q = seg_plane(srec, s, 0);
-            const float4 a0 = q[0], a1 = q[64], a2 = q[128];
+            const float4 a0 = q[0], a2 = q[128];
             L.o = mk(a0.x, a0.y, a0.z);
             L.tmax = a0.w;
-            L.p = mk(a1.x, a1.y, a1.z);
-            L.mag_a = fabsf(a1.w);
             L.au = mk(a2.x, a2.y, a2.z);
-            L.d = mk(sd[3 * s], sd[3 * s + 1], sd[3 * s + 2]);
-            L.omax = fmaxf(fmaxf(fabsf(L.o.x), fabsf(L.o.y)), fabsf(L.o.z)) + L.mag_a;
+            if constexpr (!PREP) {
+                const float4 a1 = q[64];
+                L.p = mk(a1.x, a1.y, a1.z);
+                L.mag_a = fabsf(a1.w);
+                L.d = mk(sd[3 * s], sd[3 * s + 1], sd[3 * s + 2]);
+                L.omax = fmaxf(fmaxf(fabsf(L.o.x), fabsf(L.o.y)), fabsf(L.o.z)) + L.mag_a;
+            }
         }
     } else {
         valid = load_lane(s, nseg, so, sp_, sd, stmax, L);
@@ -678,13 +685,41 @@ __global__ __launch_bounds__(kTileBlock, MINW) void k_gather_tile(
     Bundle K;
     K.delta = FLT_MAX;
     K.gbox = FLT_MAX;
-    if (prefilter && __ballot(valid) != 0ull) K = make_bundle(L, valid);
-    const ScanLane SL = make_scan_lane(L, margin);
-    // the largest lane margin Al' of the packet, folded into every beam's threshold at staging (a
-    // zero-length segment, Al' = FLT_MAX, is never rejected anyway: see scan_need)
-    const float al_max = uniform_f(wave_max(valid && SL.al < FLT_MAX ? SL.al : 0.f));
-    // 1 / MaxDistance of a uniform-radius set, correctly rounded, once per wave (tile_exact)
-    const float inv_maxd = bset.uniform ? uniform_f(1.0f / (R + bset.radius)) : 0.f;
+    float al_max, inv_maxd;
+    ScanLane SL;
+    if constexpr (PREP) {
+        // The packet's bundle and largest lane margin, formed once per packet by k_packet_prep with
+        // make_bundle and make_scan_lane themselves (the same lanes, the same reductions, the same bits)
+        // instead of once per (packet, work root) wave: scalar loads of the launch's packet seg0 / 64.
+        // 1 / MaxDistance is the launch's: one correctly rounded division on the host (launch_gather_tile).
+        const PacketRec &P = pkr[packet_index(seg0)];
+        K.co = mk(P.co[0], P.co[1], P.co[2]);
+        K.cu = mk(P.cu[0], P.cu[1], P.cu[2]);
+        K.delta = P.delta;
+        K.omax = P.omax;
+        K.s0 = P.s0;
+        K.s1 = P.s1;
+        K.gbox = P.gbox;
+        K.icu = mk(P.icu[0], P.icu[1], P.icu[2]);
+        K.q = mk(P.q[0], P.q[1], P.q[2]);
+        K.col1 = P.col1;
+        al_max = P.al_max;
+        inv_maxd = inv_maxd_arg;
+        // HAZARD: in this instantiation L holds o, tmax and au only.  L.p, L.d, L.mag_a and L.omax are
+        // zero_lane's zeros, so the Al' make_scan_lane forms here is wrong and is dropped (only q = o x au, which
+        // needs o and au alone, is kept).  Nothing after the entry may read those fields or SL.al: a later use would
+        // read zeros in the seven-wave kernel only.  What needs them belongs in make_packet_rec and the record.
+        SL.q = make_scan_lane(L, margin).q;
+        SL.al = 0.f;
+    } else {
+        if (prefilter && __ballot(valid) != 0ull) K = make_bundle(L, valid);
+        SL = make_scan_lane(L, margin);
+        // the largest lane margin Al' of the packet, folded into every beam's threshold at staging (a
+        // zero-length segment, Al' = FLT_MAX, is never rejected anyway: see scan_need)
+        al_max = uniform_f(wave_max(valid && SL.al < FLT_MAX ? SL.al : 0.f));
+        // 1 / MaxDistance of a uniform-radius set, correctly rounded, once per wave (tile_exact)
+        inv_maxd = bset.uniform ? uniform_f(1.0f / (R + bset.radius)) : 0.f;
+    }
     sh.acc[lane] = make_float4(0.f, 0.f, 0.f, 0.f);
     __builtin_amdgcn_wave_barrier();
     int cand = 0;
@@ -1072,6 +1107,73 @@ __global__ __launch_bounds__(kPassBlock) void k_seg_prep(int64_t nseg, const flo
     q[192] = make_float4(L.invs.x, L.invs.y, L.invs.z, L.mag_a != 0.0f ? 1.0f / L.mag_a : 0.0f);
 }
 
+// The packet's record (PacketRec, bre_packet.h) from its 64 lanes: make_bundle and make_scan_lane on the
+// lanes load_lane gives, the very calls the generic tile kernel makes per (packet, work root) wave, at the
+// specialised kernel's constants (prefilter on, margin mode 1).  All lanes of the wave must call; every lane
+// returns the same record.
+__device__ __forceinline__ PacketRec make_packet_rec(int64_t s, int64_t nseg, const float *__restrict__ so,
+                                                     const float *__restrict__ sp_, const float *__restrict__ sd,
+                                                     const float *__restrict__ stmax) {
+    Lane L;
+    const bool valid = load_lane(s, nseg, so, sp_, sd, stmax, L);
+    Bundle K;
+    K.delta = FLT_MAX;
+    K.gbox = FLT_MAX;
+    K.co = K.cu = K.icu = K.q = mk(0.f, 0.f, 0.f);
+    K.omax = K.s0 = K.s1 = K.col1 = 0.f;
+    if (__ballot(valid) != 0ull) K = make_bundle(L, valid);
+    const ScanLane SL = make_scan_lane(L, TileProd::kMargin);
+    PacketRec P;
+    P.co[0] = K.co.x, P.co[1] = K.co.y, P.co[2] = K.co.z;
+    P.cu[0] = K.cu.x, P.cu[1] = K.cu.y, P.cu[2] = K.cu.z;
+    P.delta = K.delta;
+    P.omax = K.omax;
+    P.s0 = K.s0;
+    P.s1 = K.s1;
+    P.gbox = K.gbox;
+    P.icu[0] = K.icu.x, P.icu[1] = K.icu.y, P.icu[2] = K.icu.z;
+    P.q[0] = K.q.x, P.q[1] = K.q.y, P.q[2] = K.q.z;
+    P.col1 = K.col1;
+    P.al_max = uniform_f(wave_max(valid && SL.al < FLT_MAX ? SL.al : 0.f));
+    P.pad = 0.f;
+    return P;
+}
+
+// One PacketRec per 64-segment packet of the launch, one wave per packet, beside k_seg_prep: once per
+// launch instead of once per (packet, work root) wave of the specialised tile kernel.  A one-wave workgroup
+// within the pass chain's budget (seven waves per SIMD, no LDS).
+__global__ __launch_bounds__(64, 7) void k_packet_prep(int64_t nseg, const float *__restrict__ so,
+                                                       const float *__restrict__ sp_, const float *__restrict__ sd,
+                                                       const float *__restrict__ stmax, PacketRec *__restrict__ out) {
+    const int64_t s = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    const PacketRec P = make_packet_rec(s, nseg, so, sp_, sd, stmax);
+    // lane w stores word w of the record
+    const float *w = reinterpret_cast<const float *>(&P);
+    float v = 0.f;
+#pragma unroll
+    for (int k = 0; k < kPacketRecWords; ++k) v = (int)threadIdx.x == k ? w[k] : v;
+    if ((int)threadIdx.x < kPacketRecWords)
+        reinterpret_cast<float *>(out + blockIdx.x)[threadIdx.x] = v;
+}
+
+// bre_device_check kind 15: the stored records against the bundle and margin formed again, word for word
+__global__ __launch_bounds__(64) void k_packet_check(int64_t nseg, const float *__restrict__ so,
+                                                     const float *__restrict__ sp_, const float *__restrict__ sd,
+                                                     const float *__restrict__ stmax,
+                                                     const PacketRec *__restrict__ in, unsigned int *__restrict__ bad) {
+    const int64_t s = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    const PacketRec P = make_packet_rec(s, nseg, so, sp_, sd, stmax);
+    const unsigned int *w = reinterpret_cast<const unsigned int *>(&P);
+    unsigned int v = 0u;
+#pragma unroll
+    for (int k = 0; k < kPacketRecWords; ++k) v = (int)threadIdx.x == k ? w[k] : v;
+    bool differs = false;
+    if ((int)threadIdx.x < kPacketRecWords)
+        differs = reinterpret_cast<const unsigned int *>(in + blockIdx.x)[threadIdx.x] != v;
+    const int n = __popcll(__ballot(differs));
+    if (threadIdx.x == 0 && n != 0) atomicAdd(bad, (unsigned int)n);
+}
+
 // Sum the per-subtree partials of each segment in subtree order; write seg_rgb and add the
 // segment's sum to its pixel (one float atomic per channel, PhotonBeamPixel::Ld +=).  With counts,
 // also sum the per-subtree candidate / contribution counts (candidates -1: not counted).  seg_index
@@ -1160,10 +1262,12 @@ hipError_t launch_gather_tile(const GatherArgs &a, bool counters, hipStream_t s)
     // per-subtree counts: candidates + contributions with counters, contributions alone otherwise
     int32_t *pcnt = (counters || a.out.seg_counts) ? a.pcnt : nullptr;
     if ((counters || a.out.seg_counts) && !pcnt) return hipErrorInvalidValue;
-    if (!a.segrec || a.leaf_size > 64) return hipErrorInvalidValue;
+    if (!a.segrec || !a.pktrec || a.leaf_size > 64) return hipErrorInvalidValue;
     if (!a.nodes4) return hipErrorInvalidValue;  // the 4-wide walk needs the collapsed view
     hipLaunchKernelGGL(k_seg_prep, dim3((unsigned int)((a.nseg + kPassBlock - 1) / kPassBlock)), dim3(kPassBlock), 0, s, a.nseg, a.seg.o, a.seg.p, a.seg.d,
                        a.seg.t, a.segrec);
+    hipLaunchKernelGGL(k_packet_prep, dim3((unsigned int)packet_count(a.nseg)), dim3(64), 0, s, a.nseg, a.seg.o, a.seg.p,
+                       a.seg.d, a.seg.t, a.pktrec);
     const TileAxis *tax = nullptr;
     if (a.tileax && a.segbox && a.prefilter && a.nvalid > 0) {
         const hipError_t ea = launch_tile_axis(a, s);
@@ -1190,11 +1294,15 @@ hipError_t launch_gather_tile(const GatherArgs &a, bool counters, hipStream_t s)
                        a.margin == TileProd::kMargin && block_map == TileProd::kMap &&
                        a.leaf_size == TileProd::kLeaf && tax != nullptr && a.bset.uniform != 0;
     if (a.tile_variant) *a.tile_variant = fixed ? 2 : 1;
+    // 1 / MaxDistance of a uniform-radius set for the specialised instantiation: the float sum and the one
+    // correctly rounded float division the generic kernel performs per wave (1.0f / (R + radius))
+    const float maxd = a.R + a.bset.radius;
+    const float inv_maxd = a.bset.uniform ? 1.0f / maxd : 0.f;
 #define BRE_LAUNCH_TILE(C, W, CFG)                                                                               \
     hipLaunchKernelGGL((k_gather_tile<C, W, CFG>), grid4, dim3(kTileBlock), 0, s, a.nseg, a.seg.o, a.seg.p,      \
                        a.seg.d, a.seg.t, a.segrec, a.R, a.partial, pcnt, a.recs, a.pow, a.bset, a.nodes,         \
                        a.nodes4, a.nvalid, a.leaf_size, a.roots, a.split, a.ctr, stack_cap, (int)a.prefilter,    \
-                       block_map, a.tscan, a.margin, tax)
+                       block_map, a.tscan, a.margin, tax, a.pktrec, inv_maxd)
     if (counters) {
         BRE_LAUNCH_TILE(true, 1, TileGeneric);
     } else if (fixed && a.tile_budget == 7) {
@@ -1227,6 +1335,14 @@ hipError_t launch_gather_tile(const GatherArgs &a, bool counters, hipStream_t s)
     }
     hipLaunchKernelGGL(k_reduce, dim3((unsigned int)((a.nseg + kPassBlock - 1) / kPassBlock)), dim3(kPassBlock), 0, s, a.nseg, a.partial, pcnt,
                        a.roots, a.split, a.seg.pix, a.npix, a.out.accum, a.out.seg_rgb, a.out.seg_counts, a.seg_index, a.ctr);
+    return hipGetLastError();
+}
+
+hipError_t launch_packet_check(int64_t nseg, const SegView &seg, const PacketRec *pktrec, unsigned int *bad,
+                               hipStream_t s) {
+    if (nseg <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_packet_check, dim3((unsigned int)packet_count(nseg)), dim3(64), 0, s, nseg, seg.o, seg.p, seg.d,
+                       seg.t, pktrec, bad);
     return hipGetLastError();
 }
 

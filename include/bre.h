@@ -533,6 +533,13 @@ bre_status bre_resolve_image(int64_t npix, const float *ld_rgb, int iteration, f
              children, mirror and glass records: the table is then checked as bre_set_materials_ex checks it, the rules
              between records included, and evaluated through the wide lobe lists of a mixed context; a record may name
              any entry of type >= 4 (a mirror or a smooth glass is evaluated only as a mix's child).
+     kind 15: the per-packet records of the context's last tile-kernel launch (one per 64 gathered segments:
+             the packet bundle and the packet's largest lane margin, which the specialised tile kernel reads
+             instead of forming them in every wave).  x holds that launch's n / 10 segments in the GATHERED order
+             (the caller's with BRE_OPT_SORT_SEGMENTS 0 and no packet shard), 10 floats each: o (xyz), p (xyz),
+             d (xyz), tmax.  A wave per packet forms the record again and compares the stored one word for
+             word: y[0] receives the number of words that differ, y[1] the number of packets compared.
+             BRE_ERR_STATE if the last launch gathered another number of segments.
    so the tests can hold them against the reference's own primitive tests (src/tests/fp_tests.cpp,
    find_interval.cpp), against the compiler's correctly rounded sqrt and division, and (kinds 10, 11)
    against a host restatement and validator of the hierarchy (tests/refpy_lbvh.py). */
